@@ -24,11 +24,17 @@ recipe (random-init) weights, fp32-accurate arithmetic.
   --workload cfg2  BASELINE configs[1] (MossFormer2 only, 32 x 4 s) — the H1 kernel measurement of round 1.
   --workload cfg3  BASELINE configs[2] (600 s, H1 + H2 + cosine).
   --dry-run        N-rank plumbing on the CPU (gloo, kernels skipped, fabricated embeddings): tests only.
+  --dump-outputs DIR  after the timed steps, what the last timed step handed back (separated streams as a seeded sample,
+                   embeddings, scores, tokens, ...) as DIR/<name>.npy in float32 / float64; inputs are seeded, so two builds
+                   run with the same arguments can be compared output for output.
 
-Output: ONE JSON line on rank 0 (driver contract) with
+Output: ONE JSON line on rank 0 (driver contract): metric, value, unit, higher_is_better, dtype, ms_per_step (mean wall
+time of one timed step) and the workload.  A plain run does only what that line needs: set-up, warm-up, the timed steps.
+With --full the default workloads (cfg3 / cfg4 / cfg5) also measure, after the headline:
   roofline     — the dominant kernel (to_hidden+to_qk GEMM of MossFormer2, 24 launches per forward):
                  algorithmic FLOPs per launch / mean launch duration from HIP events recorded around that launch
                  on the forward's stream inside the timed region (tdx_mf2_profile_*).
+  pcie_inclusive, stage_ms_per_step_rank0 — extra untimed steps: input from pinned host memory, per-stage events.
   cpu_baseline — the oracle chain (CPU restatement of the reference: separator + fbank + ERes2NetV2 + SANM
                  encoder) timed on this host's cores on a bounded sample of the same workload (rank 0, N=1).
 """
@@ -62,6 +68,44 @@ FUSION_NOTE = ("since round 3 this launch also does the work of round 2's conv17
                "the two separate launches together ran 12.8 + 7.9 ms per 90-window launch of the default workload (profiles/r03_b_kernel_stats_cfg4_default_bench.csv) "
                "= 194 TFLOP/s on the same definition (DESIGN 4.1g, 5)")
 WINDOW = 160000
+DUMP_MAX_SAMPLES = 1 << 22       # --dump-outputs keeps a seeded sample of 4 Mi samples (16 MB) of longer separated audio
+
+
+def seeded_sample(a: np.ndarray, n_max: int, seed: int = 0) -> np.ndarray:
+    """`a` itself when it holds at most n_max elements, else the elements at fixed seeded positions (sorted, flat): the positions
+    depend only on a.size, n_max and the seed"""
+    if a.size <= n_max:
+        return a
+    idx = np.unique(np.random.default_rng(seed).integers(0, a.size, n_max))
+    return a.reshape(-1)[idx]
+
+
+def hotpath_outputs(out) -> dict:
+    """HotPath.run's results as flat arrays: the separated streams (utterances in order, stream 0 then 1, concatenated; a seeded
+    sample), embeddings, scores, the target embedding and cluster labels where present, and over the recognised segments (streams
+    in order) the tokens, their scores and timestamps and the punctuated text as code points"""
+    arr = {"streams": seeded_sample(np.concatenate([s for pair in out["streams"] for s in pair]), DUMP_MAX_SAMPLES)}
+    for k in ("embeddings", "scores", "target_embedding", "cluster_labels"):
+        if k in out:
+            arr[k] = out[k]
+    if "asr" in out:
+        segs = [seg for stream in out["asr"] for seg in stream]
+        arr["asr_tokens_per_segment"] = [len(s["token_ids"]) for s in segs]
+        arr["asr_token_ids"] = [t for s in segs for t in s["token_ids"]]
+        arr["asr_token_scores"] = [x for s in segs for x in s["scores"]]
+        arr["asr_timestamps_ms"] = np.asarray([ts for s in segs for ts in s["timestamp"]], dtype=np.float64).reshape(-1, 2)
+        if any("text" in s for s in segs):
+            arr["punc_text_lengths"] = [len(s["text"]) for s in segs]
+            arr["punc_text_codepoints"] = [ord(c) for s in segs for c in s["text"]]
+    return arr
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as <path>/<name>.npy, float32 where the result is float32, float64 otherwise"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
 
 
 def synth_mixtures(batch: int, n: int, seed: int) -> np.ndarray:
@@ -295,7 +339,8 @@ def pipe_bench(args):
             print(f"[bench] warmup {k + 1}/{args.warmup}", file=sys.stderr, flush=True)
     sep = hp.ap.separater
     launches_per_step = 24 * ((windows_local + args.windows_per_launch - 1) // args.windows_per_launch)
-    sep.profile_enable(launches_per_step * args.steps)
+    if args.full:
+        sep.profile_enable(launches_per_step * args.steps)
     barrier()
     t0 = time.perf_counter()
     step_s = []
@@ -305,17 +350,20 @@ def pipe_bench(args):
         step_s.append(time.perf_counter() - t1)
     barrier()
     dt = time.perf_counter() - t0
-    gemm_ms, gemm_launches = sep.profile_collect()
+    if args.full:
+        gemm_ms, gemm_launches = sep.profile_collect()
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     assert np.isfinite(out["embeddings"]).all() and np.isfinite(out["scores"]).all()
     assert out["embeddings"].shape[0] == out["scores"].shape[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hotpath_outputs(out))
     d2h_bytes = out.get("d2h_bytes", 0)
     # PCIe-inclusive figure (never `value`): the same step with its input coming from page-locked HOST memory (H2D + step + D2H)
     pcie = None
-    if rank == 0 or use_dist:
+    if args.full and (rank == 0 or use_dist):
         host_in = [u.cpu().pin_memory() for u in batches[0]]
         barrier()
         t1 = time.perf_counter()
@@ -328,7 +376,7 @@ def pipe_bench(args):
 
     # one extra, untimed, instrumented step: per-stage times (events around the stages) and FLOP accounting
     stage_ms = None
-    if rank == 0:
+    if args.full and rank == 0:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         utts = batches[0]
         torch.cuda.synchronize(dev)
@@ -363,30 +411,6 @@ def pipe_bench(args):
     if rank == 0:
         value = audio_s_per_step * args.steps / dt
         print(f"[bench] gpu: {dt / args.steps * 1e3:.1f} ms/step, RTF {value:.1f}", file=sys.stderr, flush=True)
-        S = (WINDOW - 16) // 8 + 1
-        F = 1 + (WINDOW - 400) // 160
-        # algorithmic FLOPs of the step on THIS rank (rank 0's shard; shards differ by at most one utterance)
-        n_win_rank = windows_local
-        fl = {"separation": sep.flops(1, WINDOW) * n_win_rank}
-        if embed_segment:
-            fl["embedding"] = hp.spk.model.flops(2 * n_win_rank, F)
-            fl["asr_encoder"] = hp.asr.flops(2 * n_win_rank // 3, ((1 + (3 * WINDOW - 400) // 160) + 5) // 6) if with_asr else 0.0
-        else:
-            F30 = 1 + (3 * WINDOW - 400) // 160
-            fl["embedding"] = hp.spk.model.flops(2 * n_win_rank // 3, F30)
-            fl["asr_encoder"] = hp.asr.flops(2 * n_win_rank // 3, (F30 + 5) // 6) if with_asr else 0.0
-        # dominant kernel: every timed launch covers min(windows_per_launch, remaining) windows; report per FULL launch
-        rows_total = args.steps * n_win_rank * S              # token rows through the GEMM over the timed region (x 24 layers)
-        gemm_flops_total = 2.0 * rows_total * 512 * 2176 * 24
-        ach = gemm_flops_total / (gemm_ms * 1e-3) / 1e12 if gemm_launches else None
-        full_rows = min(args.windows_per_launch, n_win_rank) * S
-        traffic, mfma_util, clock_held, traffic_note = recorded_pmc(full_rows)
-        n1_ref = None
-        if wl == "cfg5" and world > 1:            # the same workload on ONE GPU, measured this round (the N = 1 default line is configs[3])
-            f = os.path.join(ROOT, "profiles", "r03_bench_cfg5_n1.json")
-            if os.path.exists(f):
-                j = json.loads(open(f).read().strip().splitlines()[-1])
-                n1_ref = {"value": j["value"], "ms_per_step": j["ms_per_step"], "source": "profiles/r03_bench_cfg5_n1.json (`bench.py --workload cfg5`, 1 x MI355X, this round)"}
         line = {
             "metric": METRIC, "value": value, "unit": "audio-s/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "ms_per_step_median": float(np.median(step_s)) * 1e3, "higher_is_better": True,
@@ -394,34 +418,61 @@ def pipe_bench(args):
             "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
             "config": {"workload": desc, "audio_seconds_per_step": audio_s_per_step, "windows_per_launch": args.windows_per_launch,
                        "parallelism": f"{world} rank(s), one process per GPU, utterances sharded round-robin, full weight replica per rank"},
-            "roofline": {"bound": "mfma", "achieved": ach, "peak": PEAK_H3_TFLOPS, "unit": "TFLOP/s",
-                         "frac": (ach / PEAK_H3_TFLOPS) if ach else None, "traffic": traffic, "kernel": KERNEL, "fusion_note": FUSION_NOTE,
-                         "peak_note": "algorithmic fp32-accurate FLOP/s ceiling of the kernel = dense f16 MFMA peak 2500 / 3 passes",
-                         "mfma_pipe_executed_tflops": (ach * H3_PASSES) if ach else None,
-                         "launches_timed": gemm_launches, "ms_per_launch": gemm_ms / max(gemm_launches, 1),
-                         "algorithmic_flops_per_launch": 2.0 * full_rows * 512 * 2176,
-                         "token_rows_per_full_launch": full_rows,
-                         "pmc_recorded_mfma_pipe_utilisation": mfma_util,
-                         "pmc_recorded_clock_GHz": clock_held,     # the chip is power-limited under this load: the peak above assumes 2.4 GHz
-                         "frac_of_peak_at_recorded_clock": (ach / (PEAK_H3_TFLOPS * clock_held / 2.4)) if (ach and clock_held) else None,      # SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x busy cycles), recorded pass
-                         "traffic_source": "pmc_recorded (not measured by this run)" if traffic is not None else None,
-                         "traffic_note": traffic_note,
-                         "whole_path_tflops_per_gpu": sum(fl.values()) * args.steps / dt / 1e12,
-                         "whole_path_frac": sum(fl.values()) * args.steps / dt / 1e12 / PEAK_H3_TFLOPS},
             "timed_region": "inputs resident in HBM -> all launches -> D2H of the results (streams, embeddings, scores, tokens) into pinned host memory",
-            "pcie_inclusive": pcie,
-            "same_workload_n1": n1_ref,
-            "stage_ms_per_step_rank0": stage_ms,
             "peak_device_memory_gib_rank0": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1),
-            "stage_tflops_rank0": {k: (fl[a] / (stage_ms[k] * 1e-3) / 1e12 if stage_ms[k] > 0 else None)
-                                   for k, a in (("separation+loudness", "separation"), ("embedding+cosine", "embedding"), ("asr_encoder+decoder", "asr_encoder"))},
-            "algorithmic_flops_per_step_rank0": fl,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            if sample_window is None:
-                sample_window = batches[0][0][:WINDOW].cpu().numpy()
-            line["cpu_baseline"] = cpu_baseline_pipe(sep_sd, spk_sd, asr_sd, sample_window, with_asr)
-            line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
+        if args.full:
+            S = (WINDOW - 16) // 8 + 1
+            F = 1 + (WINDOW - 400) // 160
+            # algorithmic FLOPs of the step on THIS rank (rank 0's shard; shards differ by at most one utterance)
+            n_win_rank = windows_local
+            fl = {"separation": sep.flops(1, WINDOW) * n_win_rank}
+            if embed_segment:
+                fl["embedding"] = hp.spk.model.flops(2 * n_win_rank, F)
+                fl["asr_encoder"] = hp.asr.flops(2 * n_win_rank // 3, ((1 + (3 * WINDOW - 400) // 160) + 5) // 6) if with_asr else 0.0
+            else:
+                F30 = 1 + (3 * WINDOW - 400) // 160
+                fl["embedding"] = hp.spk.model.flops(2 * n_win_rank // 3, F30)
+                fl["asr_encoder"] = hp.asr.flops(2 * n_win_rank // 3, (F30 + 5) // 6) if with_asr else 0.0
+            # dominant kernel: every timed launch covers min(windows_per_launch, remaining) windows; report per FULL launch
+            rows_total = args.steps * n_win_rank * S              # token rows through the GEMM over the timed region (x 24 layers)
+            gemm_flops_total = 2.0 * rows_total * 512 * 2176 * 24
+            ach = gemm_flops_total / (gemm_ms * 1e-3) / 1e12 if gemm_launches else None
+            full_rows = min(args.windows_per_launch, n_win_rank) * S
+            traffic, mfma_util, clock_held, traffic_note = recorded_pmc(full_rows)
+            n1_ref = None
+            if wl == "cfg5" and world > 1:            # the same workload on ONE GPU, measured this round (the N = 1 default line is configs[3])
+                f = os.path.join(ROOT, "profiles", "r03_bench_cfg5_n1.json")
+                if os.path.exists(f):
+                    j = json.loads(open(f).read().strip().splitlines()[-1])
+                    n1_ref = {"value": j["value"], "ms_per_step": j["ms_per_step"], "source": "profiles/r03_bench_cfg5_n1.json (`bench.py --workload cfg5`, 1 x MI355X, this round)"}
+            line.update({
+                "roofline": {"bound": "mfma", "achieved": ach, "peak": PEAK_H3_TFLOPS, "unit": "TFLOP/s",
+                             "frac": (ach / PEAK_H3_TFLOPS) if ach else None, "traffic": traffic, "kernel": KERNEL, "fusion_note": FUSION_NOTE,
+                             "peak_note": "algorithmic fp32-accurate FLOP/s ceiling of the kernel = dense f16 MFMA peak 2500 / 3 passes",
+                             "mfma_pipe_executed_tflops": (ach * H3_PASSES) if ach else None,
+                             "launches_timed": gemm_launches, "ms_per_launch": gemm_ms / max(gemm_launches, 1),
+                             "algorithmic_flops_per_launch": 2.0 * full_rows * 512 * 2176,
+                             "token_rows_per_full_launch": full_rows,
+                             "pmc_recorded_mfma_pipe_utilisation": mfma_util,
+                             "pmc_recorded_clock_GHz": clock_held,     # the chip is power-limited under this load: the peak above assumes 2.4 GHz
+                             "frac_of_peak_at_recorded_clock": (ach / (PEAK_H3_TFLOPS * clock_held / 2.4)) if (ach and clock_held) else None,      # SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x busy cycles), recorded pass
+                             "traffic_source": "pmc_recorded (not measured by this run)" if traffic is not None else None,
+                             "traffic_note": traffic_note,
+                             "whole_path_tflops_per_gpu": sum(fl.values()) * args.steps / dt / 1e12,
+                             "whole_path_frac": sum(fl.values()) * args.steps / dt / 1e12 / PEAK_H3_TFLOPS},
+                "pcie_inclusive": pcie,
+                "same_workload_n1": n1_ref,
+                "stage_ms_per_step_rank0": stage_ms,
+                "stage_tflops_rank0": {k: (fl[a] / (stage_ms[k] * 1e-3) / 1e12 if stage_ms[k] > 0 else None)
+                                       for k, a in (("separation+loudness", "separation"), ("embedding+cosine", "embedding"), ("asr_encoder+decoder", "asr_encoder"))},
+                "algorithmic_flops_per_step_rank0": fl,
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                if sample_window is None:
+                    sample_window = batches[0][0][:WINDOW].cpu().numpy()
+                line["cpu_baseline"] = cpu_baseline_pipe(sep_sd, spk_sd, asr_sd, sample_window, with_asr)
+                line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.barrier()
@@ -457,6 +508,8 @@ def cfg1_bench(args):
         out = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, hotpath_outputs(out))
     t1 = time.perf_counter()
     for _ in range(args.steps):
         hp.separate([mix])
@@ -511,6 +564,8 @@ def cfg2_bench(args):
     dt = time.perf_counter() - t0
     gemm_ms, gemm_launches = sep.profile_collect()
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"separated": seeded_sample(out.cpu().numpy(), DUMP_MAX_SAMPLES)})
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -621,6 +676,8 @@ def dry_run(args):
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     ref = torch.stack([emb_of(i, s) for i in range(per_step) for s in (0, 1)])
     ok = bool(torch.equal(full, ref))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"embeddings": full})
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": per_step * 30.0 * args.steps / float(dt.item()), "unit": "audio-s/s", "n_gpus": world,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": float(dt.item()) / args.steps * 1e3,
@@ -664,9 +721,16 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-punc", action="store_true", help="configs[3] without the CT-Transformer punctuation stage (the round-1/2 form of the workload: pass-through)")
     ap.add_argument("--dry-run", action="store_true", help="rank plumbing on the CPU (gloo), no kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="cfg3 / cfg4 / cfg5: after the headline also the roofline of the dominant kernel (HIP events in the timed steps), "
+                         "the PCIe-inclusive and per-stage extra steps and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB; seeded inputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(spawn_ranks(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -681,6 +745,8 @@ def main():
     if args.workload == "cfg2":
         return cfg2_bench(args)
     if args.workload == "hbm":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the hbm workload hands nothing back")
         return hbm_workload(args)
     return pipe_bench(args)
 

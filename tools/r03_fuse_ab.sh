@@ -9,5 +9,5 @@ for f in 0 1 0 1; do
   TDX_FUSE_CONV=$f timeout -k 10 300 python bench.py --workload cfg2 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('cfg2 fuse=$f', round(d['ms_per_step'],2), 'ms', round(d['roofline']['ms_per_launch'],3), 'ms/launch')" || exit 1
 done
 for f in 0 1; do
-  TDX_FUSE_CONV=$f timeout -k 10 400 python bench.py --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('default fuse=$f', round(d['value'],1), 'RTF', round(d['ms_per_step'],1), 'ms', d['stage_ms_per_step_rank0'])" || exit 1
+  TDX_FUSE_CONV=$f timeout -k 10 400 python bench.py --steps 4 --warmup 2 --full --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('default fuse=$f', round(d['value'],1), 'RTF', round(d['ms_per_step'],1), 'ms', d['stage_ms_per_step_rank0'])" || exit 1
 done
