@@ -282,6 +282,30 @@ int tdx_loudness(const float* wav_dev, int B, long N, int rate, double* lufs_dev
 int tdx_resample_poly(const float* x_dev, long n_in, int C, int up, int down, const float* h_dev, int half,
                       float* y_dev, long n_out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * N3   Apollo band-split RoFormer restorer — replaces `self.restorer(audio_data_tensor)` in
+ *      AudioProcessor.restore_audio  AudioProcessor.py:959-980 (look2hear/models/apollo.py with
+ *      sr=44100, win=20, feature_dim=256, layer=num_layers; num_layers >= 1, the reference ships 6).
+ *      blob: TDXW container with the reference's state-dict names (BN.*, net.{l}.*, output.*, the rotary
+ *      buffers cos_freq / sin_freq included); names AND shapes are checked both ways (strict load),
+ *      any mismatch is TDX_E_BLOB before device work.
+ *      x_dev: nclips clips at 44.1 kHz, concatenated (clip c at sample offset lens[0] + ... + lens[c-1]);
+ *      y_dev: same layout.  lens_host: nclips lengths, each >= 442 (the reflect pad of the STFT needs it).
+ *      items_host: NULL (one item per clip: the whole clip, nitems = nclips) or nitems x 5 int32
+ *      {clip, frame_lo, frame_hi, sample_lo, sample_hi}: the item runs the net on frames [frame_lo, frame_hi)
+ *      of the clip (T = 1 + n / 441 frames, frame t centred on sample 441 t) and writes y over samples
+ *      [sample_lo, sample_hi) only.  The net is local in time (receptive field +-54 frames): a frame within 54
+ *      of a window edge that is not a clip edge is inexact, and an item whose samples read such a frame is
+ *      TDX_E_INVALID.  1 <= nitems <= 64; frames of the call = sum over items of (frame_hi - frame_lo).
+ * ---------------------------------------------------------------------------------- */
+typedef struct tdx_apollo tdx_apollo;
+int tdx_apollo_create(int num_layers, const void* weights_blob, size_t blob_bytes, int device, tdx_apollo** out);
+int tdx_apollo_destroy(tdx_apollo* h);
+size_t tdx_apollo_workspace_bytes(const tdx_apollo* h, int frames);
+double tdx_apollo_flops(const tdx_apollo* h, int frames);
+int tdx_apollo_forward(tdx_apollo* h, const float* x_dev, const int64_t* lens_host, int nclips, const int32_t* items_host, int nitems,
+                       float* y_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

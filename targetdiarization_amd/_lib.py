@@ -85,6 +85,11 @@ SIGNATURES = {
     "tdx_loudness_workspace_bytes": (_sz, [_i, C.c_long, _i]),
     "tdx_loudness": (_i, [_fp, _i, C.c_long, _i, _vp, _vp, _sz, _vp]),
     "tdx_resample_poly": (_i, [_fp, C.c_long, _i, _i, _i, _fp, _i, _fp, C.c_long, _vp]),
+    "tdx_apollo_create": (_i, [_i, _vp, _sz, _i, C.POINTER(_vp)]),
+    "tdx_apollo_destroy": (_i, [_vp]),
+    "tdx_apollo_workspace_bytes": (_sz, [_vp, _i]),
+    "tdx_apollo_flops": (C.c_double, [_vp, _i]),
+    "tdx_apollo_forward": (_i, [_vp, _fp, _vp, _i, _vp, _i, _fp, _vp, _sz, _vp]),
 }
 
 

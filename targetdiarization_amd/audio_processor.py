@@ -12,8 +12,11 @@ implementation of its architecture (`mdx_state_dict` -> `mdx.ConvTDFNetBody`, cs
 `mdx_model(spec[n,4,dim_f,dim_t]) -> spec` on device tensors.  Resampling runs on the device polyphase resampler
 (`ops.resample_poly`; the reference calls librosa: parity unpinned).
 
-Out of scope here: enhancer, Apollo restorer, noisereduce (fast_mode), file I/O — those flags are
-accepted and degrade to "module skipped" exactly like the reference does when a package is disabled.
+`restore_audio` (:959-980) runs the Apollo restorer on the device (`apollo.ApolloRestorer`, csrc/apollo.hip) from
+`<restorer_weights_folder>/pytorch_model.bin` like `init_restorer_model` (:277-281), or from an in-memory `restorer_state_dict`.
+
+Out of scope here: enhancer, noisereduce (fast_mode), file I/O — those flags are accepted and degrade to
+"module skipped" exactly like the reference does when a package is disabled.
 """
 from __future__ import annotations
 
@@ -35,12 +38,14 @@ class AudioProcessor:
                  is_restore_audio: bool = False, restorer_weights_folder: str = "JusperLee/Apollo",
                  verbose_log: bool = True, cuda_device: int = 0, quality: int = 2,
                  separater_state_dict=None, mdx_model=None, mdx_dim_f: int = 3072, mdx_n_fft: int = 6144, silero_vad=None,
-                 mdx_state_dict=None, mdx_args=None):
+                 mdx_state_dict=None, mdx_args=None, restorer_state_dict=None):
         """`separater_state_dict` (extension): an in-memory state_dict instead of
         `<separater_weights_folder>/best_model.pth` — no checkpoint ships with the reference.
         `mdx_model` (extension): the MDX net body as a callable on device tensors, spec[n,4,dim_f,256] -> spec (the
         reference runs the ONNX file through onnxruntime, AudioProcessor.py:231-233,630); without it the denoiser is off,
-        like a failed `init_mdx_model` (:171-176).  `mdx_dim_f` / `mdx_n_fft`: the ONNX metadata the reference reads (:234-237)."""
+        like a failed `init_mdx_model` (:171-176).  `mdx_dim_f` / `mdx_n_fft`: the ONNX metadata the reference reads (:234-237).
+        `restorer_state_dict` (extension): the Apollo weights in memory instead of `<restorer_weights_folder>/pytorch_model.bin`
+        (the reference's 6 layers, or as many as the dict holds)."""
         if is_denoise_vocal and mdx_model is None and mdx_state_dict is not None:
             # the ConvTDFNet body on the device (mdx.ConvTDFNetBody, csrc/mdx.hip) from a state dict with the PyTorch module names;
             # `mdx_args`: its geometry (L, l, g, k, bn, dim_f, dim_t, max_blocks_per_launch).  A failure prints and leaves the denoiser
@@ -58,7 +63,6 @@ class AudioProcessor:
         if is_denoise_vocal and mdx_model is None:
             print("Failed to init MDX model: the MDX net body is a third-party ONNX model; pass mdx_model=callable(spec)->spec")
         self.is_enhance_vocal = False
-        self.is_restore_audio = False
         self.is_separate_audio = is_separate_audio
         self.mdx_weights_file = mdx_weights_file.replace("\\", "/")
         self.enhancer_weights_folder = enhancer_weights_folder.replace("\\", "/")
@@ -77,6 +81,16 @@ class AudioProcessor:
                 self.is_separate_audio = False
         else:
             self.is_separate_audio = False
+        self.restorer = None
+        self.is_restore_audio = is_restore_audio
+        if self.is_restore_audio and (restorer_state_dict is not None or os.path.isdir(self.restorer_weights_folder)):
+            try:
+                self.init_restorer_model(restorer_state_dict)
+            except Exception as e:                       # AudioProcessor.py:195-200
+                print(f"Failed to init restorer model: {e}")
+                self.is_restore_audio = False
+        else:
+            self.is_restore_audio = False
 
     # AudioProcessor.py:205-221 — None -> auto, -1 -> cpu, n -> cuda:n
     def get_device(self):
@@ -110,6 +124,67 @@ class AudioProcessor:
                 model_args.pop("_target_", None)
             self.separater = MossFormer2Separator.from_pretrain(f"{self.separater_weights_folder}/best_model.pth", device=dev, **model_args)
         self.separater.eval()
+
+    # AudioProcessor.py:277-281 (sr=44100, win=20, feature_dim=256, layer=6; BaseModel.from_pretrain loads strictly)
+    def init_restorer_model(self, state_dict=None):
+        from .apollo import ApolloRestorer, load_state_dict
+        if str(self.device) == "cpu":
+            raise _lib.TdxError("the MI355X build has no CPU restorer (cuda_device=-1 is not supported)")
+        num_layers = 6
+        if state_dict is None:
+            state_dict = load_state_dict(self.restorer_weights_folder)
+        else:                                            # in-memory weights: as many BSNet layers as they hold
+            num_layers = sum(1 for k in state_dict if k.endswith("band_net.cos_freq"))
+        self.restorer = ApolloRestorer(state_dict, device=self._dev(), num_layers=num_layers).eval()
+
+    # AudioProcessor.py:959-980
+    def restore_audio(self, audio_data, sampling_rate: int, keep_sampling_rate: bool = False, output_audio_only: bool = False):
+        """Resample to 44.1 kHz, restore, and optionally resample back.  Mono [n] -> [n]; [n, C] is restored as C independent clips
+        and returned as [C, n] (the reference's squeezed model output).  numpy in -> numpy out, device tensor in -> device tensor
+        out.  Returns (audio, rate) — rate 44100 unless keep_sampling_rate — or the audio alone with output_audio_only.
+        Unlike the reference, keep_sampling_rate resamples a [C, n] result along time: the reference hands the [C, n] array to a
+        resampler that expects [n, C], i.e. it resamples across channels."""
+        if not self.is_restore_audio:
+            print("\nSkip module: restore_audio")
+            return audio_data
+        if self.verbose_log:
+            print("\nRunning module: restore_audio")
+        orig_sr = sampling_rate
+        is_np = isinstance(audio_data, np.ndarray)
+        x = torch.from_numpy(np.ascontiguousarray(audio_data, dtype=np.float32)) if is_np else audio_data
+        x = x.to(self._dev(), torch.float32)
+        x, sampling_rate = self.audio_resample(x, orig_sr, 44100)
+        outs = self.restorer([x] if x.ndim == 1 else list(x.t()))
+        out = outs[0] if x.ndim == 1 or x.shape[1] == 1 else torch.stack(outs)
+        if keep_sampling_rate:
+            out, sampling_rate = self.audio_resample(out if out.ndim == 1 else out.t(), 44100, orig_sr)
+            out = out if out.ndim == 1 else out.t().contiguous()
+        if is_np:
+            out = out.cpu().numpy().astype(np.float32)
+        if output_audio_only:
+            return out
+        return out, sampling_rate
+
+    def restore_streams_device(self, streams, sampling_rate: int = 16000):
+        """restore_audio(keep_sampling_rate=True, output_audio_only=True) for a list of 1-D device streams: resampled to 44.1 kHz
+        (equal lengths share a launch), ONE restorer call for all of them, resampled back"""
+        if not streams:
+            return []
+        return self._resample_many(self.restorer(self._resample_many(streams, sampling_rate, 44100)), 44100, sampling_rate)
+
+    @staticmethod
+    def _resample_many(xs, orig_sr: int, target_sr: int):
+        from . import ops
+        if orig_sr == target_sr:
+            return list(xs)
+        out, by_len = [None] * len(xs), {}
+        for i, x in enumerate(xs):
+            by_len.setdefault(int(x.shape[0]), []).append(i)
+        for idxs in by_len.values():
+            y = ops.resample_poly(torch.stack([xs[i] for i in idxs]), orig_sr, target_sr)
+            for j, i in enumerate(idxs):
+                out[i] = y[j]
+        return out
 
     # AudioProcessor.py:1123-1127
     def meter_loudness(self, audio_data: np.ndarray, sampling_rate: int):

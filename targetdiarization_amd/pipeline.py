@@ -62,12 +62,14 @@ class HotPath:
     def __init__(self, sep_state_dict, spk_state_dict=None, asr_state_dict=None, cuda_device: int = 0,
                  asr_segment: int = 480000, cmvn_shift=None, cmvn_scale=None, windows_per_launch: int = 32,
                  asr_rows_per_launch: int = 32768, mdx_model=None, mdx_weights_file: str = "mdx/weights/UVR-MDX-NET-Inst_HQ_3.onnx",
-                 mdx_state_dict=None, mdx_args=None):
+                 mdx_state_dict=None, mdx_args=None, restorer_state_dict=None, restorer_weights_folder: str | None = None):
         from .audio_processor import AudioProcessor
         self.device = torch.device(f"cuda:{cuda_device}")
         self.ap = AudioProcessor(is_separate_audio=True, separater_state_dict=sep_state_dict, cuda_device=cuda_device, verbose_log=False,
                                  is_denoise_vocal=mdx_model is not None or mdx_state_dict is not None, mdx_model=mdx_model,
-                                 mdx_weights_file=mdx_weights_file, quality=3, mdx_state_dict=mdx_state_dict, mdx_args=mdx_args)
+                                 mdx_weights_file=mdx_weights_file, quality=3, mdx_state_dict=mdx_state_dict, mdx_args=mdx_args,
+                                 is_restore_audio=restorer_state_dict is not None or bool(restorer_weights_folder),
+                                 restorer_weights_folder=restorer_weights_folder or "", restorer_state_dict=restorer_state_dict)
         if not self.ap.is_separate_audio:
             from ._lib import TdxError
             raise TdxError("separator failed to initialise")
@@ -125,6 +127,18 @@ class HotPath:
             h = p.cpu().numpy()
             res.append((h[0], h[1]))
         return res
+
+    def restore_device(self, streams, sampling_rate: int = 16000):
+        """the Apollo restorer of hot loop B (TargetASR.py:627-628: restore_audio(keep_sampling_rate=True, output_audio_only=True))
+        on a list of 1-D streams in one batched call: list of 1-D DEVICE tensors; the streams unchanged without a restorer"""
+        streams = [self._dev(s) for s in streams]
+        if not self.ap.is_restore_audio:
+            return streams
+        return self.ap.restore_streams_device(streams, sampling_rate)
+
+    def restore(self, streams, sampling_rate: int = 16000):
+        """host form: list of numpy arrays"""
+        return [t.cpu().numpy() for t in self.restore_device(streams, sampling_rate)]
 
     # ---- H2 -------------------------------------------------------------------------------
     def embed_streams(self, streams):

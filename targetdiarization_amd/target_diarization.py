@@ -13,8 +13,9 @@ order of its steps, with two differences that are the point of the rewrite:
       decoder(encoder_out[T',512]) -> (text, [(token, [s, e]), ...][, language])   (CIF + NAR decoder)
       punctuation(text)  -> text                                          (CT-Transformer, ASRProcessor.py:880-897)
     Defaults: one segment per utterance / no overlap detector / whole clip is speech / the device decoder / text unchanged.
-The MDX denoiser body runs on the device when `mdx_state_dict` is given (mdx.ConvTDFNetBody, or any `mdx_model` callable); Apollo
-restoration and non-.wav file decoding are outside the path.
+The MDX denoiser body runs on the device when `mdx_state_dict` is given (mdx.ConvTDFNetBody, or any `mdx_model` callable); the
+Apollo restorer of hot loop B when `restorer_state_dict` is given or `restorer_weights_folder` names a directory holding
+pytorch_model.bin (apollo.ApolloRestorer).  Non-.wav file decoding is outside the path.
 """
 from __future__ import annotations
 
@@ -46,7 +47,7 @@ class TargetDiarization:
                  sd_pipeline: Optional[Callable] = None, od_pipeline: Optional[Callable] = None,
                  vad: Optional[Callable] = None, decoder: Optional[Callable] = None, mdx_model: Optional[Callable] = None, token_list=None,
                  punctuation: Optional[Callable] = None, mdx_state_dict=None, mdx_args=None,
-                 punc_state_dict=None, punc_vocab=None, **kwargs):
+                 punc_state_dict=None, punc_vocab=None, restorer_state_dict=None, **kwargs):
         self.target_similarity_threshold = target_similarity_threshold
         self.asr_engine = asr_engine
         self.cuda_device = cuda_device
@@ -61,7 +62,8 @@ class TargetDiarization:
             from .punctuation import CTTransformer
             self.punctuation = CTTransformer(punc_state_dict, device=f"cuda:{cuda_device}", vocab=punc_vocab)
         self.hp = HotPath(sep_state_dict, spk_state_dict, asr_state_dict, cuda_device=cuda_device, mdx_model=mdx_model,
-                          mdx_weights_file=mdx_weights_file, mdx_state_dict=mdx_state_dict, mdx_args=mdx_args)
+                          mdx_weights_file=mdx_weights_file, mdx_state_dict=mdx_state_dict, mdx_args=mdx_args,
+                          restorer_state_dict=restorer_state_dict, restorer_weights_folder=restorer_weights_folder)
         # One model serves every request of the reference's server (main.py:42): REST handlers and WebSocket worker threads call
         # into it concurrently.  Each model object of the hot path serialises its own calls (_lib.HandleGuard); this lock keeps a
         # whole infer() — and, in stream mode, the processing of one released buffer — together, so that concurrent requests
@@ -206,10 +208,16 @@ class TargetDiarization:
         seps = self.hp.separate([clips[i] for i in ok])
         embs = self.hp.spk.get_speaker_embeddings([s for pair in seps for s in pair])
         scores = self.hp.spk.cosine_scores(embs, target_embedding)
+        picks = []
         for j, i in enumerate(ok):
             s1, s2 = float(scores[2 * j]), float(scores[2 * j + 1])
             a, b = seps[j]
-            tgt, noise = (a, b) if s1 > s2 else (b, a)
+            picks.append((i, (a, b) if s1 > s2 else (b, a)))
+        if getattr(self.hp.ap, "is_restore_audio", False):          # (a stand-in hot path without the attribute has no restorer)
+            # TargetASR.py:626-628: restore the target and noise streams, here of ALL segments in one batched call
+            flat = self.hp.restore([s for _, pair in picks for s in pair])
+            picks = [(i, (flat[2 * k], flat[2 * k + 1])) for k, (i, _) in enumerate(picks)]
+        for i, (tgt, noise) in picks:
             for stream in (tgt, noise):
                 v = self.vad(stream)
                 if v:

@@ -451,3 +451,74 @@ def recipe_punc_state_dict(seed: int = 0, num_blocks: int = 4, vocab: int = 4096
             t = u * float(1.0 / np.sqrt(int(np.prod(shape[1:]))))
         out[name] = t.to(torch.float32).contiguous()
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# Apollo band-split RoFormer restorer (look2hear/models/apollo.py, built by AudioProcessor.init_restorer_model with
+# sr=44100, win=20, feature_dim=256, layer=6): 80 bands (79 x 5 bins + 47), 6 BSNet layers.  Key list verified against the
+# imported reference by tools/make_goldens_apollo.py (tests/golden/apollo_catalogue.json).
+# ---------------------------------------------------------------------------------------
+APOLLO_BANDS = [5] * 79 + [47]
+
+
+def apollo_param_shapes(num_layers: int = 6, d: int = 256) -> "OrderedDict[str, tuple]":
+    """Ordered {state_dict key: shape}, module order of the reference (rotary tables are registered buffers: they are in the
+    state dict and a strict load checks them)."""
+    s = OrderedDict()
+    for i, bw in enumerate(APOLLO_BANDS):
+        s[f"BN.{i}.0.weight"] = (2 * bw + 1,)
+        s[f"BN.{i}.1.weight"] = (d, 2 * bw + 1, 1)
+        s[f"BN.{i}.1.bias"] = (d,)
+    for l in range(num_layers):
+        p = f"net.{l}.band_net."
+        s[p + "cos_freq"] = (100, 32)
+        s[p + "sin_freq"] = (100, 32)
+        s[p + "input_norm.weight"] = (d,)
+        s[p + "weight.weight"] = (3 * d, d, 1)
+        s[p + "output.weight"] = (d, d, 1)
+        s[p + "MLP.0.weight"] = (d,)
+        s[p + "MLP.1.weight"] = (8 * d, d, 1)
+        s[p + "MLP_output.weight"] = (d, 4 * d, 1)
+        for b in range(3):
+            q = f"net.{l}.seq_net.blocks.{b}.conv."
+            s[q + "0.weight"] = (d, 1, 7)
+            s[q + "0.bias"] = (d,)
+            s[q + "1.weight"] = (d,)
+            s[q + "2.weight"] = (4 * d, d, 1)
+            s[q + "2.bias"] = (4 * d,)
+            s[q + "4.weight"] = (d, 4 * d, 1)
+            s[q + "4.bias"] = (d,)
+    for i, bw in enumerate(APOLLO_BANDS):
+        s[f"output.{i}.0.weight"] = (d,)
+        s[f"output.{i}.1.weight"] = (4 * bw, d, 1)
+        s[f"output.{i}.1.bias"] = (4 * bw,)
+    return s
+
+
+def apollo_rotary_tables(window: int = 100, dim: int = 32, theta: float = 10000.0):
+    """cos / sin tables [window, dim] in float32, computed the way Roformer._calc_rotary_emb does (pair-duplicated angles)."""
+    freq = 1.0 / (theta ** (torch.arange(0, dim, 2)[: dim // 2] / dim))
+    ang = torch.arange(0, window).reshape(-1, 1) * freq.reshape(1, -1)
+    cos = torch.stack([torch.cos(ang)] * 2, -1).reshape(window, dim)
+    sin = torch.stack([torch.sin(ang)] * 2, -1).reshape(window, dim)
+    return cos.to(torch.float32), sin.to(torch.float32)
+
+
+def recipe_apollo_state_dict(seed: int = 0, num_layers: int = 6) -> "OrderedDict[str, torch.Tensor]":
+    """Deterministic fp32 weights for the Apollo layout: conv weights and biases U(+-1/sqrt(fan_in)) (PyTorch's Conv1d init range),
+    RMSNorm weights 1 + 0.1 u, the rotary buffers as the reference computes them."""
+    cos, sin = apollo_rotary_tables()
+    shapes = apollo_param_shapes(num_layers)
+    out = OrderedDict()
+    for name, shape in shapes.items():
+        if name.endswith("cos_freq") or name.endswith("sin_freq"):
+            out[name] = (cos if name.endswith("cos_freq") else sin).clone()
+            continue
+        u = torch.from_numpy(philox_uniform("apollo:" + name, int(np.prod(shape)), seed)).reshape(shape)
+        if len(shape) == 1 and name.endswith(".weight"):         # every 1-D weight is an RMSNorm gain (conv weights are 3-D)
+            t = 1.0 + 0.1 * u
+        else:
+            wshape = shapes[name[:-len("bias")] + "weight"] if name.endswith(".bias") else shape
+            t = u * float(1.0 / np.sqrt(int(np.prod(wshape[1:]))))
+        out[name] = t.to(torch.float32).contiguous()
+    return out
