@@ -306,6 +306,25 @@ double tdx_apollo_flops(const tdx_apollo* h, int frames);
 int tdx_apollo_forward(tdx_apollo* h, const float* x_dev, const int64_t* lens_host, int nclips, const int32_t* items_host, int nitems,
                        float* y_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * N4   CAM++ speaker-embedding extractor (3D-Speaker speakerlab/models/campplus: FCM head + D-TDNN with
+ *      context-aware masking, 192-d) — the embedding model of modelscope's
+ *      speech_campplus_speaker-diarization_common pipeline (TargetDiarization.py:73) and
+ *      `self.embedding['campp']` (TargetASR.py:109).
+ *      blob: TDXW container with 3D-Speaker's state-dict names (head.*, xvector.*; num_batches_tracked
+ *      dropped); strict both ways: a missing and an unexpected tensor are TDX_E_BLOB with the name in
+ *      tdx_last_error().  BatchNorm is eval-mode (eps 1e-5) and folded where a convolution precedes it.
+ *      feat_dev [B,F,80] = tdx_fbank mode-0 output (mean-normalised fbank) -> emb_dev [B,192].
+ *      All B utterances share F; F >= 9 (workspace_bytes returns 0 below that).
+ * ---------------------------------------------------------------------------------- */
+typedef struct tdx_campp tdx_campp;
+int tdx_campp_create(const void* weights_blob, size_t blob_bytes, int device, tdx_campp** out);
+int tdx_campp_destroy(tdx_campp* h);
+size_t tdx_campp_workspace_bytes(const tdx_campp* h, int B, int F);
+double tdx_campp_flops(const tdx_campp* h, int B, int F);
+int tdx_campp_forward(tdx_campp* h, const float* feat_dev, int B, int F, float* emb_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

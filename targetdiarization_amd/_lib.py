@@ -90,6 +90,11 @@ SIGNATURES = {
     "tdx_apollo_workspace_bytes": (_sz, [_vp, _i]),
     "tdx_apollo_flops": (C.c_double, [_vp, _i]),
     "tdx_apollo_forward": (_i, [_vp, _fp, _vp, _i, _vp, _i, _fp, _vp, _sz, _vp]),
+    "tdx_campp_create": (_i, [_vp, _sz, _i, C.POINTER(_vp)]),
+    "tdx_campp_destroy": (_i, [_vp]),
+    "tdx_campp_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "tdx_campp_flops": (C.c_double, [_vp, _i, _i]),
+    "tdx_campp_forward": (_i, [_vp, _fp, _i, _i, _fp, _vp, _sz, _vp]),
 }
 
 

@@ -156,3 +156,90 @@ def hdbscan_labels(X, min_cluster_size: int = 2, min_samples: int | None = None)
             if q in label_of:
                 labels[c] = label_of[q]
     return labels
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Spectral clustering of the CAM++ diarizer's window embeddings (modelscope speech_campplus_speaker-diarization_common:
+# cluster_backend.SpectralCluster + merge-by-cosine) [upstream-recall; DESIGN §8.10 is the governing description].
+# modelscope switches to UMAP + HDBSCAN from 2 048 embeddings on; UMAP is third-party and absent, so the spectral path
+# serves every n.  k-means is an own deterministic one (k-means++ seeding from a fixed seed, Lloyd iterations).
+# ---------------------------------------------------------------------------------------------------------------
+def kmeans_labels(X: np.ndarray, k: int, seed: int = 0, n_init: int = 10, iters: int = 100) -> np.ndarray:
+    """deterministic k-means: best inertia of n_init k-means++ starts drawn from default_rng(seed)"""
+    X = np.asarray(X, dtype=np.float64)
+    n = X.shape[0]
+    k = max(1, min(k, n))
+    rng = np.random.default_rng(seed)
+    best, best_inertia = np.zeros(n, dtype=np.int64), np.inf
+    for _ in range(n_init):
+        centres = [X[rng.integers(n)]]
+        for _c in range(1, k):
+            d2 = np.min(((X[:, None, :] - np.asarray(centres)[None]) ** 2).sum(-1), axis=1)
+            tot = d2.sum()
+            centres.append(X[rng.choice(n, p=d2 / tot)] if tot > 0 else X[rng.integers(n)])
+        C = np.asarray(centres)
+        lab = None
+        for _it in range(iters):
+            d2 = ((X[:, None, :] - C[None]) ** 2).sum(-1)
+            new = d2.argmin(axis=1)
+            if lab is not None and np.array_equal(new, lab):
+                break
+            lab = new
+            for j in range(k):
+                if np.any(lab == j):
+                    C[j] = X[lab == j].mean(axis=0)
+        inertia = ((X - C[lab]) ** 2).sum()
+        if inertia < best_inertia - 1e-12:
+            best, best_inertia = lab.copy(), inertia
+    return best
+
+
+def _unit(X):
+    return X / np.maximum(np.linalg.norm(X, axis=1, keepdims=True), 1e-12)
+
+
+def merge_by_cosine(labels: np.ndarray, X: np.ndarray, threshold: float = 0.78) -> np.ndarray:
+    """merge the pair of clusters whose centres (mean embeddings) have the highest cosine while it exceeds threshold"""
+    labels = np.asarray(labels).copy()
+    while True:
+        ids = np.unique(labels)
+        if len(ids) <= 1:
+            return labels
+        C = _unit(np.stack([X[labels == i].mean(axis=0) for i in ids]))
+        S = C @ C.T
+        np.fill_diagonal(S, -np.inf)
+        a, b = np.unravel_index(np.argmax(S), S.shape)
+        if S[a, b] <= threshold:
+            return labels
+        labels[labels == ids[max(a, b)]] = ids[min(a, b)]
+
+
+def spectral_labels(X: np.ndarray, oracle_num: int | None = None, min_num: int = 20, pval: float = 0.022, min_pnum: int = 6,
+                    max_spks: int = 15, merge_threshold: float = 0.78, seed: int = 0) -> np.ndarray:
+    """X [n,d] embeddings -> labels [n] (0-based, in no particular order).  n < min_num: all zeros."""
+    from scipy.linalg import eigh
+    X = np.asarray(X, dtype=np.float64)
+    n = X.shape[0]
+    if n < min_num:
+        return np.zeros(n, dtype=np.int64)
+    U = _unit(X)
+    A = U @ U.T
+    drop = max(0, min(int((1.0 - pval) * n), n - min_pnum))          # per row: zero the `drop` smallest affinities
+    if drop:
+        idx = np.argsort(A, axis=1, kind="stable")[:, :drop]
+        np.put_along_axis(A, idx, 0.0, axis=1)
+    A = 0.5 * (A + A.T)
+    np.fill_diagonal(A, 0.0)
+    L = np.diag(A.sum(axis=1)) - A
+    m = min(max_spks + 1, n)
+    w, V = eigh(L, subset_by_index=[0, m - 1])
+    if oracle_num is not None:
+        k = int(oracle_num)
+    else:
+        gaps = np.diff(w)[:max_spks]
+        k = int(np.argmax(gaps)) + 1
+    k = max(1, min(k, max_spks, n))
+    labels = kmeans_labels(V[:, :k], k, seed=seed)
+    if oracle_num is None:
+        labels = merge_by_cosine(labels, X, merge_threshold)
+    return labels

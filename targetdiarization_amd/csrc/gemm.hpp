@@ -73,6 +73,7 @@ struct GemmArgs {
     int pair_off;     // PAIRED: column offset of the second member of a pair
     int shift_k;      // SHIFT: k < shift_k is read from row m-1 (zero when m % shift_S == 0)
     int shift_S;
+    int cv_stride_w;  // CONV: stride along w when it differs from cv_stride (0: cv_stride on both axes)
 };
 
 // XCD-aware bijective remap of the linear block id (cdna_hip_programming.md §5 T1):
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f32_kernel(GemmArgs g, E
             const int hw = g.cv_Hout * g.cv_Wout;                        \
             const int b_ = m / hw, r_ = m - b_ * hw;                     \
             const int h_ = r_ / g.cv_Wout, w_ = r_ - h_ * g.cv_Wout;     \
-            cvb = b_ * g.cv_Hin * g.cv_Win; cvh = h_ * g.cv_stride; cvw = w_ * g.cv_stride; \
+            cvb = b_ * g.cv_Hin * g.cv_Win; cvh = h_ * g.cv_stride; cvw = w_ * (g.cv_stride_w ? g.cv_stride_w : g.cv_stride); \
         }
         TDX_CV_DECODE(i0, cvb0, cvh0, cvw0) TDX_CV_DECODE(i1, cvb1, cvh1, cvw1)
         TDX_CV_DECODE(i2, cvb2, cvh2, cvw2) TDX_CV_DECODE(i3, cvb3, cvh3, cvw3)

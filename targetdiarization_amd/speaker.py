@@ -1,4 +1,4 @@
-"""ERes2NetV2 speaker-embedding extractor over the C-ABI (tdx_eres2net_*) and the
+"""ERes2NetV2 and CAM++ speaker-embedding extractors over the C-ABI (tdx_eres2net_*, tdx_campp_*) and the
 TargetASR-compatible host methods (TargetASR.py:144-163)."""
 from __future__ import annotations
 
@@ -9,7 +9,7 @@ import torch
 
 from . import _lib, ops
 from .frontend import Fbank
-from .weights import pack_blob
+from .weights import drop_num_batches_tracked, pack_blob
 
 
 class ERes2NetV2:
@@ -69,13 +69,69 @@ class ERes2NetV2:
             pass
 
 
+class CAMPPlus:
+    """CAM++ (csrc/campplus.hip): the same front end and surface as ERes2NetV2; state_dict with 3D-Speaker's names."""
+
+    def __init__(self, state_dict, device="cuda:0"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.TdxError("CAMPPlus needs a HIP device")
+        self._l = _lib.lib()
+        blob = pack_blob(drop_num_batches_tracked(state_dict))
+        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
+        h = C.c_void_p()
+        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", idx)
+        with torch.cuda.device(idx):
+            _lib.check(self._l.tdx_campp_create(buf, len(blob), idx, C.byref(h)))
+        self._h = h
+        self._guard = _lib.HandleGuard(self.device)      # calls on this object are serialised (host lock + device event chain)
+        self.fbank = Fbank("sv", self.device)
+
+    def flops(self, B, F):
+        return float(self._l.tdx_campp_flops(self._h, B, F))
+
+    def embed_features(self, feat: torch.Tensor) -> torch.Tensor:
+        """feat [B,F,80] (mean-normalised fbank) -> [B,192]"""
+        feat = feat.to(self.device, torch.float32).contiguous()
+        B, F, _ = feat.shape
+        nb = int(self._l.tdx_campp_workspace_bytes(self._h, B, F))
+        if nb == 0:
+            raise _lib.TdxError("CAMPPlus: need at least 9 fbank frames (and B*F*80 < 2^31 per launch)")
+        with torch.cuda.device(self.device), self._guard.call():
+            ws = self._guard.workspace(nb)
+            out = torch.empty(B, 192, device=self.device)
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self._l.tdx_campp_forward(self._h, feat.data_ptr(), B, F, out.data_ptr(), ws.data_ptr(), ws.numel(), st))
+            return out
+
+    def __call__(self, wav: torch.Tensor) -> torch.Tensor:
+        """wav [B,N] in [-1,1] -> [B,192]; all B clips share N (bucket by length)."""
+        if wav.ndim == 1:
+            wav = wav[None]
+        return self.embed_features(self.fbank(wav))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._l.tdx_campp_destroy(self._h); self._h = None
+        except Exception:
+            pass
+
+
 class SpeakerEmbedder:
     """The two hot-path methods of the reference's TargetASR (TargetASR.py:144-163) plus the
     batched forms the MI355X pipeline uses (hot loops A/C of TargetDiarization.infer issue one
     embedding call per segment; here equal-length segments share a launch)."""
 
-    def __init__(self, state_dict, cuda_device: int = 0, max_batch_frames: int = 40000):
-        self.model = ERes2NetV2(state_dict, device=f"cuda:{cuda_device}")
+    def __init__(self, state_dict, cuda_device: int = 0, max_batch_frames: int = 40000, arch: str = "eres2netv2"):
+        if arch == "eres2netv2":
+            self.model = ERes2NetV2(state_dict, device=f"cuda:{cuda_device}")
+        elif arch == "campplus":
+            self.model = CAMPPlus(state_dict, device=f"cuda:{cuda_device}")
+        else:
+            raise _lib.TdxError(f"SpeakerEmbedder: unknown arch {arch!r} (eres2netv2 | campplus)")
+        self.arch = arch
         self.device = self.model.device
         self.max_batch_frames = max_batch_frames
 

@@ -92,8 +92,10 @@ class TargetASR:
                  vad_model_dir: str = "iic/speech_fsmn_vad_zh-cn-16k-common-pytorch", diarization_model_dir: Optional[str] = None,
                  asr_model_dir: Union[str, list, None] = None, mdx_weights_file: Optional[str] = None,
                  separater_weights_folder: Optional[str] = None, restorer_weights_folder: Optional[str] = None, verbose_log: bool = False,
-                 *, spk_state_dict=None, vad: Optional[Callable] = None, loudness_control: Optional[Callable] = None):
-        """vad(audio) -> [[start_s, end_s], ...]: FunASR FSMN-VAD (`self.asrp.vad_detection`, third-party) as a plug-in, default = whole clip;
+                 *, spk_state_dict=None, vad: Optional[Callable] = None, loudness_control: Optional[Callable] = None,
+                 campp_state_dict=None):
+        """campp_state_dict: CAM++ weights (3D-Speaker names) -> `self.embedding["campp"]` (TargetASR.py:109);
+        vad(audio) -> [[start_s, end_s], ...]: FunASR FSMN-VAD (`self.asrp.vad_detection`, third-party) as a plug-in, default = whole clip;
         loudness_control(audio) -> audio: AudioProcessor.audio_loudness_control (:417-429), default = the BS.1770 host meter"""
         self.cuda_device = cuda_device
         self.verbose_log = verbose_log
@@ -105,6 +107,12 @@ class TargetASR:
                 from .speaker import SpeakerEmbedder
                 self.embedding["eres2netv2_large"] = SpeakerEmbedder(spk_state_dict, cuda_device=cuda_device)
             except Exception as e:                       # reference: init failure -> print, feature off (TargetASR.py:98-109)
+                print(f"Load embedding model failed: {e}")
+        if campp_state_dict is not None:
+            try:
+                from .speaker import SpeakerEmbedder
+                self.embedding["campp"] = SpeakerEmbedder(campp_state_dict, cuda_device=cuda_device, arch="campplus")
+            except Exception as e:
                 print(f"Load embedding model failed: {e}")
 
     # TargetASR.py:144-152

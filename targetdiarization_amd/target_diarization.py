@@ -12,6 +12,8 @@ order of its steps, with two differences that are the point of the rewrite:
       vad(audio)         -> [[start, end], ...] in seconds               (FSMN-VAD, ASRProcessor.py:742)
       decoder(encoder_out[T',512]) -> (text, [(token, [s, e]), ...][, language])   (CIF + NAR decoder)
       punctuation(text)  -> text                                          (CT-Transformer, ASRProcessor.py:880-897)
+    `sd_state_dict` (CAM++ weights, 3D-Speaker names) or a `diarization_pipeline_dir` holding campplus_cn_common.bin puts the
+    device diarizer (diarization.CamppDiarizer, csrc/campplus.hip) behind sd_pipeline.
     Defaults: one segment per utterance / no overlap detector / whole clip is speech / the device decoder / text unchanged.
 The MDX denoiser body runs on the device when `mdx_state_dict` is given (mdx.ConvTDFNetBody, or any `mdx_model` callable); the
 Apollo restorer of hot loop B when `restorer_state_dict` is given or `restorer_weights_folder` names a directory holding
@@ -47,7 +49,7 @@ class TargetDiarization:
                  sd_pipeline: Optional[Callable] = None, od_pipeline: Optional[Callable] = None,
                  vad: Optional[Callable] = None, decoder: Optional[Callable] = None, mdx_model: Optional[Callable] = None, token_list=None,
                  punctuation: Optional[Callable] = None, mdx_state_dict=None, mdx_args=None,
-                 punc_state_dict=None, punc_vocab=None, restorer_state_dict=None, **kwargs):
+                 punc_state_dict=None, punc_vocab=None, restorer_state_dict=None, sd_state_dict=None, **kwargs):
         self.target_similarity_threshold = target_similarity_threshold
         self.asr_engine = asr_engine
         self.cuda_device = cuda_device
@@ -61,6 +63,16 @@ class TargetDiarization:
         if punctuation is None and punc_state_dict is not None:      # the device CT-Transformer (punctuation.py, tdx_punc_*)
             from .punctuation import CTTransformer
             self.punctuation = CTTransformer(punc_state_dict, device=f"cuda:{cuda_device}", vocab=punc_vocab)
+        if sd_pipeline is None:               # the CAM++ diarizer on the device (diarization.py, tdx_campp_*); neither source: one segment per utterance
+            if sd_state_dict is None and isinstance(diarization_pipeline_dir, str):
+                import os
+                ckpt = os.path.join(diarization_pipeline_dir, "campplus_cn_common.bin")
+                if os.path.isdir(diarization_pipeline_dir) and os.path.isfile(ckpt):
+                    import torch
+                    sd_state_dict = torch.load(ckpt, map_location="cpu", weights_only=True)
+            if sd_state_dict is not None:
+                from .diarization import CamppDiarizer
+                self.sd_pipeline = CamppDiarizer(sd_state_dict, cuda_device=cuda_device, vad=self.vad)
         self.hp = HotPath(sep_state_dict, spk_state_dict, asr_state_dict, cuda_device=cuda_device, mdx_model=mdx_model,
                           mdx_weights_file=mdx_weights_file, mdx_state_dict=mdx_state_dict, mdx_args=mdx_args,
                           restorer_state_dict=restorer_state_dict, restorer_weights_folder=restorer_weights_folder)

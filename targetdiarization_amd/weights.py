@@ -522,3 +522,82 @@ def recipe_apollo_state_dict(seed: int = 0, num_layers: int = 6) -> "OrderedDict
             t = u * float(1.0 / np.sqrt(int(np.prod(wshape[1:]))))
         out[name] = t.to(torch.float32).contiguous()
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# CAM++ (3D-Speaker speakerlab/models/campplus/{DTDNN,layers}.py: FCM head + D-TDNN with context-aware masking)
+# [upstream-recall]: the source is not vendored; tests/campplus_oracle.py restates the forward and csrc/campplus.hip
+# loads exactly these names (strict both ways).  BatchNorm entries: weight, bias, running_mean, running_var
+# (num_batches_tracked is dropped before packing); dense.nonlinear.batchnorm is affine=False.
+# ---------------------------------------------------------------------------------------
+def campplus_param_shapes(feat_dim: int = 80, emb: int = 192, growth: int = 32, bn_size: int = 4, init: int = 128,
+                          layers=(12, 24, 16), m: int = 32) -> "OrderedDict[str, tuple]":
+    s = OrderedDict()
+
+    def bn(p, c, affine=True):
+        for leaf in (("weight", "bias") if affine else ()) + ("running_mean", "running_var"):
+            s[p + leaf] = (c,)
+
+    s["head.conv1.weight"] = (m, 1, 3, 3); bn("head.bn1.", m)
+    for li in (1, 2):
+        for i in (0, 1):
+            p = f"head.layer{li}.{i}."
+            s[p + "conv1.weight"] = (m, m, 3, 3); bn(p + "bn1.", m)
+            s[p + "conv2.weight"] = (m, m, 3, 3); bn(p + "bn2.", m)
+            if i == 0:
+                s[p + "shortcut.0.weight"] = (m, m, 1, 1); bn(p + "shortcut.1.", m)
+    s["head.conv2.weight"] = (m, m, 3, 3); bn("head.bn2.", m)
+    c = m * (feat_dim // 8)
+    s["xvector.tdnn.linear.weight"] = (init, c, 5); bn("xvector.tdnn.nonlinear.batchnorm.", init)
+    c = init
+    bnc = bn_size * growth
+    for bi, nl in enumerate(layers, start=1):
+        for i in range(nl):
+            p = f"xvector.block{bi}.tdnnd{i + 1}."
+            bn(p + "nonlinear1.batchnorm.", c + growth * i)
+            s[p + "linear1.weight"] = (bnc, c + growth * i, 1)
+            bn(p + "nonlinear2.batchnorm.", bnc)
+            s[p + "cam_layer.linear_local.weight"] = (growth, bnc, 3)
+            s[p + "cam_layer.linear1.weight"] = (bnc // 2, bnc, 1); s[p + "cam_layer.linear1.bias"] = (bnc // 2,)
+            s[p + "cam_layer.linear2.weight"] = (growth, bnc // 2, 1); s[p + "cam_layer.linear2.bias"] = (growth,)
+        c += growth * nl
+        bn(f"xvector.transit{bi}.nonlinear.batchnorm.", c)
+        s[f"xvector.transit{bi}.linear.weight"] = (c // 2, c, 1)
+        c //= 2
+    bn("xvector.out_nonlinear.batchnorm.", c)
+    s["xvector.dense.linear.weight"] = (emb, 2 * c, 1)
+    bn("xvector.dense.nonlinear.batchnorm.", emb, affine=False)
+    return s
+
+
+def campplus_learnable(name: str) -> bool:
+    return not name.endswith(("running_mean", "running_var"))
+
+
+def recipe_campplus_state_dict(seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Deterministic fp32 weights for the CAM++ layout, in the manner of recipe_eres2netv2_state_dict.  With these
+    plain weights the embedding hardly depends on the input (the final BatchNorm's statistics do not match the
+    activations); tests calibrate `xvector.dense.nonlinear.batchnorm.*` from tests/golden/campplus_calibration.json."""
+    out = OrderedDict()
+    for name, shape in campplus_param_shapes().items():
+        n = int(np.prod(shape))
+        u = torch.from_numpy(philox_uniform("campp:" + name, n, seed)).reshape(shape)
+        leaf = name.rsplit(".", 1)[-1]
+        if leaf == "running_var":
+            t = 1.0 + 0.3 * u
+        elif leaf == "running_mean":
+            t = 0.1 * u
+        elif len(shape) == 1 and leaf == "weight":
+            t = 1.0 + 0.2 * u                      # BatchNorm gamma
+        elif leaf == "bias":
+            t = 0.1 * u
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            t = u * float(np.sqrt(3.0 / fan_in))
+        out[name] = t.to(torch.float32).contiguous()
+    return out
+
+
+def drop_num_batches_tracked(state_dict):
+    """PyTorch checkpoints carry one int64 `num_batches_tracked` per BatchNorm; the device loaders are strict, so they go."""
+    return OrderedDict((k, v) for k, v in state_dict.items() if not k.endswith("num_batches_tracked"))
