@@ -325,6 +325,30 @@ double tdx_campp_flops(const tdx_campp* h, int B, int F);
 int tdx_campp_forward(tdx_campp* h, const float* feat_dev, int B, int F, float* emb_dev,
                       void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * N5   FSMN-VAD frame posteriors — replaces `self.vad.generate(input=audio_data, cache={})` in
+ *      ASRProcessor.vad_detection  ASRProcessor.py:742-817 (funasr fsmn_vad_streaming, third-party; parity
+ *      unpinned [upstream-recall]: WavFrontend LFR 5/1 + CMVN, in_linear1/2, four FSMN blocks with a causal
+ *      20-tap depthwise memory, out_linear1/2, softmax over 248).  The segmenter that turns posteriors into
+ *      [start_ms, end_ms] ranges runs on the host (targetdiarization_amd/vad.py).
+ *      blob: TDXW container with funasr's state-dict names under "encoder." plus "cmvn.shift"[400] and
+ *      "cmvn.scale"[400] (the <AddShift> / <Rescale> vectors of am.mvn); strict both ways: a missing and an
+ *      unexpected tensor are TDX_E_BLOB with the name in tdx_last_error(), before any device work.
+ *      feat_dev [rows,80] = tdx_fbank mode-1 frames of nclips clips packed back to back; starts_dev int32
+ *      [nclips+1] on the DEVICE, ascending, starts[0] = 0, starts[nclips] = rows: clip c owns rows
+ *      [starts[c], starts[c+1]) (an empty clip is legal, a clip of one frame too).  LFR edge replication and the
+ *      zero history of the FSMN memory are per clip: no value crosses a clip boundary.
+ *      p0_dev [rows]: posterior of class 0 (the only silence class); post_dev: NULL or [rows,248].
+ *      1 <= rows <= 2^22 (workspace_bytes returns 0 outside).  16 launches per call whatever nclips.
+ * ---------------------------------------------------------------------------------- */
+typedef struct tdx_fsmnvad tdx_fsmnvad;
+int tdx_fsmnvad_create(const void* weights_blob, size_t blob_bytes, int device, tdx_fsmnvad** out);
+int tdx_fsmnvad_destroy(tdx_fsmnvad* h);
+size_t tdx_fsmnvad_workspace_bytes(const tdx_fsmnvad* h, int rows);
+double tdx_fsmnvad_flops(const tdx_fsmnvad* h, int rows);
+int tdx_fsmnvad_forward(tdx_fsmnvad* h, const float* feat_dev, const int32_t* starts_dev, int nclips, int rows,
+                        float* p0_dev, float* post_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

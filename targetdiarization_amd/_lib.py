@@ -95,6 +95,11 @@ SIGNATURES = {
     "tdx_campp_workspace_bytes": (_sz, [_vp, _i, _i]),
     "tdx_campp_flops": (C.c_double, [_vp, _i, _i]),
     "tdx_campp_forward": (_i, [_vp, _fp, _i, _i, _fp, _vp, _sz, _vp]),
+    "tdx_fsmnvad_create": (_i, [_vp, _sz, _i, C.POINTER(_vp)]),
+    "tdx_fsmnvad_destroy": (_i, [_vp]),
+    "tdx_fsmnvad_workspace_bytes": (_sz, [_vp, _i]),
+    "tdx_fsmnvad_flops": (C.c_double, [_vp, _i]),
+    "tdx_fsmnvad_forward": (_i, [_vp, _fp, _vp, _i, _i, _fp, _fp, _vp, _sz, _vp]),
 }
 
 

@@ -19,9 +19,21 @@ class ASRProcessor:
                  is_emotion: bool = False, emotion_model_dir: str = "", is_diarization: bool = False, diarization_model_dir: str = "",
                  is_asr_api: bool = False, api_config_path: str = "", verbose_log: bool = True, cuda_device: int = 0, ap=None,
                  *, asr_state_dict=None, decoder: Optional[Callable] = None, punctuation: Optional[Callable] = None, token_list=None,
-                 punc_state_dict=None, punc_vocab=None):
+                 punc_state_dict=None, punc_vocab=None, vad_state_dict=None, vad_cmvn=None):
         self.is_asr = is_asr
         self.verbose_log = verbose_log
+        self.ap = ap
+        self.is_vad = is_vad
+        self.vad = None
+        if is_vad:                                       # ASRProcessor.py:253-260: load, or print and switch the feature off
+            try:
+                from .vad import build_vad
+                self.vad = build_vad(vad_state_dict, vad_cmvn, vad_model_dir, cuda_device)
+                if self.vad is None:
+                    raise FileNotFoundError(f"no vad_state_dict, and {vad_model_dir!r} is not a directory holding model.pt and am.mvn")
+            except Exception as e:
+                self.is_vad = False
+                print(f"Failed to load FunASR VAD model: {e}")
         self.decoder = decoder
         self.punctuation = punctuation
         if punctuation is None and punc_state_dict is not None:      # ASRProcessor.py:261-268: load, or print and switch the feature off
@@ -91,6 +103,54 @@ class ASRProcessor:
             if "language" not in result:
                 result_list[i]["language"] = detect_language(result["text"])
         return result_list
+
+    # ASRProcessor.py:742-817
+    def vad_detection(self, wav_file, min_silence_sec: float = 0.5, min_clip_sec: float = 0.0, max_clip_sec: float = 0.0,
+                      format_to_sec: bool = True, output_folder: str = "", output_name: str = "", output_format: str = "wav"):
+        """16 kHz float32 audio -> [[start, end], ...] in seconds (format_to_sec=False: the detector's own milliseconds, before the
+        min_clip_sec merge and the max_clip_sec split, as the reference returns them).  `self.vad.generate(...)` (:765) is the device
+        FSMN-VAD (vad.FsmnVad); an empty detection with min_clip_sec > 0 returns [] where the reference raises IndexError."""
+        if self.verbose_log:
+            print("\nRunning module: vad_detection")
+        if not self.is_vad or self.vad is None:
+            print("FunASR VAD model hasn't been loaded. Return empty result.")
+            return []
+        sampling_rate = 16000
+        orig_audio_data = None
+        if isinstance(wav_file, str):
+            if not hasattr(self.ap, "read_audio"):
+                raise ValueError("vad_detection: pass 16 kHz float32 numpy audio (file decoding is outside the MI355X hot path)")
+            audio_data, sampling_rate = self.ap.read_audio(wav_file)
+            if sampling_rate != 16000:                   # :752-755: clips are then cut from the audio at its own rate
+                orig_audio_data = audio_data.copy()
+                audio_data, _ = self.ap.audio_resample(audio_data=audio_data, orig_sr=sampling_rate, target_sr=16000)
+            audio_data = self.ap.audio_to_mono(audio_data)
+        elif isinstance(wav_file, bytes):
+            if not hasattr(self.ap, "raw_bytes_to_ndarray"):
+                raise ValueError("vad_detection: pass 16 kHz float32 numpy audio (byte decoding is outside the MI355X hot path)")
+            audio_data = self.ap.raw_bytes_to_ndarray(audio_bytes=wav_file)
+        else:
+            audio_data = wav_file
+        from .vad import clip_ranges
+        value = self.vad.detect_batch_ms([np.asarray(audio_data, dtype=np.float32).reshape(-1)], int(min_silence_sec * 1000))[0]
+        value_sec = [[round(point / 1000, 3) for point in clip] for clip in value]
+        value_sec = clip_ranges(value_sec, min_clip_sec, max_clip_sec)
+        if output_folder:
+            if not (hasattr(self.ap, "write_to_file") and hasattr(self.ap, "split_audio_by_time")):
+                print("vad_detection: output_folder needs an `ap` with split_audio_by_time and write_to_file; nothing written")
+            else:
+                import os
+                os.makedirs(output_folder, exist_ok=True)
+                for i, clip in enumerate(value_sec):
+                    audio_clip = self.ap.split_audio_by_time(audio_data=audio_data if orig_audio_data is None else orig_audio_data, sampling_rate=sampling_rate, start_time=clip[0], end_time=clip[1])
+                    if output_name:
+                        base_name = output_name
+                    elif isinstance(wav_file, str):
+                        base_name = os.path.basename(wav_file).split(".")[0]
+                    else:
+                        base_name = os.path.abspath(output_folder).replace("\\", "/").split("/")[-1]
+                    self.ap.write_to_file(output_path=f"{output_folder}/{base_name}_{i}.{output_format}", audio_data=audio_clip, sampling_rate=sampling_rate)
+        return value_sec if format_to_sec else value
 
     def asr_detection(self, wav_file, language: str = "auto", prompt: str = "", asr_engine: str = "paraformer", no_punc: bool = False,
                       output_text_only: bool = False, output_raw_result: bool = False):

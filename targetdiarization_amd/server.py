@@ -150,8 +150,8 @@ def env_to_kwargs(environ=None) -> Dict[str, Any]:
 def model_from_env(dotenv_path: str = ".env", environ=None, **plugins):
     """main.py:101-137 (the startup hook): `.env` -> constructor kwargs -> TargetDiarizationStream.  `plugins`: what the environment
     cannot carry here — the state dicts (no checkpoint ships with the reference) and the third-party detectors
-    (sep_state_dict, spk_state_dict, asr_state_dict, sd_state_dict — the CAM++ diarizer's weights —, sd_pipeline, od_pipeline, vad,
-    stream_vad, ...)."""
+    (sep_state_dict, spk_state_dict, asr_state_dict, sd_state_dict — the CAM++ diarizer's weights —, vad_state_dict / vad_cmvn — the device
+    FSMN-VAD's; VAD_MODEL_DIR naming a directory with model.pt and am.mvn loads it as well —, sd_pipeline, od_pipeline, vad, stream_vad, ...)."""
     from .target_diarization_stream import TargetDiarizationStream
     load_dotenv(dotenv_path, environ)
     kwargs = env_to_kwargs(environ)

@@ -9,7 +9,8 @@ order of its steps, with two differences that are the point of the rewrite:
   * the third-party stages that are NOT kernels of the path are plug-ins, not hard imports:
       sd_pipeline(audio) -> {"text": [[start, end, label], ...]}        (CAM++ modelscope pipeline, :73,:126)
       od_pipeline(audio) -> [(start, end, "SPEAKER_xx"), ...]           (pyannote itertracks, :84,:132)
-      vad(audio)         -> [[start, end], ...] in seconds               (FSMN-VAD, ASRProcessor.py:742)
+      vad(audio)         -> [[start, end], ...] in seconds               (ASRProcessor.vad_detection :742; `vad_state_dict` /
+                                                                            a funasr `vad_model_dir` puts the device FSMN-VAD here)
       decoder(encoder_out[T',512]) -> (text, [(token, [s, e]), ...][, language])   (CIF + NAR decoder)
       punctuation(text)  -> text                                          (CT-Transformer, ASRProcessor.py:880-897)
     `sd_state_dict` (CAM++ weights, 3D-Speaker names) or a `diarization_pipeline_dir` holding campplus_cn_common.bin puts the
@@ -49,14 +50,19 @@ class TargetDiarization:
                  sd_pipeline: Optional[Callable] = None, od_pipeline: Optional[Callable] = None,
                  vad: Optional[Callable] = None, decoder: Optional[Callable] = None, mdx_model: Optional[Callable] = None, token_list=None,
                  punctuation: Optional[Callable] = None, mdx_state_dict=None, mdx_args=None,
-                 punc_state_dict=None, punc_vocab=None, restorer_state_dict=None, sd_state_dict=None, **kwargs):
+                 punc_state_dict=None, punc_vocab=None, restorer_state_dict=None, sd_state_dict=None, vad_state_dict=None, vad_cmvn=None,
+                 **kwargs):
         self.target_similarity_threshold = target_similarity_threshold
         self.asr_engine = asr_engine
         self.cuda_device = cuda_device
         self.verbose_log = verbose_log
         self.sd_pipeline = sd_pipeline
         self.od_pipeline = od_pipeline
-        self.vad = vad or _whole_clip_vad
+        self.vad = vad
+        if vad is None:                       # the device FSMN-VAD (vad.py, tdx_fsmnvad_*) from weights or a funasr model directory; neither: whole clip
+            from .vad import build_vad
+            self.vad = build_vad(vad_state_dict, vad_cmvn, vad_model_dir, cuda_device)
+        self.vad = self.vad or _whole_clip_vad
         self.decoder = decoder
         self.token_list = token_list          # funasr's tokens.json (absent here): ids -> text; None -> "<id>" placeholders
         self.punctuation = punctuation        # CT-Transformer punctuation restorer (ASRProcessor.punctuation_restore :880-897, third-party): text -> text

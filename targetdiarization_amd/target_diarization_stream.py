@@ -5,6 +5,7 @@ The arithmetic stages are the base class's (HotPath: MossFormer2, ERes2NetV2, Pa
 detectors are plug-ins with the reference's result formats:
     stream_vad(audio) -> [[start_s, end_s], ...]     silero-VAD `get_speech_timestamps(..., threshold 0.5, min_silence 100 ms)` (:132-133)
     vad(audio)        -> [[start_s, end_s], ...]     FunASR FSMN-VAD (`tasr.asrp.vad_detection`, :58, :135, :209)
+                                                     (`vad_state_dict=` / `vad_cmvn=` put the device detector vad.FsmnVad here)
     od_pipeline(audio)-> [(start, end, "SPEAKER_xx")] pyannote overlap detection (:179-184)
 Defaults treat the whole clip as one speech range (no detector installed), like the base class.  Everything else — the five
 buffer rules, the loudness gate, the bootstrap of the target embedding from the first released buffer, the choice of the longest

@@ -601,3 +601,71 @@ def recipe_campplus_state_dict(seed: int = 0) -> "OrderedDict[str, torch.Tensor]
 def drop_num_batches_tracked(state_dict):
     """PyTorch checkpoints carry one int64 `num_batches_tracked` per BatchNorm; the device loaders are strict, so they go."""
     return OrderedDict((k, v) for k, v in state_dict.items() if not k.endswith("num_batches_tracked"))
+
+
+# ---------------------------------------------------------------------------------------
+# FSMN-VAD (funasr/models/fsmn_vad_streaming/encoder.py, speech_fsmn_vad_zh-cn-16k-common-pytorch config)
+# [upstream-recall]: the source is not vendored and no checkpoint is at hand, parity is unpinned; tests/fsmn_vad_oracle.py
+# restates the forward and csrc/fsmn_vad.hip loads exactly these names plus cmvn.shift / cmvn.scale (strict both ways).
+# ---------------------------------------------------------------------------------------
+def fsmn_vad_param_shapes(d_in: int = 400, h1: int = 140, d: int = 250, proj: int = 128, taps: int = 20, layers: int = 4,
+                          classes: int = 248) -> "OrderedDict[str, tuple]":
+    s = OrderedDict()
+    s["encoder.in_linear1.linear.weight"] = (h1, d_in); s["encoder.in_linear1.linear.bias"] = (h1,)
+    s["encoder.in_linear2.linear.weight"] = (d, h1); s["encoder.in_linear2.linear.bias"] = (d,)
+    for i in range(layers):
+        p = f"encoder.fsmn.{i}."
+        s[p + "linear.linear.weight"] = (proj, d)
+        s[p + "fsmn_block.conv_left.weight"] = (proj, 1, taps, 1)
+        s[p + "affine.linear.weight"] = (d, proj); s[p + "affine.linear.bias"] = (d,)
+    s["encoder.out_linear1.linear.weight"] = (h1, d); s["encoder.out_linear1.linear.bias"] = (h1,)
+    s["encoder.out_linear2.linear.weight"] = (classes, h1); s["encoder.out_linear2.linear.bias"] = (classes,)
+    return s
+
+
+def recipe_fsmn_vad_state_dict(seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Deterministic fp32 weights for the FSMN-VAD layout (Philox keyed by the tensor name, fan-in scaled, like
+    recipe_campplus_state_dict).  With these plain weights every posterior sits near 1/248; the tests fit row 0 of
+    out_linear2 and the CMVN from tests/golden/fsmn_vad_calibration.json."""
+    out = OrderedDict()
+    for name, shape in fsmn_vad_param_shapes().items():
+        n = int(np.prod(shape))
+        u = torch.from_numpy(philox_uniform("fsmnvad:" + name, n, seed)).reshape(shape)
+        if name.endswith("bias"):
+            t = 0.1 * u
+        else:
+            # fan-in scaled so the activations keep their level through the stack: gain 2 where a ReLU follows (in_linear2,
+            # affine), 1 otherwise; the memory taps add a quarter of the identity path's variance
+            fan_in = int(np.prod(shape[1:]))
+            gain = 2.0 if "in_linear2" in name or "affine" in name else (0.25 if "conv_left" in name else 1.0)
+            t = u * float(np.sqrt(3.0 * gain / fan_in))
+        out[name] = t.to(torch.float32).contiguous()
+    return out
+
+
+def pack_fsmn_vad_blob(state_dict, cmvn=None) -> bytes:
+    """The TDXW blob tdx_fsmnvad_create reads: the state dict under funasr's names (a checkpoint's bare `in_linear1...` keys
+    get the `encoder.` prefix) plus cmvn.shift / cmvn.scale [400]; cmvn = (shift, scale) or None = (0, 1)."""
+    sd = OrderedDict()
+    for k, v in state_dict.items():
+        sd[k if k.startswith(("encoder.", "cmvn.")) else "encoder." + k] = v
+    if cmvn is not None:
+        sd["cmvn.shift"], sd["cmvn.scale"] = (np.asarray(torch.as_tensor(c).detach().cpu(), dtype=np.float32).reshape(-1) for c in cmvn)
+    elif "cmvn.shift" not in sd:
+        sd["cmvn.shift"], sd["cmvn.scale"] = np.zeros(400, np.float32), np.ones(400, np.float32)
+    return pack_blob(sd)
+
+
+def parse_kaldi_cmvn(path: str):
+    """am.mvn (Kaldi nnet text): the vectors after <AddShift> and <Rescale>, each `<LearnRateCoef> 0 [ v ... ]` -> (shift, scale)"""
+    import re
+    text = open(path).read()
+    out = []
+    for tag in ("<AddShift>", "<Rescale>"):
+        m = re.search(re.escape(tag) + r".*?\[(.*?)\]", text, flags=re.S)
+        if not m:
+            raise ValueError(f"{path}: no {tag} vector")
+        out.append(np.array(m.group(1).split(), dtype=np.float64).astype(np.float32))
+    if out[0].shape != out[1].shape:
+        raise ValueError(f"{path}: <AddShift> and <Rescale> differ in length")
+    return out[0], out[1]
