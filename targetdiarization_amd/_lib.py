@@ -233,6 +233,43 @@ class _GuardedCall:
         return False
 
 
+class Handle:
+    """Owner of one tdx_*_create'd handle: checks the device, copies the weight blob into a ctypes buffer, creates the handle
+    with its device current and destroys it once — on close(), or when the last reference goes.
+
+        Handle(device, who, create_fn, destroy_fn, *create_args, blob=None)
+
+    calls create_fn(*create_args, [blob, len(blob),] device_index, &handle).  `.ptr` is the c_void_p to pass to the C-ABI
+    (NULL after close(): a late call is then TDX_E_INVALID, not a use after free), `.device` the torch.device with its index
+    resolved, `.guard` the HandleGuard that serialises the calls on the handle."""
+
+    def __init__(self, device, who, create_fn, destroy_fn, *create_args, blob=None):
+        import torch
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise TdxError(f"{who} needs a HIP device (cuda:N); there is no CPU path")
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", idx)
+        self.ptr = C.c_void_p()
+        self._destroy = destroy_fn
+        if blob is not None:
+            create_args += ((C.c_char * len(blob)).from_buffer_copy(blob), len(blob))
+        with torch.cuda.device(idx):
+            check(create_fn(*create_args, idx, C.byref(self.ptr)))
+        self.guard = HandleGuard(self.device)
+
+    def close(self):
+        if self.ptr:
+            self._destroy(self.ptr)
+            self.ptr.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class GraphRunner:
     """HIP-graph replay of a C-ABI forward for SMALL problems (the reference's own call pattern is one clip per call: a
     forward is then hundreds of 10-100 us kernels and the launch gaps are a sizeable part of the latency).  The forwards

@@ -35,23 +35,13 @@ def load_state_dict(weights_folder: str):
 
 class ApolloRestorer:
     def __init__(self, state_dict, device="cuda:0", num_layers: int = 6, rows_per_launch: int = 1 << 19):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.TdxError("ApolloRestorer needs a HIP device (there is no CPU restorer)")
         self._l = _lib.lib()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
         self.num_layers = num_layers
         self.max_frames = int(rows_per_launch) // 80
         if self.max_frames < 2 * (HALO + 1) + 1:
             raise _lib.TdxError(f"ApolloRestorer: rows_per_launch must hold at least {80 * (2 * HALO + 3)} rows")
-        blob = pack_blob(state_dict)
-        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        h = C.c_void_p()
-        with torch.cuda.device(idx):
-            _lib.check(self._l.tdx_apollo_create(num_layers, buf, len(blob), idx, C.byref(h)))
-        self._h = h
-        self._guard = _lib.HandleGuard(self.device)
+        self._own = _lib.Handle(device, "ApolloRestorer", self._l.tdx_apollo_create, self._l.tdx_apollo_destroy, num_layers, blob=pack_blob(state_dict))
+        self.device, self._h, self._guard = self._own.device, self._own.ptr, self._own.guard
 
     def eval(self):
         return self
@@ -105,9 +95,5 @@ class ApolloRestorer:
                                                       ws.data_ptr(), ws.numel(), st))
         return list(y.split(lens))
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._l.tdx_apollo_destroy(self._h); self._h = None
-        except Exception:
-            pass
+    def close(self):
+        self._own.close()

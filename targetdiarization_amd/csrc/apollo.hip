@@ -29,14 +29,7 @@ constexpr int AD = 256, NB = 80, NFFT = 882, HOP = 441, NBIN = 442, KP = 896, HA
 constexpr int FEAT = 79 * 11 + 95;          // band-feature channels of all bands (2 bw + 1 each)
 constexpr int HEADS = 79 * 20 + 188;        // head output channels of all bands (4 bw each)
 constexpr float EPS_P = 1.1920928955078125e-07f;   // finfo(float32).eps
-inline size_t al(size_t n) { return (n + 63) / 64 * 64; }
 __host__ __device__ inline int band_w(int b) { return b < 79 ? 5 : 47; }
-#define LAUNCH_CHECK()                                    \
-    do {                                                  \
-        hipError_t e__ = hipGetLastError();               \
-        if (e__ != hipSuccess) return tdx::fail_hip(e__, __FILE__, __LINE__); \
-    } while (0)
-#define TRY(x) do { int rc__ = (x); if (rc__ != TDX_OK) return rc__; } while (0)
 
 // the items of one forward (kernel argument, < 2 KB)
 struct ApItems {
@@ -270,7 +263,7 @@ struct ALayer { size_t cosT, sinT, Wqkv, Wo, W1, W2; AIcb icb[3]; };
 
 struct tdx_apollo {
     int device = 0, L = 0;
-    float* dev = nullptr;
+    tdx::DevBuf dev;
     size_t bana = 0, bsyn = 0, w2 = 0, Wt = 0, bin = 0, Wh = 0, bh = 0;
     std::vector<ALayer> layers;
 };
@@ -279,115 +272,92 @@ extern "C" {
 
 int tdx_apollo_create(int num_layers, const void* blob, size_t blob_bytes, int device, tdx_apollo** out) {
     if (!blob || !out || num_layers < 1) return tdx::fail(TDX_E_INVALID, "tdx_apollo_create: bad argument");
-    tdx::Blob bl;
-    if (!bl.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_apollo_create: malformed TDXW blob");
-    std::vector<float> host;
-    bool ok = true;
-    std::string bad;
-    // exact shape check (a strict load_state_dict compares shapes, not element counts)
-    auto get = [&](const std::string& name, std::initializer_list<uint32_t> dims) -> const float* {
-        const tdx::BlobTensor* t = bl.find(name);
-        bool same = t && t->ndim == (int)dims.size();
-        if (same) { int d = 0; for (uint32_t v : dims) same = same && t->dims[d++] == v; }
-        if (!same) { ok = false; if (bad.empty()) bad = name; return nullptr; }
-        return t->data;
-    };
-    auto alloc = [&](size_t n) { size_t o = host.size(); host.resize(o + al(n), 0.f); return o; };
-    auto push = [&](const float* p, size_t n) { size_t o = alloc(n); if (p) memcpy(host.data() + o, p, n * sizeof(float)); return o; };
+    tdx::Loader ld;       // every tensor by exact shape (a strict load_state_dict compares shapes, not element counts)
+    if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_apollo_create: malformed TDXW blob");
     // W'[o][c] = W[o][c] * gain[c]  (the RMSNorm gain in front of a 1x1 conv, folded)
     auto push_folded = [&](const float* W, const float* gain, int O, int Cin) {
-        size_t o = alloc((size_t)O * Cin);
-        if (W && gain) for (int i = 0; i < O; ++i) for (int c = 0; c < Cin; ++c) host[o + (size_t)i * Cin + c] = W[(size_t)i * Cin + c] * gain[c];
+        size_t o = ld.room((size_t)O * Cin);
+        if (W && gain) for (int i = 0; i < O; ++i) for (int c = 0; c < Cin; ++c) ld.host[o + (size_t)i * Cin + c] = W[(size_t)i * Cin + c] * gain[c];
         return o;
     };
-    tdx_apollo* h = new tdx_apollo();
+    std::unique_ptr<tdx_apollo> h(new tdx_apollo());
     h->L = num_layers;
     // analysis / synthesis DFT bases (double, exact angle reduction), periodic hann window
     {
         std::vector<double> w(NFFT);
         for (int k = 0; k < NFFT; ++k) w[k] = 0.5 - 0.5 * cos(2.0 * M_PI * k / NFFT);
-        h->bana = alloc((size_t)KP * KP);
-        h->bsyn = alloc((size_t)KP * KP);
-        h->w2 = alloc(NFFT);
-        for (int k = 0; k < NFFT; ++k) host[h->w2 + k] = (float)(w[k] * w[k]);
+        h->bana = ld.room((size_t)KP * KP);
+        h->bsyn = ld.room((size_t)KP * KP);
+        h->w2 = ld.room(NFFT);
+        for (int k = 0; k < NFFT; ++k) ld.host[h->w2 + k] = (float)(w[k] * w[k]);
         for (int f = 0; f < NBIN; ++f) {
             const double cre = (f == 0 || f == NBIN - 1) ? 1.0 : 2.0, cim = (f == 0 || f == NBIN - 1) ? 0.0 : 2.0;
             for (int k = 0; k < NFFT; ++k) {
                 const double ang = 2.0 * M_PI * (double)(((long)f * k) % NFFT) / NFFT, c = cos(ang), s = sin(ang);
-                host[h->bana + (size_t)f * KP + k] = (float)(w[k] * c);                    // Re X_f = sum w x cos
-                host[h->bana + (size_t)(NBIN + f) * KP + k] = (float)(-w[k] * s);          // Im X_f = -sum w x sin
-                host[h->bsyn + (size_t)k * KP + f] = (float)(cre * c * w[k] / NFFT);       // C2R: Im of bins 0 and 441 ignored
-                host[h->bsyn + (size_t)k * KP + NBIN + f] = (float)(-cim * s * w[k] / NFFT);
+                ld.host[h->bana + (size_t)f * KP + k] = (float)(w[k] * c);                    // Re X_f = sum w x cos
+                ld.host[h->bana + (size_t)(NBIN + f) * KP + k] = (float)(-w[k] * s);          // Im X_f = -sum w x sin
+                ld.host[h->bsyn + (size_t)k * KP + f] = (float)(cre * c * w[k] / NFFT);       // C2R: Im of bins 0 and 441 ignored
+                ld.host[h->bsyn + (size_t)k * KP + NBIN + f] = (float)(-cim * s * w[k] / NFFT);
             }
         }
     }
     // band-split input: Wt[11 b + k][c] = W_b[c][k] * gain_b[k], bias [80][256]
-    h->Wt = alloc((size_t)FEAT * AD);
-    h->bin = alloc((size_t)NB * AD);
-    for (int b = 0; b < NB && ok; ++b) {
+    h->Wt = ld.room((size_t)FEAT * AD);
+    h->bin = ld.room((size_t)NB * AD);
+    for (int b = 0; b < NB && ld.ok(); ++b) {
         const uint32_t nk = 2 * band_w(b) + 1;
-        const float* gn = get("BN." + std::to_string(b) + ".0.weight", {nk});
-        const float* W = get("BN." + std::to_string(b) + ".1.weight", {AD, nk, 1});
-        const float* bb = get("BN." + std::to_string(b) + ".1.bias", {AD});
-        if (!ok) break;
+        const float* gn = ld.get("BN." + std::to_string(b) + ".0.weight", {nk});
+        const float* W = ld.get("BN." + std::to_string(b) + ".1.weight", {AD, nk, 1});
+        const float* bb = ld.get("BN." + std::to_string(b) + ".1.bias", {AD});
+        if (!ld.ok()) break;
         for (int c = 0; c < AD; ++c) {
-            for (uint32_t k = 0; k < nk; ++k) host[h->Wt + (size_t)(11 * b + k) * AD + c] = W[(size_t)c * nk + k] * gn[k];
-            host[h->bin + (size_t)b * AD + c] = bb[c];
+            for (uint32_t k = 0; k < nk; ++k) ld.host[h->Wt + (size_t)(11 * b + k) * AD + c] = W[(size_t)c * nk + k] * gn[k];
+            ld.host[h->bin + (size_t)b * AD + c] = bb[c];
         }
     }
-    for (int l = 0; l < num_layers && ok; ++l) {
+    for (int l = 0; l < num_layers && ld.ok(); ++l) {
         const std::string p = "net." + std::to_string(l) + ".";
         ALayer w;
-        w.cosT = push(get(p + "band_net.cos_freq", {100, 32}), 100 * 32);
-        w.sinT = push(get(p + "band_net.sin_freq", {100, 32}), 100 * 32);
-        w.Wqkv = push_folded(get(p + "band_net.weight.weight", {3 * AD, AD, 1}), get(p + "band_net.input_norm.weight", {AD}), 3 * AD, AD);
-        w.Wo = push(get(p + "band_net.output.weight", {AD, AD, 1}), (size_t)AD * AD);
-        w.W1 = push_folded(get(p + "band_net.MLP.1.weight", {8 * AD, AD, 1}), get(p + "band_net.MLP.0.weight", {AD}), 8 * AD, AD);
-        w.W2 = push(get(p + "band_net.MLP_output.weight", {AD, 4 * AD, 1}), (size_t)AD * 4 * AD);
+        w.cosT = ld.push(ld.get(p + "band_net.cos_freq", {100, 32}), 100 * 32);
+        w.sinT = ld.push(ld.get(p + "band_net.sin_freq", {100, 32}), 100 * 32);
+        w.Wqkv = push_folded(ld.get(p + "band_net.weight.weight", {3 * AD, AD, 1}), ld.get(p + "band_net.input_norm.weight", {AD}), 3 * AD, AD);
+        w.Wo = ld.push(ld.get(p + "band_net.output.weight", {AD, AD, 1}), (size_t)AD * AD);
+        w.W1 = push_folded(ld.get(p + "band_net.MLP.1.weight", {8 * AD, AD, 1}), ld.get(p + "band_net.MLP.0.weight", {AD}), 8 * AD, AD);
+        w.W2 = ld.push(ld.get(p + "band_net.MLP_output.weight", {AD, 4 * AD, 1}), (size_t)AD * 4 * AD);
         for (int b = 0; b < 3; ++b) {
             const std::string q = p + "seq_net.blocks." + std::to_string(b) + ".conv.";
             AIcb& c = w.icb[b];
-            const float* w7 = get(q + "0.weight", {AD, 1, 7});
-            c.w7 = alloc(7 * AD);
-            if (w7) for (int ch = 0; ch < AD; ++ch) for (int j = 0; j < 7; ++j) host[c.w7 + (size_t)j * AD + ch] = w7[ch * 7 + j];
-            c.b7 = push(get(q + "0.bias", {AD}), AD);
-            c.Wa = push_folded(get(q + "2.weight", {4 * AD, AD, 1}), get(q + "1.weight", {AD}), 4 * AD, AD);
-            c.ba = push(get(q + "2.bias", {4 * AD}), 4 * AD);
-            c.Wb = push(get(q + "4.weight", {AD, 4 * AD, 1}), (size_t)AD * 4 * AD);
-            c.bb = push(get(q + "4.bias", {AD}), AD);
+            c.w7 = ld.push_tapmajor(ld.get(q + "0.weight", {AD, 1, 7}), AD, 7);
+            c.b7 = ld.push(ld.get(q + "0.bias", {AD}), AD);
+            c.Wa = push_folded(ld.get(q + "2.weight", {4 * AD, AD, 1}), ld.get(q + "1.weight", {AD}), 4 * AD, AD);
+            c.ba = ld.push(ld.get(q + "2.bias", {4 * AD}), 4 * AD);
+            c.Wb = ld.push(ld.get(q + "4.weight", {AD, 4 * AD, 1}), (size_t)AD * 4 * AD);
+            c.bb = ld.push(ld.get(q + "4.bias", {AD}), AD);
         }
         h->layers.push_back(w);
     }
     // heads: Wh[20 b + j][c] = W_b[j][c] * gain_b[c], bh[20 b + j]
-    h->Wh = alloc((size_t)HEADS * AD);
-    h->bh = alloc(HEADS);
-    for (int b = 0; b < NB && ok; ++b) {
+    h->Wh = ld.room((size_t)HEADS * AD);
+    h->bh = ld.room(HEADS);
+    for (int b = 0; b < NB && ld.ok(); ++b) {
         const uint32_t no = 4 * band_w(b);
-        const float* gn = get("output." + std::to_string(b) + ".0.weight", {AD});
-        const float* W = get("output." + std::to_string(b) + ".1.weight", {no, AD, 1});
-        const float* bb = get("output." + std::to_string(b) + ".1.bias", {no});
-        if (!ok) break;
+        const float* gn = ld.get("output." + std::to_string(b) + ".0.weight", {AD});
+        const float* W = ld.get("output." + std::to_string(b) + ".1.weight", {no, AD, 1});
+        const float* bb = ld.get("output." + std::to_string(b) + ".1.bias", {no});
+        if (!ld.ok()) break;
         for (uint32_t j = 0; j < no; ++j) {
-            for (int c = 0; c < AD; ++c) host[h->Wh + (size_t)(20 * b + j) * AD + c] = W[(size_t)j * AD + c] * gn[c];
-            host[h->bh + 20 * b + j] = bb[j];
+            for (int c = 0; c < AD; ++c) ld.host[h->Wh + (size_t)(20 * b + j) * AD + c] = W[(size_t)j * AD + c] * gn[c];
+            ld.host[h->bh + 20 * b + j] = bb[j];
         }
     }
-    if (!ok) { delete h; return tdx::fail(TDX_E_BLOB, "tdx_apollo_create: tensor missing or of the wrong shape: " + bad); }
-    { const std::string extra = bl.first_unused(); if (!extra.empty()) { delete h; return tdx::fail(TDX_E_BLOB, "tdx_apollo_create: unexpected tensor in the blob: " + extra); } }
-    tdx::DeviceGuard guard(device);
-    hipError_t e = guard.err;
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
     h->device = device;
-    e = hipMalloc(&h->dev, host.size() * sizeof(float));
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-    e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(h->dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-    *out = h;
+    TRY(ld.finish("tdx_apollo_create", true, device, h->dev));
+    *out = h.release();
     return TDX_OK;
 }
 
 int tdx_apollo_destroy(tdx_apollo* h) {
-    if (h) { if (h->dev) hipFree(h->dev); delete h; }
+    delete h;
     return TDX_OK;
 }
 

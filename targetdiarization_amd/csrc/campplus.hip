@@ -39,15 +39,7 @@ const int kDil[NBLOCK] = {1, 2, 2};
 const int kCin[NBLOCK] = {128, 256, 512};       // channels entering the block
 const int kLd[NBLOCK] = {512, 1024, 1024};      // channels leaving it = buffer pitch
 
-inline size_t al(size_t n) { return (n + 63) / 64 * 64; }
-inline int up(int n, int m) { return (n + m - 1) / m * m; }
 
-#define LAUNCH_CHECK()                                    \
-    do {                                                  \
-        hipError_t e__ = hipGetLastError();               \
-        if (e__ != hipSuccess) return tdx::fail_hip(e__, __FILE__, __LINE__); \
-    } while (0)
-#define TRY(x) do { int rc__ = (x); if (rc__ != TDX_OK) return rc__; } while (0)
 
 // head.conv1: conv3x3(1->32, pad 1) + BN + ReLU on x[b, h=freq, w=time] = feat[b, w, h]
 __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ feat, const float* __restrict__ w9,   // [9][32]
@@ -258,7 +250,7 @@ int plain_gemm(const float* A, long lda, const float* dev, const ConvW& cw, long
 
 struct tdx_campp {
     int device = 0;
-    float* dev = nullptr;
+    tdx::DevBuf dev;
     size_t stem_w, stem_b;
     ConvW l_c1[4], l_c2[4], l_sc[2], head2, tdnn;      // head.layer{1,2}.{0,1} in order; shortcuts of the two .0 blocks
     std::vector<LayerW> layers;
@@ -270,22 +262,15 @@ extern "C" {
 
 int tdx_campp_create(const void* blob, size_t blob_bytes, int device, tdx_campp** out) {
     if (!blob || !out) return tdx::fail(TDX_E_INVALID, "tdx_campp_create: null argument");
-    tdx::Blob bl;
-    if (!bl.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_campp_create: malformed TDXW blob");
-    std::vector<float> host;
-    bool ok = true; std::string missing;
-    auto get = [&](const std::string& name, size_t n) -> const float* {
-        const tdx::BlobTensor* t = bl.find(name);
-        if (!t || t->numel != n) { ok = false; if (missing.empty()) missing = name; return nullptr; }
-        return t->data;
-    };
+    tdx::Loader ld;
+    if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_campp_create: malformed TDXW blob");
     struct BN { std::vector<double> s, sh; };
     // eval BatchNorm `p` -> y = x*s + sh   (affine = false: running statistics only)
     auto bn = [&](const std::string& p, int N, bool affine = true) -> BN {
         BN r; r.s.assign(N, 1.0); r.sh.assign(N, 0.0);
-        const float *g = affine ? get(p + "weight", N) : nullptr, *be = affine ? get(p + "bias", N) : nullptr;
-        const float *mu = get(p + "running_mean", N), *var = get(p + "running_var", N);
-        if (!ok) return r;
+        const float *g = affine ? ld.get(p + "weight", N) : nullptr, *be = affine ? ld.get(p + "bias", N) : nullptr;
+        const float *mu = ld.get(p + "running_mean", N), *var = ld.get(p + "running_var", N);
+        if (!ld.ok()) return r;
         for (int n = 0; n < N; ++n) {
             r.s[n] = (affine ? (double)g[n] : 1.0) / sqrt((double)var[n] + 1e-5);
             r.sh[n] = (affine ? (double)be[n] : 0.0) - (double)mu[n] * r.s[n];
@@ -293,42 +278,36 @@ int tdx_campp_create(const void* blob, size_t blob_bytes, int device, tdx_campp*
         return r;
     };
     auto put = [&](const std::vector<double>& v) -> size_t {
-        const size_t o = host.size(); host.resize(o + al(v.size()), 0.f);
-        for (size_t i = 0; i < v.size(); ++i) host[o + i] = (float)v[i];
-        return o;
-    };
-    auto copy = [&](const std::string& name, size_t n) -> size_t {
-        const size_t o = host.size(); host.resize(o + al(n), 0.f);
-        const float* p = get(name, n);
-        if (p) memcpy(host.data() + o, p, n * sizeof(float));
+        const size_t o = ld.room(v.size());
+        for (size_t i = 0; i < v.size(); ++i) ld.host[o + i] = (float)v[i];
         return o;
     };
     // bias-free conv [N,cin,taps] followed by eval BatchNorm `bnp` ("" = none) -> [Npad][taps][cinp] + bias[Npad]
     auto fold = [&](const std::string& wname, const std::string& bnp, int N, int cin, int taps, bool affine = true) -> ConvW {
         ConvW cw; cw.N = N; cw.Npad = up(N, 128); cw.cinp = up(cin, 32); cw.taps = taps;
-        const float* W = get(wname, (size_t)N * cin * taps);
+        const float* W = ld.get(wname, (size_t)N * cin * taps);
         BN b; if (!bnp.empty()) b = bn(bnp, N, affine);
-        cw.w = host.size(); host.resize(host.size() + al((size_t)cw.Npad * taps * cw.cinp), 0.f);
-        cw.b = host.size(); host.resize(host.size() + al(cw.Npad), 0.f);
-        if (!ok) return cw;
+        cw.w = ld.room((size_t)cw.Npad * taps * cw.cinp);
+        cw.b = ld.room(cw.Npad);
+        if (!ld.ok()) return cw;
         for (int n = 0; n < N; ++n) {
             const double sc = bnp.empty() ? 1.0 : b.s[n];
-            host[cw.b + n] = bnp.empty() ? 0.f : (float)b.sh[n];
+            ld.host[cw.b + n] = bnp.empty() ? 0.f : (float)b.sh[n];
             for (int c = 0; c < cin; ++c)
                 for (int t = 0; t < taps; ++t)
-                    host[cw.w + ((size_t)n * taps + t) * cw.cinp + c] = (float)((double)W[((size_t)n * cin + c) * taps + t] * sc);
+                    ld.host[cw.w + ((size_t)n * taps + t) * cw.cinp + c] = (float)((double)W[((size_t)n * cin + c) * taps + t] * sc);
         }
         return cw;
     };
-    tdx_campp* h = new tdx_campp();
+    std::unique_ptr<tdx_campp> h(new tdx_campp());
     {   // head.conv1 [32,1,3,3] + bn1 -> w9[9][32], bias[32]
-        const float* W = get("head.conv1.weight", HC * 9);
+        const float* W = ld.get("head.conv1.weight", HC * 9);
         const BN b = bn("head.bn1.", HC);
-        h->stem_w = host.size(); host.resize(host.size() + al(9 * HC), 0.f);
-        h->stem_b = host.size(); host.resize(host.size() + al(HC), 0.f);
-        if (ok) for (int n = 0; n < HC; ++n) {
-            host[h->stem_b + n] = (float)b.sh[n];
-            for (int t = 0; t < 9; ++t) host[h->stem_w + t * HC + n] = (float)((double)W[n * 9 + t] * b.s[n]);
+        h->stem_w = ld.room(9 * HC);
+        h->stem_b = ld.room(HC);
+        if (ld.ok()) for (int n = 0; n < HC; ++n) {
+            ld.host[h->stem_b + n] = (float)b.sh[n];
+            for (int t = 0; t < 9; ++t) ld.host[h->stem_w + t * HC + n] = (float)((double)W[n * 9 + t] * b.s[n]);
         }
     }
     for (int i = 0; i < 4; ++i) {
@@ -339,35 +318,35 @@ int tdx_campp_create(const void* blob, size_t blob_bytes, int device, tdx_campp*
     }
     h->head2 = fold("head.conv2.weight", "head.bn2.", HC, HC, 9);
     {   // xvector.tdnn.linear [128, 320 (c*10 + f), 5] + BN -> [128][j*320 + f*32 + c]
-        const float* W = get("xvector.tdnn.linear.weight", (size_t)BNC * 320 * 5);
+        const float* W = ld.get("xvector.tdnn.linear.weight", (size_t)BNC * 320 * 5);
         const BN b = bn("xvector.tdnn.nonlinear.batchnorm.", BNC);
         ConvW& cw = h->tdnn; cw.N = BNC; cw.Npad = BNC; cw.cinp = 1600; cw.taps = 1;
-        cw.w = host.size(); host.resize(host.size() + al((size_t)BNC * 1600), 0.f);
-        cw.b = host.size(); host.resize(host.size() + al(BNC), 0.f);
-        if (ok) for (int n = 0; n < BNC; ++n) {
-            host[cw.b + n] = (float)b.sh[n];
+        cw.w = ld.room((size_t)BNC * 1600);
+        cw.b = ld.room(BNC);
+        if (ld.ok()) for (int n = 0; n < BNC; ++n) {
+            ld.host[cw.b + n] = (float)b.sh[n];
             for (int c = 0; c < HC; ++c)
                 for (int f = 0; f < 10; ++f)
                     for (int j = 0; j < 5; ++j)
-                        host[cw.w + (size_t)n * 1600 + j * 320 + f * HC + c] = (float)((double)W[((size_t)n * 320 + c * 10 + f) * 5 + j] * b.s[n]);
+                        ld.host[cw.w + (size_t)n * 1600 + j * 320 + f * HC + c] = (float)((double)W[((size_t)n * 320 + c * 10 + f) * 5 + j] * b.s[n]);
         }
     }
-    for (int bi = 0; bi < NBLOCK && ok; ++bi) {
-        for (int i = 0; i < kLayers[bi] && ok; ++i) {
+    for (int bi = 0; bi < NBLOCK && ld.ok(); ++bi) {
+        for (int i = 0; i < kLayers[bi] && ld.ok(); ++i) {
             const std::string p = "xvector.block" + std::to_string(bi + 1) + ".tdnnd" + std::to_string(i + 1) + ".";
             LayerW L; L.cin = kCin[bi] + GROWTH * i;
             const BN b1 = bn(p + "nonlinear1.batchnorm.", L.cin);
             L.s1 = put(b1.s); L.sh1 = put(b1.sh);
             L.lin1 = fold(p + "linear1.weight", p + "nonlinear2.batchnorm.", BNC, L.cin, 1);
             {   // cam_layer.linear_local [32,128,3] -> [32][tap*128 + c]
-                const float* W = get(p + "cam_layer.linear_local.weight", (size_t)GROWTH * BNC * 3);
-                L.wl = host.size(); host.resize(host.size() + al((size_t)GROWTH * 3 * BNC), 0.f);
+                const float* W = ld.get(p + "cam_layer.linear_local.weight", (size_t)GROWTH * BNC * 3);
+                L.wl = ld.room((size_t)GROWTH * 3 * BNC);
                 if (W) for (int n = 0; n < GROWTH; ++n)
                     for (int c = 0; c < BNC; ++c)
-                        for (int t = 0; t < 3; ++t) host[L.wl + (size_t)n * 3 * BNC + t * BNC + c] = W[((size_t)n * BNC + c) * 3 + t];
+                        for (int t = 0; t < 3; ++t) ld.host[L.wl + (size_t)n * 3 * BNC + t * BNC + c] = W[((size_t)n * BNC + c) * 3 + t];
             }
-            L.cw1 = copy(p + "cam_layer.linear1.weight", 64 * BNC); L.cb1 = copy(p + "cam_layer.linear1.bias", 64);
-            L.cw2 = copy(p + "cam_layer.linear2.weight", GROWTH * 64); L.cb2 = copy(p + "cam_layer.linear2.bias", GROWTH);
+            L.cw1 = ld.push(ld.get(p + "cam_layer.linear1.weight", 64 * BNC), 64 * BNC); L.cb1 = ld.push(ld.get(p + "cam_layer.linear1.bias", 64), 64);
+            L.cw2 = ld.push(ld.get(p + "cam_layer.linear2.weight", GROWTH * 64), GROWTH * 64); L.cb2 = ld.push(ld.get(p + "cam_layer.linear2.bias", GROWTH), GROWTH);
             h->layers.push_back(L);
         }
         const std::string p = "xvector.transit" + std::to_string(bi + 1) + ".";
@@ -377,27 +356,18 @@ int tdx_campp_create(const void* blob, size_t blob_bytes, int device, tdx_campp*
         // the BN of out_nonlinear follows transit3's convolution: folded; its ReLU is the epilogue's
         t.lin = fold(p + "linear.weight", bi == NBLOCK - 1 ? "xvector.out_nonlinear.batchnorm." : "", t.cin / 2, t.cin, 1);
     }
-    if (ok) {
+    if (ld.ok()) {
         const ConvW d = fold("xvector.dense.linear.weight", "xvector.dense.nonlinear.batchnorm.", EMB, 1024, 1, false);
         h->dense_w = d.w; h->dense_b = d.b;
     }
-    if (!ok) { delete h; return tdx::fail(TDX_E_BLOB, "tdx_campp_create: tensor missing or wrong size: " + missing); }
-    const std::string extra = bl.first_unused();
-    if (!extra.empty()) { delete h; return tdx::fail(TDX_E_BLOB, "tdx_campp_create: unexpected tensor: " + extra); }
-    tdx::DeviceGuard guard(device);
-    hipError_t e = guard.err;
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
     h->device = device;
-    e = hipMalloc(&h->dev, host.size() * sizeof(float));
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-    e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(h->dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-    *out = h;
+    TRY(ld.finish("tdx_campp_create", true, device, h->dev));
+    *out = h.release();
     return TDX_OK;
 }
 
 int tdx_campp_destroy(tdx_campp* h) {
-    if (h) { if (h->dev) hipFree(h->dev); delete h; }
+    delete h;
     return TDX_OK;
 }
 

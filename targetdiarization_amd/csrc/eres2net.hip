@@ -22,6 +22,7 @@
 #include "gemm_h3.hpp"
 #include "devutil.hpp"
 #include "tdx_common.hpp"
+#include "weight_planes.hpp"
 
 using namespace tdx;
 
@@ -32,15 +33,7 @@ const int kBlocks[NSTAGE] = {3, 4, 6, 3};
 const int kPlanes[NSTAGE] = {64, 128, 256, 512};
 const int kStride[NSTAGE] = {1, 2, 2, 2};
 
-inline size_t al(size_t n) { return (n + 63) / 64 * 64; }
-inline int up(int n, int m) { return (n + m - 1) / m * m; }
 
-#define LAUNCH_CHECK()                                    \
-    do {                                                  \
-        hipError_t e__ = hipGetLastError();               \
-        if (e__ != hipSuccess) return tdx::fail_hip(e__, __FILE__, __LINE__); \
-    } while (0)
-#define TRY(x) do { int rc__ = (x); if (rc__ != TDX_OK) return rc__; } while (0)
 
 __device__ __forceinline__ float relu20(float v) { return fminf(fmaxf(v, 0.f), 20.f); }
 
@@ -598,8 +591,8 @@ inline int conv_gemm_h3_tapsplit(const unsigned char* Ap, const float* inv_scale
 
 struct tdx_eres2net {
     int device = 0;
-    float* dev; std::vector<BlockW> blocks; size_t stem_w, stem_b, seg_w, seg_b; ConvW ds; AffW fuse34;
-    unsigned char* dev_planes = nullptr;      // x3 planes of the stage-3/4 and layer3_ds convolution weights
+    tdx::DevBuf dev; std::vector<BlockW> blocks; size_t stem_w, stem_b, seg_w, seg_b; ConvW ds; AffW fuse34;
+    tdx::DevBuf dev_planes;                   // x3 planes of the stage-3/4 and layer3_ds convolution weights
     size_t consts = 0;                        // dev + consts: {2^-10, 2^-9} inverse static scales, then 8 KB of zeros (halo row)
 };
 
@@ -668,32 +661,25 @@ extern "C" {
 
 int tdx_eres2net_create(const void* blob, size_t blob_bytes, int device, tdx_eres2net** out) {
     if (!blob || !out) return tdx::fail(TDX_E_INVALID, "tdx_eres2net_create: null argument");
-    tdx::Blob bl;
-    if (!bl.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_eres2net_create: malformed TDXW blob");
-    std::vector<float> host;
-    bool ok = true; std::string missing;
-    auto get = [&](const std::string& name, size_t n) -> const float* {
-        const tdx::BlobTensor* t = bl.find(name);
-        if (!t || t->numel != n) { ok = false; if (missing.empty()) missing = name; return nullptr; }
-        return t->data;
-    };
+    tdx::Loader ld;       // (not strict: a checkpoint carries the BatchNorms' num_batches_tracked and the like)
+    if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_eres2net_create: malformed TDXW blob");
     // conv [N,Cin,kh,kw] (+bias) followed by eval BatchNorm `bn` ("" = none) -> [Npad][taps][cinp], bias[Npad]
     auto fold = [&](const std::string& wname, const std::string& bname, const std::string& bn, int N, int cin, int taps) -> ConvW {
         ConvW cw; cw.N = N; cw.Npad = up(N, 128); cw.cin = cin; cw.cinp = up(cin, 32); cw.taps = taps;
-        const float* W = get(wname, (size_t)N * cin * taps);
-        const float* cb = bname.empty() ? nullptr : get(bname, N);
+        const float* W = ld.get(wname, (size_t)N * cin * taps);
+        const float* cb = bname.empty() ? nullptr : ld.get(bname, N);
         const float *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
-        if (!bn.empty()) { g = get(bn + "weight", N); be = get(bn + "bias", N); mu = get(bn + "running_mean", N); var = get(bn + "running_var", N); }
-        cw.w = host.size(); host.resize(host.size() + al((size_t)cw.Npad * taps * cw.cinp), 0.f);
-        cw.b = host.size(); host.resize(host.size() + al(cw.Npad), 0.f);
-        if (!ok) return cw;
+        if (!bn.empty()) { g = ld.get(bn + "weight", N); be = ld.get(bn + "bias", N); mu = ld.get(bn + "running_mean", N); var = ld.get(bn + "running_var", N); }
+        cw.w = ld.room((size_t)cw.Npad * taps * cw.cinp);
+        cw.b = ld.room(cw.Npad);
+        if (!ld.ok()) return cw;
         for (int n = 0; n < N; ++n) {
             const double sc = bn.empty() ? 1.0 : (double)g[n] / sqrt((double)var[n] + 1e-5);
             const double b0 = cb ? (double)cb[n] : 0.0;
-            host[cw.b + n] = (float)(bn.empty() ? b0 : (b0 - (double)mu[n]) * sc + (double)be[n]);
+            ld.host[cw.b + n] = (float)(bn.empty() ? b0 : (b0 - (double)mu[n]) * sc + (double)be[n]);
             for (int c = 0; c < cin; ++c)
                 for (int t = 0; t < taps; ++t)
-                    host[cw.w + ((size_t)n * taps + t) * cw.cinp + c] = (float)((double)W[((size_t)n * cin + c) * taps + t] * sc);
+                    ld.host[cw.w + ((size_t)n * taps + t) * cw.cinp + c] = (float)((double)W[((size_t)n * cin + c) * taps + t] * sc);
         }
         return cw;
     };
@@ -703,23 +689,23 @@ int tdx_eres2net_create(const void* blob, size_t blob_bytes, int device, tdx_ere
         a.c3 = fold(p + "local_att.3.weight", p + "local_att.3.bias", p + "local_att.4.", C, a.inter, 1);
         return a;
     };
-    tdx_eres2net* h = new tdx_eres2net();
+    std::unique_ptr<tdx_eres2net> h(new tdx_eres2net());
     // stem: [64,1,3,3] + bn1 -> w9[9][64], bias[64]
     {
-        const float* W = get("conv1.weight", 64 * 9);
-        const float *g = get("bn1.weight", 64), *be = get("bn1.bias", 64), *mu = get("bn1.running_mean", 64), *var = get("bn1.running_var", 64);
-        h->stem_w = host.size(); host.resize(host.size() + al(9 * 64), 0.f);
-        h->stem_b = host.size(); host.resize(host.size() + al(64), 0.f);
-        if (ok) for (int n = 0; n < 64; ++n) {
+        const float* W = ld.get("conv1.weight", 64 * 9);
+        const float *g = ld.get("bn1.weight", 64), *be = ld.get("bn1.bias", 64), *mu = ld.get("bn1.running_mean", 64), *var = ld.get("bn1.running_var", 64);
+        h->stem_w = ld.room(9 * 64);
+        h->stem_b = ld.room(64);
+        if (ld.ok()) for (int n = 0; n < 64; ++n) {
             const double sc = (double)g[n] / sqrt((double)var[n] + 1e-5);
-            host[h->stem_b + n] = (float)((double)be[n] - (double)mu[n] * sc);
-            for (int t = 0; t < 9; ++t) host[h->stem_w + t * 64 + n] = (float)((double)W[n * 9 + t] * sc);
+            ld.host[h->stem_b + n] = (float)((double)be[n] - (double)mu[n] * sc);
+            for (int t = 0; t < 9; ++t) ld.host[h->stem_w + t * 64 + n] = (float)((double)W[n * 9 + t] * sc);
         }
     }
     int in_planes = 64;
-    for (int s = 0; s < NSTAGE && ok; ++s) {
+    for (int s = 0; s < NSTAGE && ld.ok(); ++s) {
         const int planes = kPlanes[s], width = planes * 24 / 64, cout = planes * 4;
-        for (int i = 0; i < kBlocks[s] && ok; ++i) {
+        for (int i = 0; i < kBlocks[s] && ld.ok(); ++i) {
             const std::string p = "layer" + std::to_string(s + 1) + "." + std::to_string(i) + ".";
             BlockW b;
             b.stride = i == 0 ? kStride[s] : 1; b.cin = in_planes; b.width = width; b.wpad = up(width, 32); b.w4 = width * SCALE;
@@ -734,29 +720,17 @@ int tdx_eres2net_create(const void* blob, size_t blob_bytes, int device, tdx_ere
             in_planes = cout;
         }
     }
-    if (ok) {
+    if (ld.ok()) {
         h->ds = fold("layer3_ds.weight", "", "", 2048, 1024, 9);
         h->fuse34 = fold_aff("fuse34.", 2048);
-        h->seg_w = host.size(); host.resize(host.size() + al((size_t)EMB * 40960), 0.f);
-        const float* sw = get("seg_1.weight", (size_t)EMB * 40960);
-        if (sw) memcpy(host.data() + h->seg_w, sw, (size_t)EMB * 40960 * sizeof(float));
-        h->seg_b = host.size(); host.resize(host.size() + al(EMB), 0.f);
-        const float* sb = get("seg_1.bias", EMB);
-        if (sb) memcpy(host.data() + h->seg_b, sb, EMB * sizeof(float));
+        h->seg_w = ld.push(ld.get("seg_1.weight", (size_t)EMB * 40960), (size_t)EMB * 40960);
+        h->seg_b = ld.push(ld.get("seg_1.bias", EMB), EMB);
     }
-    h->consts = host.size();
-    host.resize(host.size() + al(64 + 2048), 0.f);
-    host[h->consts] = 1.0f / 1024.0f;      // activations <= 20 (ReLU20): x * 2^10 < 2^15
-    host[h->consts + 1] = 1.0f / 512.0f;   // sums of two such (Res2Net chain inputs, AFF outputs) <= 40: x * 2^9 < 2^15
-    if (!ok) { delete h; return tdx::fail(TDX_E_BLOB, "tdx_eres2net_create: tensor missing or wrong size: " + missing); }
-    tdx::DeviceGuard guard(device);
-    hipError_t e = guard.err;
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
+    h->consts = ld.room(64 + 2048);
+    ld.host[h->consts] = 1.0f / 1024.0f;      // activations <= 20 (ReLU20): x * 2^10 < 2^15
+    ld.host[h->consts + 1] = 1.0f / 512.0f;   // sums of two such (Res2Net chain inputs, AFF outputs) <= 40: x * 2^9 < 2^15
     h->device = device;
-    e = hipMalloc(&h->dev, host.size() * sizeof(float));
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-    e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(h->dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
+    TRY(ld.finish("tdx_eres2net_create", false, device, h->dev));
     {   // x3 planes of the compute-heavy convolutions (stages 3-4: K >= 96 per tap; layer3_ds), split once
         std::vector<ConvW*> jobs;
         size_t bi = 0;
@@ -770,28 +744,16 @@ int tdx_eres2net_create(const void* blob, size_t blob_bytes, int device, tdx_ere
             }
         jobs.push_back(&h->ds);
         jobs.push_back(&h->fuse34.c0); jobs.push_back(&h->fuse34.c3);
-        size_t bytes = 0;
-        for (ConvW* c : jobs) bytes += (size_t)c->Npad * c->taps * c->cinp * 4 + al(c->Npad) * 4;
-        e = hipMalloc(&h->dev_planes, bytes);
-        if (e != hipSuccess) { hipFree(h->dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-        unsigned char* q = h->dev_planes;
-        for (ConvW* c : jobs) {
-            const int K = c->taps * c->cinp;
-            float* sc = (float*)(q + (size_t)c->Npad * K * 4);
-            e = tdx::launch_h3_split_rows_long(h->dev + c->w, K, q, sc, c->Npad, K, nullptr);
-            if (e != hipSuccess) { hipFree(h->dev_planes); hipFree(h->dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-            c->hp = q; c->hs = sc;
-            q += (size_t)c->Npad * K * 4 + al(c->Npad) * 4;
-        }
-        e = hipDeviceSynchronize();
-        if (e != hipSuccess) { hipFree(h->dev_planes); hipFree(h->dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
+        std::vector<tdx::PlaneJob> planes;
+        for (ConvW* c : jobs) planes.push_back({h->dev + c->w, c->Npad, c->taps * c->cinp, &c->hp, &c->hs, tdx::launch_h3_split_rows_long});
+        TRY(tdx::split_weight_planes(planes, device, h->dev_planes));
     }
-    *out = h;
+    *out = h.release();
     return TDX_OK;
 }
 
 int tdx_eres2net_destroy(tdx_eres2net* h) {
-    if (h) { if (h->dev_planes) hipFree(h->dev_planes); if (h->dev) hipFree(h->dev); delete h; }
+    delete h;
     return TDX_OK;
 }
 

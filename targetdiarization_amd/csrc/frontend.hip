@@ -26,13 +26,7 @@ namespace {
 constexpr int NF = 512, NBIN_PAD = 320, NMEL = 80, FLEN = 400, FSHIFT = 160;
 constexpr float LOG_EPS = 1.1920928955078125e-07f;
 
-inline size_t al(size_t n) { return (n + 63) / 64 * 64; }
 
-#define LAUNCH_CHECK()                                    \
-    do {                                                  \
-        hipError_t e__ = hipGetLastError();               \
-        if (e__ != hipSuccess) return tdx::fail_hip(e__, __FILE__, __LINE__); \
-    } while (0)
 
 // one block (256 threads) per frame: scale, DC removal, pre-emphasis 0.97 (replicate-left),
 // window, zero-pad 400 -> 512     [kaldi.fbank _get_window]
@@ -149,19 +143,20 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
 struct tdx_fbank {
     int device = 0;
     int mode; float scale;
-    float* dev; const float *Wdft, *mel, *win;
+    tdx::DevBuf dev; const float *Wdft, *mel, *win;
 };
 struct tdx_stft {
     int device = 0;
     int nfft, hop, dimf, T, chunk;
-    float* dev; const float *Wf, *Wi, *win, *env;
+    tdx::DevBuf dev; const float *Wf, *Wi, *win, *env;
 };
 
 extern "C" {
 
 int tdx_fbank_create(int mode, int device, tdx_fbank** out) {
     if (!out || (mode != 0 && mode != 1)) return tdx::fail(TDX_E_INVALID, "tdx_fbank_create: mode must be 0 (SV) or 1 (ASR)");
-    std::vector<float> host;
+    tdx::Loader ld;       // (no blob: the tables are computed here, then staged and uploaded like weights)
+    std::vector<float>& host = ld.host;
     const size_t oW = 0, nW = (size_t)2 * NBIN_PAD * NF;
     host.resize(al(nW), 0.f);
     std::vector<double> cs(NF), sn(NF);
@@ -194,23 +189,17 @@ int tdx_fbank_create(int mode, int device, tdx_fbank** out) {
         if (mode == 0) host[oWin + i] = (float)pow(0.5 - 0.5 * cos(2.0 * M_PI * i / (FLEN - 1)), 0.85);   // povey
         else host[oWin + i] = (float)(0.54 - 0.46 * cos(2.0 * M_PI * i / (FLEN - 1)));                     // hamming
     }
-    tdx::DeviceGuard guard(device);
-    hipError_t e = guard.err;
-    if (e != hipSuccess) return tdx::fail_hip(e, __FILE__, __LINE__);
-    float* dev = nullptr;
-    e = hipMalloc(&dev, host.size() * sizeof(float));
-    if (e != hipSuccess) return tdx::fail_hip(e, __FILE__, __LINE__);
-    e = hipMemcpy(dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(dev); return tdx::fail_hip(e, __FILE__, __LINE__); }
-    tdx_fbank* h = new tdx_fbank();
+    std::unique_ptr<tdx_fbank> h(new tdx_fbank());
+    TRY(ld.finish("tdx_fbank_create", false, device, h->dev));
+    const float* dev = h->dev;
     h->device = device;
-    h->mode = mode; h->scale = mode == 1 ? 32768.0f : 1.0f; h->dev = dev; h->Wdft = dev + oW; h->mel = dev + oM; h->win = dev + oWin;
-    *out = h;
+    h->mode = mode; h->scale = mode == 1 ? 32768.0f : 1.0f; h->Wdft = dev + oW; h->mel = dev + oM; h->win = dev + oWin;
+    *out = h.release();
     return TDX_OK;
 }
 
 int tdx_fbank_destroy(tdx_fbank* h) {
-    if (h) { if (h->dev) hipFree(h->dev); delete h; }
+    delete h;
     return TDX_OK;
 }
 
@@ -267,7 +256,8 @@ int tdx_stft_create(int n_fft, int hop, int dim_f, int dim_t, int device, tdx_st
     const int N = n_fft, T = dim_t, chunk = hop * (dim_t - 1);
     std::vector<double> cs(N), sn(N);
     for (int i = 0; i < N; ++i) { cs[i] = cos(2.0 * M_PI * i / N); sn[i] = sin(2.0 * M_PI * i / N); }
-    std::vector<float> host;
+    tdx::Loader ld;       // (no blob: the tables are computed here, then staged and uploaded like weights)
+    std::vector<float>& host = ld.host;
     // forward: rows m = ri*dim_f + f over k=n (time):  re: cos, im: -sin
     const size_t oWf = 0;
     host.resize(al((size_t)2 * dim_f * N), 0.f);
@@ -298,24 +288,18 @@ int tdx_stft_create(int n_fft, int hop, int dim_f, int dim_t, int device, tdx_st
     host.resize(oEnv + al(L), 0.f);
     for (int t = 0; t < T; ++t)
         for (int n = 0; n < N; ++n) host[oEnv + (size_t)t * hop + n] += (float)((double)host[oWin + n] * (double)host[oWin + n]);
-    tdx::DeviceGuard guard(device);
-    hipError_t e = guard.err;
-    if (e != hipSuccess) return tdx::fail_hip(e, __FILE__, __LINE__);
-    float* dev = nullptr;
-    e = hipMalloc(&dev, host.size() * sizeof(float));
-    if (e != hipSuccess) return tdx::fail_hip(e, __FILE__, __LINE__);
-    e = hipMemcpy(dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(dev); return tdx::fail_hip(e, __FILE__, __LINE__); }
-    tdx_stft* h = new tdx_stft();
+    std::unique_ptr<tdx_stft> h(new tdx_stft());
+    TRY(ld.finish("tdx_stft_create", false, device, h->dev));
+    const float* dev = h->dev;
     h->device = device;
-    h->nfft = N; h->hop = hop; h->dimf = dim_f; h->T = T; h->chunk = chunk; h->dev = dev;
+    h->nfft = N; h->hop = hop; h->dimf = dim_f; h->T = T; h->chunk = chunk;
     h->Wf = dev + oWf; h->Wi = dev + oWi; h->win = dev + oWin; h->env = dev + oEnv;
-    *out = h;
+    *out = h.release();
     return TDX_OK;
 }
 
 int tdx_stft_destroy(tdx_stft* h) {
-    if (h) { if (h->dev) hipFree(h->dev); delete h; }
+    delete h;
     return TDX_OK;
 }
 

@@ -20,7 +20,7 @@
 
 #include <algorithm>
 #include <cmath>
-#include <initializer_list>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -38,15 +38,6 @@ constexpr int NCLS = 248, NCLSP = 256;
 constexpr int MAX_ROWS = 1 << 22;
 constexpr int LFR_ROWS = 16;          // rows per block of lfr_cmvn_kernel
 constexpr int MEM_ROWS = 8;           // consecutive rows per thread of memory_kernel
-
-inline size_t al(size_t n) { return (n + 63) / 64 * 64; }
-
-#define LAUNCH_CHECK()                                    \
-    do {                                                  \
-        hipError_t e__ = hipGetLastError();               \
-        if (e__ != hipSuccess) return tdx::fail_hip(e__, __FILE__, __LINE__); \
-    } while (0)
-#define TRY(x) do { int rc__ = (x); if (rc__ != TDX_OK) return rc__; } while (0)
 
 // (a) LFR 5/1 + CMVN.  Row t of clip [s, e): columns j*80 + q = (feat[clamp(t-2+j, s, e-1)][q] + shift) * scale, j = 0..4;
 // columns 400..415 are the GEMM's K padding (zero).  The first LFR_ROWS threads find their row's clip by binary search
@@ -163,7 +154,7 @@ int dense(const float* A, const float* dev, const Lin& l, int M, float* out, int
 
 struct tdx_fsmnvad {
     int device = 0;
-    float* dev = nullptr;
+    tdx::DevBuf dev;
     size_t shift, scale;
     Lin in, lin[NLAYER], aff[NLAYER], out;
     size_t mem[NLAYER];
@@ -173,35 +164,24 @@ extern "C" {
 
 int tdx_fsmnvad_create(const void* blob, size_t blob_bytes, int device, tdx_fsmnvad** out) {
     if (!blob || !out) return tdx::fail(TDX_E_INVALID, "tdx_fsmnvad_create: null argument");
-    tdx::Blob bl;
-    if (!bl.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_fsmnvad_create: malformed TDXW blob");
-    std::vector<float> host;
-    bool ok = true; std::string missing;
-    // name AND shape: a transposed [400,140] in place of [140,400] has the right numel and must not load
-    auto get = [&](const std::string& name, std::initializer_list<uint32_t> dims) -> const float* {
-        const tdx::BlobTensor* t = bl.find(name);
-        bool same = t && t->ndim == (int)dims.size();
-        if (same) { int d = 0; for (uint32_t v : dims) same = same && t->dims[d++] == v; }
-        if (!same) { ok = false; if (missing.empty()) missing = name; return nullptr; }
-        return t->data;
-    };
-    auto room = [&](size_t n) -> size_t { const size_t o = host.size(); host.resize(o + al(n), 0.f); return o; };
+    tdx::Loader ld;
+    if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_fsmnvad_create: malformed TDXW blob");
     // W [N][K] (+ bias [N]) -> zero-padded [Np][Kp] + bias [Np]
     auto put = [&](const std::vector<double>& W, const std::vector<double>* b, int N, int K, int Np, int Kp) -> Lin {
         Lin l; l.Np = Np; l.Kp = Kp; l.bias = b != nullptr;
-        l.w = room((size_t)Np * Kp); l.b = room(Np);
+        l.w = ld.room((size_t)Np * Kp); l.b = ld.room(Np);
         for (int n = 0; n < N; ++n) {
-            for (int k = 0; k < K; ++k) host[l.w + (size_t)n * Kp + k] = (float)W[(size_t)n * K + k];
-            if (b) host[l.b + n] = (float)(*b)[n];
+            for (int k = 0; k < K; ++k) ld.host[l.w + (size_t)n * Kp + k] = (float)W[(size_t)n * K + k];
+            if (b) ld.host[l.b + n] = (float)(*b)[n];
         }
         return l;
     };
     // `b` . `a` : two linears with no activation between them, as one matrix; the product is taken in fp64
     auto folded = [&](const std::string& a, const std::string& b, int Nin, int Nmid, int Nout, int Np, int Kp) -> Lin {
-        const float *Wa = get(a + "weight", {(uint32_t)Nmid, (uint32_t)Nin}), *ba = get(a + "bias", {(uint32_t)Nmid});
-        const float *Wb = get(b + "weight", {(uint32_t)Nout, (uint32_t)Nmid}), *bb = get(b + "bias", {(uint32_t)Nout});
+        const float *Wa = ld.get(a + "weight", {(uint32_t)Nmid, (uint32_t)Nin}), *ba = ld.get(a + "bias", {(uint32_t)Nmid});
+        const float *Wb = ld.get(b + "weight", {(uint32_t)Nout, (uint32_t)Nmid}), *bb = ld.get(b + "bias", {(uint32_t)Nout});
         std::vector<double> W((size_t)Nout * Nin, 0.0), bias(Nout, 0.0);
-        if (ok) for (int n = 0; n < Nout; ++n) {
+        if (ld.ok()) for (int n = 0; n < Nout; ++n) {
             double acc = bb[n];
             for (int j = 0; j < Nmid; ++j) {
                 const double wb = Wb[(size_t)n * Nmid + j];
@@ -215,48 +195,34 @@ int tdx_fsmnvad_create(const void* blob, size_t blob_bytes, int device, tdx_fsmn
         return put(W, &bias, Nout, Nin, Np, Kp);
     };
     auto plain = [&](const std::string& p, bool with_bias, int N, int K, int Np, int Kp) -> Lin {
-        const float* Wp = get(p + "weight", {(uint32_t)N, (uint32_t)K});
-        const float* bp = with_bias ? get(p + "bias", {(uint32_t)N}) : nullptr;
+        const float* Wp = ld.get(p + "weight", {(uint32_t)N, (uint32_t)K});
+        const float* bp = with_bias ? ld.get(p + "bias", {(uint32_t)N}) : nullptr;
         std::vector<double> W((size_t)N * K, 0.0), bias(N, 0.0);
-        if (ok) {
+        if (ld.ok()) {
             for (size_t i = 0; i < W.size(); ++i) W[i] = Wp[i];
             if (with_bias) for (int n = 0; n < N; ++n) bias[n] = bp[n];
         }
         return put(W, with_bias ? &bias : nullptr, N, K, Np, Kp);
     };
-    tdx_fsmnvad* h = new tdx_fsmnvad();
-    {
-        const float *sh = get("cmvn.shift", {(uint32_t)DIN}), *sc = get("cmvn.scale", {(uint32_t)DIN});
-        h->shift = room(DINP); h->scale = room(DINP);
-        if (ok) { memcpy(host.data() + h->shift, sh, DIN * sizeof(float)); memcpy(host.data() + h->scale, sc, DIN * sizeof(float)); }
-    }
+    std::unique_ptr<tdx_fsmnvad> h(new tdx_fsmnvad());
+    h->shift = ld.push(ld.get("cmvn.shift", {(uint32_t)DIN}), DIN, DINP);
+    h->scale = ld.push(ld.get("cmvn.scale", {(uint32_t)DIN}), DIN, DINP);
     h->in = folded("encoder.in_linear1.linear.", "encoder.in_linear2.linear.", DIN, H1, DL, DLP, DINP);
     for (int i = 0; i < NLAYER; ++i) {
         const std::string p = "encoder.fsmn." + std::to_string(i) + ".";
         h->lin[i] = plain(p + "linear.linear.", false, DP, DL, DP, DLP);
-        const float* w = get(p + "fsmn_block.conv_left.weight", {(uint32_t)DP, 1u, (uint32_t)TAPS, 1u});      // [128,1,20,1] -> [20][128]
-        h->mem[i] = room((size_t)TAPS * DP);
-        if (w) for (int c = 0; c < DP; ++c) for (int j = 0; j < TAPS; ++j) host[h->mem[i] + (size_t)j * DP + c] = w[(size_t)c * TAPS + j];
+        h->mem[i] = ld.push_tapmajor(ld.get(p + "fsmn_block.conv_left.weight", {(uint32_t)DP, 1u, (uint32_t)TAPS, 1u}), DP, TAPS);      // [128,1,20,1] -> [20][128]
         h->aff[i] = plain(p + "affine.linear.", true, DL, DP, DLP, DP);
     }
     h->out = folded("encoder.out_linear1.linear.", "encoder.out_linear2.linear.", DL, H1, NCLS, NCLSP, DLP);
-    if (!ok) { delete h; return tdx::fail(TDX_E_BLOB, "tdx_fsmnvad_create: tensor missing or wrong shape: " + missing); }
-    const std::string extra = bl.first_unused();
-    if (!extra.empty()) { delete h; return tdx::fail(TDX_E_BLOB, "tdx_fsmnvad_create: unexpected tensor: " + extra); }
-    tdx::DeviceGuard guard(device);
-    hipError_t e = guard.err;
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
     h->device = device;
-    e = hipMalloc(&h->dev, host.size() * sizeof(float));
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-    e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(h->dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-    *out = h;
+    TRY(ld.finish("tdx_fsmnvad_create", true, device, h->dev));
+    *out = h.release();
     return TDX_OK;
 }
 
 int tdx_fsmnvad_destroy(tdx_fsmnvad* h) {
-    if (h) { if (h->dev) hipFree(h->dev); delete h; }
+    delete h;
     return TDX_OK;
 }
 

@@ -28,15 +28,7 @@ using namespace tdx;
 
 namespace {
 
-inline size_t al(size_t n) { return (n + 63) / 64 * 64; }
-inline int up(int n, int m) { return (n + m - 1) / m * m; }
 
-#define LAUNCH_CHECK()                                    \
-    do {                                                  \
-        hipError_t e__ = hipGetLastError();               \
-        if (e__ != hipSuccess) return tdx::fail_hip(e__, __FILE__, __LINE__); \
-    } while (0)
-#define TRY(x) do { int rc__ = (x); if (rc__ != TDX_OK) return rc__; } while (0)
 
 struct GW { size_t w = 0, b = 0; int N = 0, Npad = 0, K = 0; };            // folded GEMM weights [Npad][K] + bias [Npad]
 struct TdfW { size_t w1 = 0, w2 = 0, b1 = 0, b2 = 0, s1 = 0, t1 = 0, s2 = 0, t2 = 0; int f = 0, fb = 0, fbp = 0; };
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(256) void mdx_s2d_kernel(const float* __restrict__ 
 struct tdx_mdx {
     int device = 0;
     int L = 0, l = 0, g = 0, k = 0, bn = 0, dim_f = 0, dim_t = 0, n = 0;
-    float* dev = nullptr;
+    tdx::DevBuf dev;
     size_t first_w = 0, first_b = 0, fin_w = 0, fin_b = 0;
     std::vector<BlockW> enc, dec; BlockW bott;
     std::vector<GW> ds, us;
@@ -211,138 +203,115 @@ int tdx_mdx_create(const tdx_mdx_config* cfg, const void* blob, size_t blob_byte
     if (L < 1 || (L & 1) == 0 || n > 7 || l < 1 || l > 8 || g < 32 || g % 32 || k != 3 || bn < 1 || dim_f < 32 || dim_t < 1 ||
         (dim_f >> n) << n != dim_f || (dim_t >> n) << n != dim_t || (dim_f >> n) % 32 || (dim_f >> n) % bn)
         return tdx::fail(TDX_E_INVALID, "tdx_mdx_create: unsupported config (need odd num_blocks <= 15, k = 3, g % 32 == 0, dim_f / 2^n a multiple of 32 and of bn, dim_t / 2^n integral)");
-    tdx::Blob bl;
-    if (!bl.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_mdx_create: malformed TDXW blob");
-    std::vector<float> host;
-    bool ok = true; std::string missing;
-    auto get = [&](const std::string& name, size_t nn) -> const float* {
-        const tdx::BlobTensor* t = bl.find(name);
-        if (!t || t->numel != nn) { ok = false; if (missing.empty()) missing = name; return nullptr; }
-        return t->data;
-    };
-    auto opt = [&](const std::string& name, size_t nn) -> const float* {
-        const tdx::BlobTensor* t = bl.find(name);
-        if (t && t->numel != nn) { ok = false; if (missing.empty()) missing = name; return nullptr; }
-        return t ? t->data : nullptr;
-    };
+    tdx::Loader ld;
+    if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_mdx_create: malformed TDXW blob");
     struct BN { std::vector<double> s, t; };
     auto bnfold = [&](const std::string& p, int c) -> BN {       // y = x * s + t
         BN r; r.s.assign(c, 1.0); r.t.assign(c, 0.0);
-        const float *w = get(p + "weight", c), *b = get(p + "bias", c), *mu = get(p + "running_mean", c), *var = get(p + "running_var", c);
-        if (ok) for (int i = 0; i < c; ++i) { r.s[i] = (double)w[i] / std::sqrt((double)var[i] + 1e-5); r.t[i] = (double)b[i] - (double)mu[i] * r.s[i]; }
+        const float *w = ld.get(p + "weight", c), *b = ld.get(p + "bias", c), *mu = ld.get(p + "running_mean", c), *var = ld.get(p + "running_var", c);
+        if (ld.ok()) for (int i = 0; i < c; ++i) { r.s[i] = (double)w[i] / std::sqrt((double)var[i] + 1e-5); r.t[i] = (double)b[i] - (double)mu[i] * r.s[i]; }
         return r;
     };
     // Conv2d [N][cin][kh][kw] + bias + BN -> [Npad][taps][cin] (tap = kh * kw_count + kw), bias[Npad]
     auto fold_conv = [&](const std::string& p, const std::string& bnp, int N, int cin, int kh, int kw) -> GW {
         GW w; w.N = N; w.Npad = up(N, 128); w.K = kh * kw * cin;
-        const float* W = get(p + "weight", (size_t)N * cin * kh * kw);
-        const float* cb = get(p + "bias", N);
+        const float* W = ld.get(p + "weight", (size_t)N * cin * kh * kw);
+        const float* cb = ld.get(p + "bias", N);
         const BN b = bnfold(bnp, N);
-        w.w = host.size(); host.resize(host.size() + al((size_t)w.Npad * w.K), 0.f);
-        w.b = host.size(); host.resize(host.size() + al(w.Npad), 0.f);
-        if (!ok) return w;
+        w.w = ld.room((size_t)w.Npad * w.K);
+        w.b = ld.room(w.Npad);
+        if (!ld.ok()) return w;
         for (int nn = 0; nn < N; ++nn) {
-            host[w.b + nn] = (float)((double)cb[nn] * b.s[nn] + b.t[nn]);
+            ld.host[w.b + nn] = (float)((double)cb[nn] * b.s[nn] + b.t[nn]);
             for (int c = 0; c < cin; ++c)
                 for (int t = 0; t < kh * kw; ++t)
-                    host[w.w + ((size_t)nn * kh * kw + t) * cin + c] = (float)((double)W[((size_t)nn * cin + c) * kh * kw + t] * b.s[nn]);
+                    ld.host[w.w + ((size_t)nn * kh * kw + t) * cin + c] = (float)((double)W[((size_t)nn * cin + c) * kh * kw + t] * b.s[nn]);
         }
         return w;
     };
     auto fold_block = [&](const std::string& p, int c, int f) -> BlockW {
         BlockW bw; bw.c = c; bw.f = f;
-        for (int j = 0; j < l && ok; ++j)
+        for (int j = 0; j < l && ld.ok(); ++j)
             bw.conv.push_back(fold_conv(p + "tfc.H." + std::to_string(j) + ".0.", p + "tfc.H." + std::to_string(j) + ".1.", c, c, 3, 3));
         TdfW& td = bw.tdf; td.f = f; td.fb = f / bn; td.fbp = up(td.fb, 32);
-        const float* W1 = get(p + "tdf.0.weight", (size_t)td.fb * f);
-        const float* B1 = opt(p + "tdf.0.bias", td.fb);
-        const float* W2 = get(p + "tdf.3.weight", (size_t)f * td.fb);
-        const float* B2 = opt(p + "tdf.3.bias", f);
+        const float* W1 = ld.get(p + "tdf.0.weight", (size_t)td.fb * f);
+        const float* B1 = ld.get_optional(p + "tdf.0.bias", td.fb);
+        const float* W2 = ld.get(p + "tdf.3.weight", (size_t)f * td.fb);
+        const float* B2 = ld.get_optional(p + "tdf.3.bias", f);
         const BN n1 = bnfold(p + "tdf.1.", c), n2 = bnfold(p + "tdf.4.", c);
-        td.w1 = host.size(); host.resize(host.size() + al((size_t)up(td.fb, 128) * f), 0.f);          // rows read in 128-row tiles
-        td.w2 = host.size(); host.resize(host.size() + al((size_t)up(f, 128) * td.fbp), 0.f);
-        td.b1 = host.size(); host.resize(host.size() + al(up(td.fb, 128)), 0.f);
-        td.b2 = host.size(); host.resize(host.size() + al(up(f, 128)), 0.f);
+        td.w1 = ld.room((size_t)up(td.fb, 128) * f);          // rows read in 128-row tiles
+        td.w2 = ld.room((size_t)up(f, 128) * td.fbp);
+        td.b1 = ld.room(up(td.fb, 128));
+        td.b2 = ld.room(up(f, 128));
         const int cp = up(c, 128);
-        td.s1 = host.size(); host.resize(host.size() + al(cp), 0.f); td.t1 = host.size(); host.resize(host.size() + al(cp), 0.f);
-        td.s2 = host.size(); host.resize(host.size() + al(cp), 0.f); td.t2 = host.size(); host.resize(host.size() + al(cp), 0.f);
-        if (!ok) return bw;
-        memcpy(host.data() + td.w1, W1, (size_t)td.fb * f * sizeof(float));
-        for (int m = 0; m < f; ++m) memcpy(host.data() + td.w2 + (size_t)m * td.fbp, W2 + (size_t)m * td.fb, td.fb * sizeof(float));
-        if (B1) memcpy(host.data() + td.b1, B1, td.fb * sizeof(float));
-        if (B2) memcpy(host.data() + td.b2, B2, f * sizeof(float));
+        td.s1 = ld.room(cp); td.t1 = ld.room(cp);
+        td.s2 = ld.room(cp); td.t2 = ld.room(cp);
+        if (!ld.ok()) return bw;
+        memcpy(ld.host.data() + td.w1, W1, (size_t)td.fb * f * sizeof(float));
+        for (int m = 0; m < f; ++m) memcpy(ld.host.data() + td.w2 + (size_t)m * td.fbp, W2 + (size_t)m * td.fb, td.fb * sizeof(float));
+        if (B1) memcpy(ld.host.data() + td.b1, B1, td.fb * sizeof(float));
+        if (B2) memcpy(ld.host.data() + td.b2, B2, f * sizeof(float));
         for (int i = 0; i < c; ++i) {
-            host[td.s1 + i] = (float)n1.s[i]; host[td.t1 + i] = (float)n1.t[i];
-            host[td.s2 + i] = (float)n2.s[i]; host[td.t2 + i] = (float)n2.t[i];
+            ld.host[td.s1 + i] = (float)n1.s[i]; ld.host[td.t1 + i] = (float)n1.t[i];
+            ld.host[td.s2 + i] = (float)n2.s[i]; ld.host[td.t2 + i] = (float)n2.t[i];
         }
         return bw;
     };
-    tdx_mdx* h = new tdx_mdx();
+    std::unique_ptr<tdx_mdx> h(new tdx_mdx());
     h->L = L; h->l = l; h->g = g; h->k = k; h->bn = bn; h->dim_f = dim_f; h->dim_t = dim_t; h->n = n;
     {   // first_conv [g][4][1][1] + BN
-        const float* W = get("first_conv.0.weight", (size_t)g * 4);
-        const float* cb = get("first_conv.0.bias", g);
+        const float* W = ld.get("first_conv.0.weight", (size_t)g * 4);
+        const float* cb = ld.get("first_conv.0.bias", g);
         const BN b = bnfold("first_conv.1.", g);
-        h->first_w = host.size(); host.resize(host.size() + al((size_t)g * 4), 0.f);
-        h->first_b = host.size(); host.resize(host.size() + al(g), 0.f);
-        if (ok) for (int nn = 0; nn < g; ++nn) {
-            host[h->first_b + nn] = (float)((double)cb[nn] * b.s[nn] + b.t[nn]);
-            for (int c = 0; c < 4; ++c) host[h->first_w + nn * 4 + c] = (float)((double)W[nn * 4 + c] * b.s[nn]);
+        h->first_w = ld.room((size_t)g * 4);
+        h->first_b = ld.room(g);
+        if (ld.ok()) for (int nn = 0; nn < g; ++nn) {
+            ld.host[h->first_b + nn] = (float)((double)cb[nn] * b.s[nn] + b.t[nn]);
+            for (int c = 0; c < 4; ++c) ld.host[h->first_w + nn * 4 + c] = (float)((double)W[nn * 4 + c] * b.s[nn]);
         }
     }
     int f = dim_f, c = g;
-    for (int i = 0; i < n && ok; ++i) {
+    for (int i = 0; i < n && ld.ok(); ++i) {
         h->enc.push_back(fold_block("encoding_blocks." + std::to_string(i) + ".", c, f));
         h->ds.push_back(fold_conv("ds." + std::to_string(i) + ".0.", "ds." + std::to_string(i) + ".1.", c + g, c, 2, 2));
         f /= 2; c += g;
     }
-    if (ok) h->bott = fold_block("bottleneck_block.", c, f);
-    for (int i = 0; i < n && ok; ++i) {
+    if (ld.ok()) h->bott = fold_block("bottleneck_block.", c, f);
+    for (int i = 0; i < n && ld.ok(); ++i) {
         // ConvTranspose2d weight [cin = c][cout = c - g][2][2] + bias + BN -> rows r = tap * cg + n of [4 cg (pad 128)][c], bias repeated per tap
         const std::string p = "us." + std::to_string(i) + ".";
         const int cg = c - g;
         GW w; w.N = 4 * cg; w.Npad = up(4 * cg, 128); w.K = c;
-        const float* W = get(p + "0.weight", (size_t)c * cg * 4);
-        const float* cb = get(p + "0.bias", cg);
+        const float* W = ld.get(p + "0.weight", (size_t)c * cg * 4);
+        const float* cb = ld.get(p + "0.bias", cg);
         const BN b = bnfold(p + "1.", cg);
-        w.w = host.size(); host.resize(host.size() + al((size_t)w.Npad * c), 0.f);
-        w.b = host.size(); host.resize(host.size() + al(w.Npad), 0.f);
-        if (ok) for (int tap = 0; tap < 4; ++tap)
+        w.w = ld.room((size_t)w.Npad * c);
+        w.b = ld.room(w.Npad);
+        if (ld.ok()) for (int tap = 0; tap < 4; ++tap)
             for (int nn = 0; nn < cg; ++nn) {
-                host[w.b + tap * cg + nn] = (float)((double)cb[nn] * b.s[nn] + b.t[nn]);
-                for (int ci = 0; ci < c; ++ci) host[w.w + ((size_t)tap * cg + nn) * c + ci] = (float)((double)W[((size_t)ci * cg + nn) * 4 + tap] * b.s[nn]);
+                ld.host[w.b + tap * cg + nn] = (float)((double)cb[nn] * b.s[nn] + b.t[nn]);
+                for (int ci = 0; ci < c; ++ci) ld.host[w.w + ((size_t)tap * cg + nn) * c + ci] = (float)((double)W[((size_t)ci * cg + nn) * 4 + tap] * b.s[nn]);
             }
         h->us.push_back(w);
         f *= 2; c -= g;
-        if (ok) h->dec.push_back(fold_block("decoding_blocks." + std::to_string(i) + ".", c, f));
+        if (ld.ok()) h->dec.push_back(fold_block("decoding_blocks." + std::to_string(i) + ".", c, f));
     }
     {
-        const float* W = get("final_conv.0.weight", (size_t)4 * g);
-        const float* cb = get("final_conv.0.bias", 4);
-        h->fin_w = host.size(); host.resize(host.size() + al((size_t)4 * g), 0.f);
-        h->fin_b = host.size(); host.resize(host.size() + al(4), 0.f);
-        if (ok) { memcpy(host.data() + h->fin_w, W, (size_t)4 * g * sizeof(float)); memcpy(host.data() + h->fin_b, cb, 4 * sizeof(float)); }
+        const float* W = ld.get("final_conv.0.weight", (size_t)4 * g);
+        const float* cb = ld.get("final_conv.0.bias", 4);
+        h->fin_w = ld.room((size_t)4 * g);
+        h->fin_b = ld.room(4);
+        if (ld.ok()) { memcpy(ld.host.data() + h->fin_w, W, (size_t)4 * g * sizeof(float)); memcpy(ld.host.data() + h->fin_b, cb, 4 * sizeof(float)); }
     }
-    if (!ok) { delete h; return tdx::fail(TDX_E_BLOB, "tdx_mdx_create: tensor missing or wrong size: " + missing); }
-    {
-        const std::string extra = bl.first_unused();
-        if (!extra.empty()) { delete h; return tdx::fail(TDX_E_BLOB, "tdx_mdx_create: unexpected tensor in the blob: " + extra); }
-    }
-    host.resize(host.size() + 4096, 0.f);       // (weight tiles are read in 128-row pieces)
-    tdx::DeviceGuard guard(device);
-    hipError_t e = guard.err;
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
+    ld.room(4096);       // (weight tiles are read in 128-row pieces)
     h->device = device;
-    e = hipMalloc(&h->dev, host.size() * sizeof(float));
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-    e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(h->dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-    *out = h;
+    TRY(ld.finish("tdx_mdx_create", true, device, h->dev));
+    *out = h.release();
     return TDX_OK;
 }
 
 int tdx_mdx_destroy(tdx_mdx* h) {
-    if (h) { if (h->dev) hipFree(h->dev); delete h; }
+    delete h;
     return TDX_OK;
 }
 

@@ -23,6 +23,7 @@
 #include "gemm_h3a.hpp"
 #include "mf2_kernels.hpp"
 #include "tdx_common.hpp"
+#include "weight_planes.hpp"
 
 using namespace tdx;
 
@@ -362,10 +363,9 @@ constexpr long FORK_ROWS = 1L << 40;    // token rows up to which a FLASH layer 
 struct tdx_mf2 {
     int device;
     int L;
-    float* dev_weights;
-    size_t n_weights;
-    unsigned char* dev_planes;      // split-f16 planes + scales of every nn.Linear weight
-    float* dev_static;              // [L][2] inverse static scales
+    tdx::DevBuf dev_weights;
+    tdx::DevBuf dev_planes;         // split-f16 planes + scales of every nn.Linear weight
+    tdx::DevBuf dev_static;         // [L][2] inverse static scales
     H3W hWenc, hWout, hWtg, hWdec1;
     std::vector<LayerW> layers;
     const float *encT, *gn1g, *gn1b, *Wenc, *pe_scale, *inv_freq, *rot_freqs, *lnfg, *lnfb, *gn2g, *gn2b, *prelu, *Wout, *bout,
@@ -420,7 +420,6 @@ struct Plan {
         part, tap0, tap1, mask, hdr, total;
 };
 
-inline size_t al(size_t n) { return (n + 63) / 64 * 64; }
 
 bool make_plan(const tdx_mf2* h, int B, int T, Plan& P) {
     if (B < 1 || T < 16) return false;
@@ -477,11 +476,6 @@ bool make_plan(const tdx_mf2* h, int B, int T, Plan& P) {
     return true;
 }
 
-#define LAUNCH_CHECK()                                    \
-    do {                                                  \
-        hipError_t e__ = hipGetLastError();               \
-        if (e__ != hipSuccess) return tdx::fail_hip(e__, __FILE__, __LINE__); \
-    } while (0)
 
 inline dim3 rows4(long M) { return dim3((unsigned)((M + 3) / 4)); }
 
@@ -710,7 +704,6 @@ int linear_gemm_f32(const float* A, long lda, const float* W, int M, int N, int 
     return TDX_OK;
 }
 
-#define TRY(x) do { int rc__ = (x); if (rc__ != TDX_OK) return rc__; } while (0)
 
 // A/B switch: the depthwise convolution of v|u fused into the to_hidden epilogue (gemm_h3.hpp H3Conv).  TDX_FUSE_CONV=0 restores the
 // separate conv17<4> pass (same arithmetic in the same order: bit-identical results).
@@ -735,62 +728,41 @@ int tdx_mf2_create(const tdx_mf2_config* cfg, const void* blob, size_t blob_byte
     if (!cfg || !blob || !out) return tdx::fail(TDX_E_INVALID, "tdx_mf2_create: null argument");
     if (cfg->channels != C || cfg->num_spks != 2 || cfg->kernel_size != 16 || cfg->group_size != 256 || cfg->num_blocks < 1)
         return tdx::fail(TDX_E_INVALID, "tdx_mf2_create: unsupported config (need channels=512, spks=2, kernel=16, group=256)");
-    tdx::Blob bl;
-    if (!bl.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_mf2_create: malformed TDXW blob");
+    tdx::Loader ld;       // strict both ways, like load_state_dict(strict=True) at base_model.py:63
+    if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_mf2_create: malformed TDXW blob");
     const int L = cfg->num_blocks;
-    std::vector<float> host;
-    host.reserve(60u * 1000 * 1000);
-    bool ok = true;
-    std::string missing;
-    auto get = [&](const std::string& name, size_t n) -> const float* {
-        const tdx::BlobTensor* t = bl.find(name);
-        if (!t || t->numel != n) { ok = false; if (missing.empty()) missing = name; return nullptr; }
-        return t->data;
-    };
-    auto push = [&](const float* p, size_t n) -> size_t {
-        size_t o = host.size();
-        host.resize(o + al(n), 0.f);
-        if (p) memcpy(host.data() + o, p, n * sizeof(float));
-        return o;
-    };
-    // conv weight [Cc,1,k] -> tap-major [k][Cc]
-    auto push_tapmajor = [&](const float* w, int Cc, int k) -> size_t {
-        size_t o = host.size();
-        host.resize(o + al((size_t)Cc * k), 0.f);
-        if (w) for (int c = 0; c < Cc; ++c) for (int t = 0; t < k; ++t) host[o + (size_t)t * Cc + c] = w[(size_t)c * k + t];
-        return o;
-    };
+    ld.host.reserve(60u * 1000 * 1000);
     std::vector<float> stat_host((size_t)L * 2, 1.f);
     std::vector<float> sv_host((size_t)L * 2, 1.f);
     struct Off { size_t Whq, ghq, bhq, cw_h, cw_qk, gamma, beta, Wo, go, bo, cw_o, W1, b1, a1, ln1g, ln1b, Wuv, buv, cw_uv, Wl, bl, Wp, w1T, w2T, ing, inb, pre, ln2g, ln2b, W2, b2; };
     std::vector<Off> offs(L);
     const std::string PFX = "mask_net.mdl.intra_mdl.mossformerM.";
-    for (int l = 0; l < L && ok; ++l) {
+    for (int l = 0; l < L && ld.ok(); ++l) {
         Off& o = offs[l];
         const std::string p = PFX + "layers." + std::to_string(l) + ".";
-        const float* Wh = get(p + "to_hidden.mdl.1.weight", (size_t)HID * C);
-        const float* Wq = get(p + "to_qk.mdl.1.weight", (size_t)QK * C);
-        const float* bh = get(p + "to_hidden.mdl.1.bias", HID);
-        const float* bq = get(p + "to_qk.mdl.1.bias", QK);
-        const float* gh = get(p + "to_hidden.mdl.0.g", 1);
-        const float* gq = get(p + "to_qk.mdl.0.g", 1);
-        const float* cwh = get(p + "to_hidden.mdl.3.sequential.1.conv.weight", (size_t)HID * 17);
-        const float* cwq = get(p + "to_qk.mdl.3.sequential.1.conv.weight", (size_t)QK * 17);
-        if (!ok) break;
-        o.Whq = push(Wh, (size_t)HID * C); push(Wq, (size_t)QK * C);       // contiguous [2176][512] (HID*C is 64-aligned)
-        host.resize(host.size() + (size_t)128 * C, 0.f);                     // zero rows up to 2304: the x6 GEMM reads W in 256-row tiles
-        o.ghq = host.size(); host.resize(host.size() + al(HQ));
-        for (int i = 0; i < HQ; ++i) host[o.ghq + i] = i < HID ? gh[0] : gq[0];
-        o.bhq = host.size(); host.resize(host.size() + al(HQ));
-        for (int i = 0; i < HQ; ++i) host[o.bhq + i] = i < HID ? bh[i] : bq[i - HID];
-        o.cw_h = push_tapmajor(cwh, HID, 17);
-        o.cw_qk = push_tapmajor(cwq, QK, 17);
-        (void)get(p + "rotary_pos_emb.freqs", 16);      // one RotaryEmbedding object shared by all layers (mossformer_block.py:453): layer 0's copy is used
-        const float* gam = get(p + "qk_offset_scale.gamma", 4 * QK);
-        const float* bet = get(p + "qk_offset_scale.beta", 4 * QK);
-        o.gamma = push(gam, 4 * QK);
-        o.beta = push(bet, 4 * QK);
-        if (!ok) break;
+        const float* Wh = ld.get(p + "to_hidden.mdl.1.weight", (size_t)HID * C);
+        const float* Wq = ld.get(p + "to_qk.mdl.1.weight", (size_t)QK * C);
+        const float* bh = ld.get(p + "to_hidden.mdl.1.bias", HID);
+        const float* bq = ld.get(p + "to_qk.mdl.1.bias", QK);
+        const float* gh = ld.get(p + "to_hidden.mdl.0.g", 1);
+        const float* gq = ld.get(p + "to_qk.mdl.0.g", 1);
+        const float* cwh = ld.get(p + "to_hidden.mdl.3.sequential.1.conv.weight", (size_t)HID * 17);
+        const float* cwq = ld.get(p + "to_qk.mdl.3.sequential.1.conv.weight", (size_t)QK * 17);
+        if (!ld.ok()) break;
+        o.Whq = ld.push(Wh, (size_t)HID * C); ld.push(Wq, (size_t)QK * C);       // contiguous [2176][512] (HID*C is 64-aligned)
+        ld.host.resize(ld.host.size() + (size_t)128 * C, 0.f);                     // zero rows up to 2304: the x6 GEMM reads W in 256-row tiles
+        o.ghq = ld.room(HQ);
+        for (int i = 0; i < HQ; ++i) ld.host[o.ghq + i] = i < HID ? gh[0] : gq[0];
+        o.bhq = ld.room(HQ);
+        for (int i = 0; i < HQ; ++i) ld.host[o.bhq + i] = i < HID ? bh[i] : bq[i - HID];
+        o.cw_h = ld.push_tapmajor(cwh, HID, 17);
+        o.cw_qk = ld.push_tapmajor(cwq, QK, 17);
+        (void)ld.get(p + "rotary_pos_emb.freqs", 16);      // one RotaryEmbedding object shared by all layers (mossformer_block.py:453): layer 0's copy is used
+        const float* gam = ld.get(p + "qk_offset_scale.gamma", 4 * QK);
+        const float* bet = ld.get(p + "qk_offset_scale.beta", 4 * QK);
+        o.gamma = ld.push(gam, 4 * QK);
+        o.beta = ld.push(bet, 4 * QK);
+        if (!ld.ok()) break;
         {
             // Static bounds for the K-major planes (gemm_h3.hpp).  After ScaleNorm the (shifted) row has norm
             // <= sqrt(512), so |x_hat . W_n| <= sqrt(512) |g| ||W_n|| (Cauchy-Schwarz) and |silu(p)| <= |p|;
@@ -822,109 +794,95 @@ int tdx_mf2_create(const tdx_mf2_config* cfg, const void* blob, size_t blob_byte
             sv_host[l * 2] = (float)pow2scale(vub); sv_host[l * 2 + 1] = (float)pow2scale(lkb);
             stat_host[l * 2] = 1.0f / sv_host[l * 2]; stat_host[l * 2 + 1] = 1.0f / sv_host[l * 2 + 1];
         }
-        o.Wo = push(get(p + "to_out.mdl.1.weight", (size_t)C * 1024), (size_t)C * 1024);
-        const float* go = get(p + "to_out.mdl.0.g", 1);
-        o.go = host.size(); host.resize(host.size() + al(C));
-        if (go) for (int i = 0; i < C; ++i) host[o.go + i] = go[0];
-        o.bo = push(get(p + "to_out.mdl.1.bias", C), C);
-        o.cw_o = push_tapmajor(get(p + "to_out.mdl.3.sequential.1.conv.weight", (size_t)C * 17), C, 17);
+        o.Wo = ld.push(ld.get(p + "to_out.mdl.1.weight", (size_t)C * 1024), (size_t)C * 1024);
+        const float* go = ld.get(p + "to_out.mdl.0.g", 1);
+        o.go = ld.room(C);
+        if (go) for (int i = 0; i < C; ++i) ld.host[o.go + i] = go[0];
+        o.bo = ld.push(ld.get(p + "to_out.mdl.1.bias", C), C);
+        o.cw_o = ld.push_tapmajor(ld.get(p + "to_out.mdl.3.sequential.1.conv.weight", (size_t)C * 17), C, 17);
         // FSMN
         const std::string q = PFX + "fsmn." + std::to_string(l) + ".";
-        o.W1 = push(get(q + "conv1.0.weight", (size_t)INNER * C), (size_t)INNER * C);
-        o.b1 = push(get(q + "conv1.0.bias", INNER), INNER);
-        o.a1 = push(get(q + "conv1.1.weight", 1), 1);
-        o.ln1g = push(get(q + "norm1.weight", INNER), INNER);
-        o.ln1b = push(get(q + "norm1.bias", INNER), INNER);
+        o.W1 = ld.push(ld.get(q + "conv1.0.weight", (size_t)INNER * C), (size_t)INNER * C);
+        o.b1 = ld.push(ld.get(q + "conv1.0.bias", INNER), INNER);
+        o.a1 = ld.push(ld.get(q + "conv1.1.weight", 1), 1);
+        o.ln1g = ld.push(ld.get(q + "norm1.weight", INNER), INNER);
+        o.ln1b = ld.push(ld.get(q + "norm1.bias", INNER), INNER);
         // fold the FFConvM LayerNorm affine into its Linear:  LN(h)W^T+b = hhat (W diag(g))^T + (b + W beta)
-        o.Wuv = host.size(); host.resize(host.size() + al((size_t)C * INNER));
-        o.buv = host.size(); host.resize(host.size() + al(C));
-        for (int br = 0; br < 2 && ok; ++br) {
+        o.Wuv = ld.room((size_t)C * INNER);
+        o.buv = ld.room(C);
+        for (int br = 0; br < 2 && ld.ok(); ++br) {
             const std::string r = q + "gated_fsmn." + (br == 0 ? "to_u" : "to_v") + ".mdl.";
-            const float* lg = get(r + "0.weight", INNER);
-            const float* lb = get(r + "0.bias", INNER);
-            const float* W = get(r + "1.weight", (size_t)INNER * INNER);
-            const float* bb = get(r + "1.bias", INNER);
-            if (!ok) break;
+            const float* lg = ld.get(r + "0.weight", INNER);
+            const float* lb = ld.get(r + "0.bias", INNER);
+            const float* W = ld.get(r + "1.weight", (size_t)INNER * INNER);
+            const float* bb = ld.get(r + "1.bias", INNER);
+            if (!ld.ok()) break;
             for (int n = 0; n < INNER; ++n) {
                 double acc = bb[n];
                 for (int k = 0; k < INNER; ++k) {
-                    host[o.Wuv + ((size_t)br * INNER + n) * INNER + k] = W[(size_t)n * INNER + k] * lg[k];
+                    ld.host[o.Wuv + ((size_t)br * INNER + n) * INNER + k] = W[(size_t)n * INNER + k] * lg[k];
                     acc += (double)W[(size_t)n * INNER + k] * (double)lb[k];
                 }
-                host[o.buv + br * INNER + n] = (float)acc;
+                ld.host[o.buv + br * INNER + n] = (float)acc;
             }
         }
-        if (!ok) break;
+        if (!ld.ok()) break;
         {
-            const float* cu = get(q + "gated_fsmn.to_u.mdl.3.sequential.1.conv.weight", (size_t)INNER * 17);
-            const float* cv = get(q + "gated_fsmn.to_v.mdl.3.sequential.1.conv.weight", (size_t)INNER * 17);
-            o.cw_uv = host.size(); host.resize(host.size() + al((size_t)17 * C));
+            const float* cu = ld.get(q + "gated_fsmn.to_u.mdl.3.sequential.1.conv.weight", (size_t)INNER * 17);
+            const float* cv = ld.get(q + "gated_fsmn.to_v.mdl.3.sequential.1.conv.weight", (size_t)INNER * 17);
+            o.cw_uv = ld.room((size_t)17 * C);
             if (cu && cv) for (int c = 0; c < INNER; ++c) for (int t = 0; t < 17; ++t) {
-                host[o.cw_uv + (size_t)t * C + c] = cu[c * 17 + t];
-                host[o.cw_uv + (size_t)t * C + INNER + c] = cv[c * 17 + t];
+                ld.host[o.cw_uv + (size_t)t * C + c] = cu[c * 17 + t];
+                ld.host[o.cw_uv + (size_t)t * C + INNER + c] = cv[c * 17 + t];
             }
         }
         const std::string f = q + "gated_fsmn.fsmn.";
-        o.Wl = push(get(f + "linear.weight", (size_t)INNER * INNER), (size_t)INNER * INNER);
-        o.bl = push(get(f + "linear.bias", INNER), INNER);
-        o.Wp = push(get(f + "project.weight", (size_t)INNER * INNER), (size_t)INNER * INNER);
-        o.w1T = push_tapmajor(get(f + "conv.conv1.weight", (size_t)INNER * 39), INNER, 39);
+        o.Wl = ld.push(ld.get(f + "linear.weight", (size_t)INNER * INNER), (size_t)INNER * INNER);
+        o.bl = ld.push(ld.get(f + "linear.bias", INNER), INNER);
+        o.Wp = ld.push(ld.get(f + "project.weight", (size_t)INNER * INNER), (size_t)INNER * INNER);
+        o.w1T = ld.push_tapmajor(ld.get(f + "conv.conv1.weight", (size_t)INNER * 39), INNER, 39);
         {   // conv2.weight [256][2][39] -> [39][2][256]
-            const float* w2 = get(f + "conv.conv2.weight", (size_t)INNER * 2 * 39);
-            o.w2T = host.size(); host.resize(host.size() + al((size_t)39 * 2 * INNER));
+            const float* w2 = ld.get(f + "conv.conv2.weight", (size_t)INNER * 2 * 39);
+            o.w2T = ld.room((size_t)39 * 2 * INNER);
             if (w2) for (int j = 0; j < INNER; ++j) for (int ic = 0; ic < 2; ++ic) for (int t = 0; t < 39; ++t)
-                host[o.w2T + ((size_t)t * 2 + ic) * INNER + j] = w2[((size_t)j * 2 + ic) * 39 + t];
+                ld.host[o.w2T + ((size_t)t * 2 + ic) * INNER + j] = w2[((size_t)j * 2 + ic) * 39 + t];
         }
-        o.ing = push(get(f + "conv.norm1.weight", INNER), INNER); push(get(f + "conv.norm2.weight", INNER), INNER);
-        o.inb = push(get(f + "conv.norm1.bias", INNER), INNER); push(get(f + "conv.norm2.bias", INNER), INNER);
-        o.pre = push(get(f + "conv.prelu1.weight", INNER), INNER); push(get(f + "conv.prelu2.weight", INNER), INNER);
-        o.ln2g = push(get(q + "norm2.weight", INNER), INNER);
-        o.ln2b = push(get(q + "norm2.bias", INNER), INNER);
-        o.W2 = push(get(q + "conv2.weight", (size_t)C * INNER), (size_t)C * INNER);
-        o.b2 = push(get(q + "conv2.bias", C), C);
+        o.ing = ld.push(ld.get(f + "conv.norm1.weight", INNER), INNER); ld.push(ld.get(f + "conv.norm2.weight", INNER), INNER);
+        o.inb = ld.push(ld.get(f + "conv.norm1.bias", INNER), INNER); ld.push(ld.get(f + "conv.norm2.bias", INNER), INNER);
+        o.pre = ld.push(ld.get(f + "conv.prelu1.weight", INNER), INNER); ld.push(ld.get(f + "conv.prelu2.weight", INNER), INNER);
+        o.ln2g = ld.push(ld.get(q + "norm2.weight", INNER), INNER);
+        o.ln2b = ld.push(ld.get(q + "norm2.bias", INNER), INNER);
+        o.W2 = ld.push(ld.get(q + "conv2.weight", (size_t)C * INNER), (size_t)C * INNER);
+        o.b2 = ld.push(ld.get(q + "conv2.bias", C), C);
     }
     size_t encT = 0, gn1g = 0, gn1b = 0, Wenc = 0, pes = 0, invf = 0, rotf = 0, lnfg = 0, lnfb = 0, gn2g = 0, gn2b = 0, prelu = 0,
            Wout = 0, bout = 0, Wtg = 0, btg = 0, Wdec1 = 0, decT = 0;
-    if (ok) {
-        encT = push_tapmajor(get("enc.conv1d.weight", (size_t)C * 16), C, 16);
-        gn1g = push(get("mask_net.norm.weight", C), C);
-        gn1b = push(get("mask_net.norm.bias", C), C);
-        Wenc = push(get("mask_net.conv1d_encoder.weight", (size_t)C * C), (size_t)C * C);
-        pes = push(get("mask_net.pos_enc.scale", 1), 1);
-        invf = push(get("mask_net.pos_enc.inv_freq", 256), 256);
-        rotf = push(get(PFX + "layers.0.rotary_pos_emb.freqs", 16), 16);
-        lnfg = push(get("mask_net.mdl.intra_mdl.norm.weight", C), C);
-        lnfb = push(get("mask_net.mdl.intra_mdl.norm.bias", C), C);
-        gn2g = push(get("mask_net.mdl.intra_norm.weight", C), C);
-        gn2b = push(get("mask_net.mdl.intra_norm.bias", C), C);
-        prelu = push(get("mask_net.prelu.weight", 1), 1);
-        Wout = push(get("mask_net.conv1d_out.weight", (size_t)2 * C * C), (size_t)2 * C * C);
-        bout = push(get("mask_net.conv1d_out.bias", 2 * C), 2 * C);
-        Wtg = push(get("mask_net.output.0.weight", (size_t)C * C), (size_t)C * C);
-        push(get("mask_net.output_gate.0.weight", (size_t)C * C), (size_t)C * C);
-        btg = push(get("mask_net.output.0.bias", C), C);
-        push(get("mask_net.output_gate.0.bias", C), C);
-        Wdec1 = push(get("mask_net.conv1_decoder.weight", (size_t)C * C), (size_t)C * C);
-        decT = push_tapmajor(get("dec.weight", (size_t)C * 16), C, 16);
+    if (ld.ok()) {
+        encT = ld.push_tapmajor(ld.get("enc.conv1d.weight", (size_t)C * 16), C, 16);
+        gn1g = ld.push(ld.get("mask_net.norm.weight", C), C);
+        gn1b = ld.push(ld.get("mask_net.norm.bias", C), C);
+        Wenc = ld.push(ld.get("mask_net.conv1d_encoder.weight", (size_t)C * C), (size_t)C * C);
+        pes = ld.push(ld.get("mask_net.pos_enc.scale", 1), 1);
+        invf = ld.push(ld.get("mask_net.pos_enc.inv_freq", 256), 256);
+        rotf = ld.push(ld.get(PFX + "layers.0.rotary_pos_emb.freqs", 16), 16);
+        lnfg = ld.push(ld.get("mask_net.mdl.intra_mdl.norm.weight", C), C);
+        lnfb = ld.push(ld.get("mask_net.mdl.intra_mdl.norm.bias", C), C);
+        gn2g = ld.push(ld.get("mask_net.mdl.intra_norm.weight", C), C);
+        gn2b = ld.push(ld.get("mask_net.mdl.intra_norm.bias", C), C);
+        prelu = ld.push(ld.get("mask_net.prelu.weight", 1), 1);
+        Wout = ld.push(ld.get("mask_net.conv1d_out.weight", (size_t)2 * C * C), (size_t)2 * C * C);
+        bout = ld.push(ld.get("mask_net.conv1d_out.bias", 2 * C), 2 * C);
+        Wtg = ld.push(ld.get("mask_net.output.0.weight", (size_t)C * C), (size_t)C * C);
+        ld.push(ld.get("mask_net.output_gate.0.weight", (size_t)C * C), (size_t)C * C);
+        btg = ld.push(ld.get("mask_net.output.0.bias", C), C);
+        ld.push(ld.get("mask_net.output_gate.0.bias", C), C);
+        Wdec1 = ld.push(ld.get("mask_net.conv1_decoder.weight", (size_t)C * C), (size_t)C * C);
+        decT = ld.push_tapmajor(ld.get("dec.weight", (size_t)C * 16), C, 16);
     }
-    if (!ok) return tdx::fail(TDX_E_BLOB, "tdx_mf2_create: tensor missing or wrong size: " + missing);
-    {   // strict both ways, like load_state_dict(strict=True) at base_model.py:63
-        const std::string extra = bl.first_unused();
-        if (!extra.empty()) return tdx::fail(TDX_E_BLOB, "tdx_mf2_create: unexpected tensor in the blob: " + extra);
-    }
-
-    tdx::DeviceGuard guard(device);
-    hipError_t e = guard.err;
-    if (e != hipSuccess) return tdx::fail_hip(e, __FILE__, __LINE__);
-    float* dev = nullptr;
-    e = hipMalloc(&dev, host.size() * sizeof(float));
-    if (e != hipSuccess) return tdx::fail_hip(e, __FILE__, __LINE__);
-    e = hipMemcpy(dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(dev); return tdx::fail_hip(e, __FILE__, __LINE__); }
-
-    tdx_mf2* h = new tdx_mf2();
-    h->dev_planes = nullptr; h->dev_static = nullptr;
-    h->device = device; h->L = L; h->dev_weights = dev; h->n_weights = host.size(); h->taps = 0; h->ev_used = 0;
+    std::unique_ptr<tdx_mf2> h(new tdx_mf2());
+    h->device = device; h->L = L; h->taps = 0; h->ev_used = 0;
+    TRY(ld.finish("tdx_mf2_create", true, device, h->dev_weights));
+    const float* dev = h->dev_weights;
     h->layers.resize(L);
     for (int l = 0; l < L; ++l) {
         const Off& o = offs[l]; LayerW& w = h->layers[l];
@@ -939,46 +897,32 @@ int tdx_mf2_create(const tdx_mf2_config* cfg, const void* blob, size_t blob_byte
     h->inv_freq = dev + invf; h->rot_freqs = dev + rotf; h->lnfg = dev + lnfg; h->lnfb = dev + lnfb; h->gn2g = dev + gn2g;
     h->gn2b = dev + gn2b; h->prelu = dev + prelu; h->Wout = dev + Wout; h->bout = dev + bout; h->Wtg = dev + Wtg; h->btg = dev + btg;
     h->Wdec1 = dev + Wdec1; h->decT = dev + decT;
-    e = hipMalloc(&h->dev_static, stat_host.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->dev_static, stat_host.data(), stat_host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
+    {
+        tdx::DeviceGuard guard(device);
+        const hipError_t e = guard.err != hipSuccess ? guard.err : h->dev_static.upload(stat_host.data(), stat_host.size() * sizeof(float));
+        if (e != hipSuccess) return tdx::fail_hip(e, __FILE__, __LINE__);
+    }
     for (int l = 0; l < L; ++l) { h->layers[l].sv_vu = sv_host[l * 2]; h->layers[l].sv_lk = sv_host[l * 2 + 1]; h->layers[l].st = h->dev_static + l * 2; }
     // ---- split every nn.Linear weight [N][K] into f16 planes + row scales, once
     {
-        struct Job { const float* w; int N, K; H3W* dst; };
-        std::vector<Job> jobs;
+        std::vector<tdx::PlaneJob> jobs;
+        auto job = [&](const float* w, int N, int K, H3W& dst) { jobs.push_back({w, N, K, &dst.p, &dst.s}); };
         for (int l = 0; l < L; ++l) {
             LayerW& w = h->layers[l];
-            jobs.push_back({w.Whq, HQ, C, &w.hWhq}); jobs.push_back({w.Wo, C, 1024, &w.hWo}); jobs.push_back({w.W1, INNER, C, &w.hW1});
-            jobs.push_back({w.Wuv, C, INNER, &w.hWuv}); jobs.push_back({w.Wl, INNER, INNER, &w.hWl});
-            jobs.push_back({w.Wp, INNER, INNER, &w.hWp}); jobs.push_back({w.W2, C, INNER, &w.hW2});
+            job(w.Whq, HQ, C, w.hWhq); job(w.Wo, C, 1024, w.hWo); job(w.W1, INNER, C, w.hW1);
+            job(w.Wuv, C, INNER, w.hWuv); job(w.Wl, INNER, INNER, w.hWl);
+            job(w.Wp, INNER, INNER, w.hWp); job(w.W2, C, INNER, w.hW2);
         }
-        jobs.push_back({h->Wenc, C, C, &h->hWenc}); jobs.push_back({h->Wout, 2 * C, C, &h->hWout});
-        jobs.push_back({h->Wtg, 2 * C, C, &h->hWtg}); jobs.push_back({h->Wdec1, C, C, &h->hWdec1});
-        size_t bytes = 0;
-        for (const Job& j : jobs) bytes += (size_t)j.N * j.K * 4 + (size_t)al(j.N) * 4;
-        e = hipMalloc(&h->dev_planes, bytes);
-        if (e != hipSuccess) { hipFree(dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-        unsigned char* q = h->dev_planes;
-        for (const Job& j : jobs) {
-            float* sc = (float*)(q + (size_t)j.N * j.K * 4);
-            e = tdx::launch_h3_split_rows(j.w, j.K, q, sc, j.N, j.K, nullptr);
-            if (e != hipSuccess) { hipFree(h->dev_planes); hipFree(dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-            j.dst->p = q; j.dst->s = sc;
-            q += (size_t)j.N * j.K * 4 + (size_t)al(j.N) * 4;
-        }
-        e = hipDeviceSynchronize();
-        if (e != hipSuccess) { hipFree(h->dev_planes); hipFree(dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
+        job(h->Wenc, C, C, h->hWenc); job(h->Wout, 2 * C, C, h->hWout);
+        job(h->Wtg, 2 * C, C, h->hWtg); job(h->Wdec1, C, C, h->hWdec1);
+        TRY(tdx::split_weight_planes(jobs, device, h->dev_planes));
     }
-    *out = h;
+    *out = h.release();
     return TDX_OK;
 }
 
 int tdx_mf2_destroy(tdx_mf2* h) {
     if (!h) return TDX_OK;
-    if (h->dev_weights) hipFree(h->dev_weights);
-    if (h->dev_planes) hipFree(h->dev_planes);
-    if (h->dev_static) hipFree(h->dev_static);
     for (auto e : h->ev0) hipEventDestroy(e);
     for (auto e : h->ev1) hipEventDestroy(e);
     for (auto& kv : h->side_ctx) {

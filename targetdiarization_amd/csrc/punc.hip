@@ -22,14 +22,6 @@ using namespace tdx;
 namespace {
 
 constexpr int PD = 256, PH = 8, PDK = 32, PFFN = 1024, PKS = 11, PMAXT = 1024;
-inline size_t al(size_t n) { return (n + 63) / 64 * 64; }
-inline int up(int n, int m) { return (n + m - 1) / m * m; }
-#define LAUNCH_CHECK()                                    \
-    do {                                                  \
-        hipError_t e__ = hipGetLastError();               \
-        if (e__ != hipSuccess) return tdx::fail_hip(e__, __FILE__, __LINE__); \
-    } while (0)
-#define TRY(x) do { int rc__ = (x); if (rc__ != TDX_OK) return rc__; } while (0)
 
 // x[b,t,:] = emb[id] * sqrt(256) + PE(t + 1)        (SinusoidalPositionEncoder: [sin | cos] halves, positions from 1)
 __global__ __launch_bounds__(256) void punc_embed_kernel(const int* __restrict__ ids, const float* __restrict__ emb, int vocab, float* __restrict__ x, int T) {
@@ -148,7 +140,7 @@ struct PLayer { size_t Wqkv, bqkv, fsmnT, Wo, bo, W1, b1, W2, b2, n1g, n1b, n2g,
 
 struct tdx_punc {
     int device = 0, L = 0, vocab = 0, npunc = 0;
-    float* dev = nullptr;
+    tdx::DevBuf dev;
     size_t emb = 0, ang = 0, anb = 0, Wd = 0, bd = 0;
     std::vector<PLayer> layers;
 };
@@ -157,63 +149,39 @@ extern "C" {
 
 int tdx_punc_create(int num_blocks, int vocab, int npunc, const void* blob, size_t blob_bytes, int device, tdx_punc** out) {
     if (!blob || !out || num_blocks < 1 || vocab < 1 || npunc < 1 || npunc > 128) return tdx::fail(TDX_E_INVALID, "tdx_punc_create: bad argument");
-    tdx::Blob bl;
-    if (!bl.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_punc_create: malformed TDXW blob");
-    std::vector<float> host;
-    bool ok = true; std::string missing;
-    auto get = [&](const std::string& name, size_t n) -> const float* {
-        const tdx::BlobTensor* t = bl.find(name);
-        if (!t || t->numel != n) { ok = false; if (missing.empty()) missing = name; return nullptr; }
-        return t->data;
-    };
-    auto push = [&](const float* p, size_t n, size_t npad = 0) -> size_t {
-        size_t o = host.size(); host.resize(o + al(std::max(n, npad)), 0.f);
-        if (p) memcpy(host.data() + o, p, n * sizeof(float));
-        return o;
-    };
-    tdx_punc* h = new tdx_punc();
+    tdx::Loader ld;
+    if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_punc_create: malformed TDXW blob");
+    std::unique_ptr<tdx_punc> h(new tdx_punc());
     h->L = num_blocks; h->vocab = vocab; h->npunc = npunc;
-    h->emb = push(get("embed.weight", (size_t)vocab * PD), (size_t)vocab * PD);
-    for (int l = 0; l < num_blocks && ok; ++l) {
+    h->emb = ld.push(ld.get("embed.weight", (size_t)vocab * PD), (size_t)vocab * PD);
+    for (int l = 0; l < num_blocks && ld.ok(); ++l) {
         const std::string p = l == 0 ? "encoder.encoders0.0." : "encoder.encoders." + std::to_string(l - 1) + ".";
         PLayer w;
-        w.Wqkv = push(get(p + "self_attn.linear_q_k_v.weight", (size_t)3 * PD * PD), (size_t)3 * PD * PD);
-        w.bqkv = push(get(p + "self_attn.linear_q_k_v.bias", 3 * PD), 3 * PD);
-        {   // fsmn_block.weight [256][1][11] -> tap-major [11][256]
-            const float* fw = get(p + "self_attn.fsmn_block.weight", (size_t)PD * PKS);
-            w.fsmnT = host.size(); host.resize(host.size() + al((size_t)PKS * PD), 0.f);
-            if (fw) for (int c = 0; c < PD; ++c) for (int j = 0; j < PKS; ++j) host[w.fsmnT + (size_t)j * PD + c] = fw[(size_t)c * PKS + j];
-        }
-        w.Wo = push(get(p + "self_attn.linear_out.weight", (size_t)PD * PD), (size_t)PD * PD);
-        w.bo = push(get(p + "self_attn.linear_out.bias", PD), PD);
-        w.W1 = push(get(p + "feed_forward.w_1.weight", (size_t)PFFN * PD), (size_t)PFFN * PD);
-        w.b1 = push(get(p + "feed_forward.w_1.bias", PFFN), PFFN);
-        w.W2 = push(get(p + "feed_forward.w_2.weight", (size_t)PD * PFFN), (size_t)PD * PFFN);
-        w.b2 = push(get(p + "feed_forward.w_2.bias", PD), PD);
-        w.n1g = push(get(p + "norm1.weight", PD), PD); w.n1b = push(get(p + "norm1.bias", PD), PD);
-        w.n2g = push(get(p + "norm2.weight", PD), PD); w.n2b = push(get(p + "norm2.bias", PD), PD);
+        w.Wqkv = ld.push(ld.get(p + "self_attn.linear_q_k_v.weight", (size_t)3 * PD * PD), (size_t)3 * PD * PD);
+        w.bqkv = ld.push(ld.get(p + "self_attn.linear_q_k_v.bias", 3 * PD), 3 * PD);
+        w.fsmnT = ld.push_tapmajor(ld.get(p + "self_attn.fsmn_block.weight", (size_t)PD * PKS), PD, PKS);      // [256][1][11] -> [11][256]
+        w.Wo = ld.push(ld.get(p + "self_attn.linear_out.weight", (size_t)PD * PD), (size_t)PD * PD);
+        w.bo = ld.push(ld.get(p + "self_attn.linear_out.bias", PD), PD);
+        w.W1 = ld.push(ld.get(p + "feed_forward.w_1.weight", (size_t)PFFN * PD), (size_t)PFFN * PD);
+        w.b1 = ld.push(ld.get(p + "feed_forward.w_1.bias", PFFN), PFFN);
+        w.W2 = ld.push(ld.get(p + "feed_forward.w_2.weight", (size_t)PD * PFFN), (size_t)PD * PFFN);
+        w.b2 = ld.push(ld.get(p + "feed_forward.w_2.bias", PD), PD);
+        w.n1g = ld.push(ld.get(p + "norm1.weight", PD), PD); w.n1b = ld.push(ld.get(p + "norm1.bias", PD), PD);
+        w.n2g = ld.push(ld.get(p + "norm2.weight", PD), PD); w.n2b = ld.push(ld.get(p + "norm2.bias", PD), PD);
         h->layers.push_back(w);
     }
-    h->ang = push(get("encoder.after_norm.weight", PD), PD);
-    h->anb = push(get("encoder.after_norm.bias", PD), PD);
-    h->Wd = push(get("decoder.weight", (size_t)npunc * PD), (size_t)npunc * PD, (size_t)128 * PD);       // rows read in 128-row tiles
-    h->bd = push(get("decoder.bias", npunc), npunc, 128);
-    if (!ok) { delete h; return tdx::fail(TDX_E_BLOB, "tdx_punc_create: tensor missing or wrong size: " + missing); }
-    { const std::string extra = bl.first_unused(); if (!extra.empty()) { delete h; return tdx::fail(TDX_E_BLOB, "tdx_punc_create: unexpected tensor in the blob: " + extra); } }
-    tdx::DeviceGuard guard(device);
-    hipError_t e = guard.err;
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
+    h->ang = ld.push(ld.get("encoder.after_norm.weight", PD), PD);
+    h->anb = ld.push(ld.get("encoder.after_norm.bias", PD), PD);
+    h->Wd = ld.push(ld.get("decoder.weight", (size_t)npunc * PD), (size_t)npunc * PD, (size_t)128 * PD);       // rows read in 128-row tiles
+    h->bd = ld.push(ld.get("decoder.bias", npunc), npunc, 128);
     h->device = device;
-    e = hipMalloc(&h->dev, host.size() * sizeof(float));
-    if (e != hipSuccess) { delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-    e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(h->dev); delete h; return tdx::fail_hip(e, __FILE__, __LINE__); }
-    *out = h;
+    TRY(ld.finish("tdx_punc_create", true, device, h->dev));
+    *out = h.release();
     return TDX_OK;
 }
 
 int tdx_punc_destroy(tdx_punc* h) {
-    if (h) { if (h->dev) hipFree(h->dev); delete h; }
+    delete h;
     return TDX_OK;
 }
 

@@ -1,13 +1,17 @@
-// tdx_common.hpp — status/error plumbing and the TDXW weight-blob reader shared by the
-// C-ABI translation units.  No exception crosses the C boundary: entry points return a
+// tdx_common.hpp — status/error plumbing, the TDXW weight-blob reader, the weight loader (Loader) and the owner of a device
+// allocation (DevBuf) shared by the C-ABI translation units.  No exception crosses the C boundary: entry points return a
 // TDX_E_* code and leave a message in a thread-local string (include/tdx.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <map>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace tdx {
@@ -24,6 +28,17 @@ inline int fail_hip(hipError_t e, const char* file, int line) {
     last_error() = std::string("HIP error: ") + hipGetErrorString(e) + " at " + file + ":" + std::to_string(line);
     return 3;  // TDX_E_HIP
 }
+
+inline size_t al(size_t n) { return (n + 63) / 64 * 64; }      // weight images and workspaces are laid out in 64-float units
+inline int up(int n, int m) { return (n + m - 1) / m * m; }
+
+// after a kernel launch, inside a function that returns a TDX status
+#define LAUNCH_CHECK()                                    \
+    do {                                                  \
+        hipError_t e__ = hipGetLastError();               \
+        if (e__ != hipSuccess) return tdx::fail_hip(e__, __FILE__, __LINE__); \
+    } while (0)
+#define TRY(x) do { int rc__ = (x); if (rc__ != 0) return rc__; } while (0)
 
 // Makes `device` current for the lifetime of the guard and restores the caller's device afterwards (the
 // C-ABI never leaves the calling thread on another device; a forward on a handle whose device is not current
@@ -107,6 +122,104 @@ struct Blob {
     std::string first_unused() const {
         for (const auto& kv : t) if (!kv.second.used) return kv.first;
         return std::string();
+    }
+};
+
+// One hipMalloc allocation, freed with its owner (move-only).  A handle struct holds its weight images as DevBuf members, so
+// `delete h` releases them on every path; it reads as the float image it owns (`h->dev + offset`).
+class DevBuf {
+    void* p_ = nullptr;
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); return *this; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p_) (void)hipFree(p_); }
+    hipError_t alloc(size_t bytes) {
+        if (p_) { (void)hipFree(p_); p_ = nullptr; }
+        return hipMalloc(&p_, bytes);
+    }
+    hipError_t upload(const void* host, size_t bytes) {        // alloc + blocking copy
+        const hipError_t e = alloc(bytes);
+        return e != hipSuccess ? e : hipMemcpy(p_, host, bytes, hipMemcpyHostToDevice);
+    }
+    void* get() const { return p_; }
+    operator float*() const { return static_cast<float*>(p_); }
+};
+
+// What every tdx_*_create does with its blob: look tensors up by name (and size or shape), stage them — as they are, padded,
+// or transposed — into one host image at 64-float aligned offsets, then upload the image.  The first tensor that is missing
+// or of the wrong size is remembered and reported by finish(); until then get() returns nullptr for it and the push
+// functions leave zeros in its place, so a create reads as the list of tensors the model needs.
+struct Loader {
+    Blob blob;
+    std::vector<float> host;
+    bool parse(const void* p, size_t bytes) { return blob.parse(p, bytes); }
+    bool ok() const { return missing_.empty(); }
+    const std::string& missing() const { return missing_; }
+
+    const float* get(const std::string& name, size_t numel) {
+        const BlobTensor* t = blob.find(name);
+        if (!t || t->numel != numel) return miss(name, false);
+        return t->data;
+    }
+    // name AND shape: a transposed matrix has the right numel and must not load
+    const float* get(const std::string& name, std::initializer_list<uint32_t> dims) {
+        const BlobTensor* t = blob.find(name);
+        bool same = t && t->ndim == (int)dims.size();
+        if (same) { int d = 0; for (uint32_t v : dims) same = same && t->dims[d++] == v; }
+        if (!same) return miss(name, true);
+        return t->data;
+    }
+    // a tensor the checkpoint may leave out (nullptr, no error); if present its size must match
+    const float* get_optional(const std::string& name, size_t numel) {
+        const BlobTensor* t = blob.find(name);
+        if (t && t->numel != numel) return miss(name, false);
+        return t ? t->data : nullptr;
+    }
+
+    size_t room(size_t n) { const size_t o = host.size(); host.resize(o + al(n), 0.f); return o; }      // zeroed
+    size_t push(const float* p, size_t n, size_t npad = 0) {
+        const size_t o = room(std::max(n, npad));
+        if (p) memcpy(host.data() + o, p, n * sizeof(float));
+        return o;
+    }
+    // depthwise conv weight [C][k] -> tap-major [k][C]
+    size_t push_tapmajor(const float* w, int C, int k) {
+        const size_t o = room((size_t)C * k);
+        if (w) for (int c = 0; c < C; ++c) for (int t = 0; t < k; ++t) host[o + (size_t)t * C + c] = w[(size_t)c * k + t];
+        return o;
+    }
+    // [N][K] -> [N][Kp], columns K..Kp-1 zero
+    size_t push_rows_padded(const float* w, int N, int K, int Kp) {
+        const size_t o = room((size_t)N * Kp);
+        if (w) for (int n = 0; n < N; ++n) memcpy(host.data() + o + (size_t)n * Kp, w + (size_t)n * K, K * sizeof(float));
+        return o;
+    }
+
+    // the checks (a tensor missing; with `strict`, one nobody asked for — load_state_dict(strict=True)), then `device` is
+    // made current for the copy and the image goes to `dev`.  Returns a TDX status; nothing touches the device before the
+    // blob is accepted.
+    int finish(const char* fn, bool strict, int device, DevBuf& dev) {
+        if (!ok()) return fail(2, std::string(fn) + ": tensor missing or wrong " + (by_shape_ ? "shape: " : "size: ") + missing_);
+        if (strict) {
+            const std::string extra = blob.first_unused();
+            if (!extra.empty()) return fail(2, std::string(fn) + ": unexpected tensor: " + extra);
+        }
+        DeviceGuard guard(device);
+        if (guard.err != hipSuccess) return fail_hip(guard.err, __FILE__, __LINE__);
+        const hipError_t e = dev.upload(host.data(), host.size() * sizeof(float));
+        if (e != hipSuccess) return fail_hip(e, __FILE__, __LINE__);
+        return 0;
+    }
+
+private:
+    std::string missing_;
+    bool by_shape_ = false;
+    const float* miss(const std::string& name, bool by_shape) {
+        if (missing_.empty()) { missing_ = name; by_shape_ = by_shape; }
+        return nullptr;
     }
 };
 

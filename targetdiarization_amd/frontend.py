@@ -2,7 +2,6 @@
 MDX block STFT/iSTFT (ConvTDFNet.stft/.istft, AudioProcessor.py:82-120)."""
 from __future__ import annotations
 
-import ctypes as C
 
 import torch
 
@@ -18,13 +17,9 @@ class Fbank:
     mode "asr": hamming window, input x32768 (funasr WavFrontend before LFR/CMVN)."""
 
     def __init__(self, mode: str = "sv", device="cuda:0"):
-        self.device = torch.device(device)
         self._l = _lib.lib()
-        h = C.c_void_p()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        _lib.check(self._l.tdx_fbank_create({"sv": 0, "asr": 1}[mode], idx, C.byref(h)))
-        self._h = h
+        self._own = _lib.Handle(device, "Fbank", self._l.tdx_fbank_create, self._l.tdx_fbank_destroy, {"sv": 0, "asr": 1}[mode])
+        self.device, self._h = self._own.device, self._own.ptr
 
     def frames(self, N: int) -> int:
         return int(self._l.tdx_fbank_frames(N))
@@ -43,12 +38,8 @@ class Fbank:
         _lib.check(self._l.tdx_fbank_forward(self._h, wav.data_ptr(), B, N, out.data_ptr(), ws.data_ptr(), nb, _st(self.device)))
         return out
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._l.tdx_fbank_destroy(self._h); self._h = None
-        except Exception:
-            pass
+    def close(self):
+        self._own.close()
 
 
 def lfr_cmvn(feat: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
@@ -65,15 +56,11 @@ class BlockSTFT:
     (the reference passes dim_t=8 meaning 2**8)."""
 
     def __init__(self, n_fft=6144, hop=2048, dim_f=3072, dim_t=256, device="cuda:0"):
-        self.device = torch.device(device)
         self._l = _lib.lib()
-        h = C.c_void_p()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        _lib.check(self._l.tdx_stft_create(n_fft, hop, dim_f, dim_t, idx, C.byref(h)))
-        self._h = h
+        self._own = _lib.Handle(device, "BlockSTFT", self._l.tdx_stft_create, self._l.tdx_stft_destroy, n_fft, hop, dim_f, dim_t)
+        self.device, self._h = self._own.device, self._own.ptr
         self.n_fft, self.hop, self.dim_f, self.dim_t = n_fft, hop, dim_f, dim_t
-        self.chunk_size = int(self._l.tdx_stft_chunk_size(h))
+        self.chunk_size = int(self._l.tdx_stft_chunk_size(self._h))
         self.dim_c = 4
 
     def _ws(self, R):
@@ -98,9 +85,5 @@ class BlockSTFT:
         _lib.check(self._l.tdx_stft_inverse(self._h, spec.data_ptr(), R, y.data_ptr(), ws.data_ptr(), nb, _st(self.device)))
         return y.reshape(-1, 2, self.chunk_size)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._l.tdx_stft_destroy(self._h); self._h = None
-        except Exception:
-            pass
+    def close(self):
+        self._own.close()

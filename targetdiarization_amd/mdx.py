@@ -20,22 +20,12 @@ from .weights import pack_blob
 class ConvTDFNetBody:
     def __init__(self, state_dict, device="cuda:0", L: int = 11, l: int = 3, g: int = 32, k: int = 3, bn: int = 8, dim_f: int = 3072,
                  dim_t: int = 256, max_blocks_per_launch: int = 8):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.TdxError("ConvTDFNetBody needs a HIP device")
         self._l = _lib.lib()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
         self.dim_f, self.dim_t = dim_f, dim_t
         self.max_blocks_per_launch = max_blocks_per_launch
         cfg = _lib.MdxConfig(num_blocks=L, l=l, g=g, k=k, bn=bn, dim_f=dim_f, dim_t=dim_t)
-        blob = pack_blob(state_dict)
-        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        h = C.c_void_p()
-        with torch.cuda.device(idx):
-            _lib.check(self._l.tdx_mdx_create(C.byref(cfg), buf, len(blob), idx, C.byref(h)))
-        self._h = h
-        self._guard = _lib.HandleGuard(self.device)
+        self._own = _lib.Handle(device, "ConvTDFNetBody", self._l.tdx_mdx_create, self._l.tdx_mdx_destroy, C.byref(cfg), blob=pack_blob(state_dict))
+        self.device, self._h, self._guard = self._own.device, self._own.ptr, self._own.guard
 
     def flops(self, B: int) -> float:
         return float(self._l.tdx_mdx_flops(self._h, B))
@@ -56,9 +46,5 @@ class ConvTDFNetBody:
                 _lib.check(self._l.tdx_mdx_forward(self._h, x.data_ptr(), x.shape[0], out[a:a + step].data_ptr(), ws.data_ptr(), ws.numel(), st))
         return out
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._l.tdx_mdx_destroy(self._h); self._h = None
-        except Exception:
-            pass
+    def close(self):
+        self._own.close()

@@ -3,7 +3,6 @@ non-autoregressive SANM decoder (tdx_pfdec_*, SURVEY "next" row N2).  Together t
 funasr's `AutoModel.generate` (ASRProcessor.py:424); funasr's VAD segmentation, tokenizer files and punctuation stay outside."""
 from __future__ import annotations
 
-import ctypes as C
 
 import torch
 
@@ -15,22 +14,13 @@ from .weights import pack_blob
 class ParaformerEncoder:
     def __init__(self, state_dict, device="cuda:0", num_blocks: int | None = None, cmvn_shift=None, cmvn_scale=None, graph_rows: int = 2048):
         """graph_rows: forwards with B*T <= graph_rows LFR frames are replayed as HIP graphs (_lib.GraphRunner); 0 disables"""
-        self.device = torch.device(device)
         self.graph_rows = graph_rows
-        if self.device.type != "cuda":
-            raise _lib.TdxError("ParaformerEncoder needs a HIP device")
         if num_blocks is None:
             num_blocks = 2 + max(int(k.split("encoders.")[1].split(".")[0]) for k in state_dict if ".encoders." in k)
         self.num_blocks = num_blocks
         self._l = _lib.lib()
-        blob = pack_blob(state_dict)
-        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        h = C.c_void_p()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        _lib.check(self._l.tdx_pfenc_create(num_blocks, buf, len(blob), idx, C.byref(h)))
-        self._h = h
-        self._guard = _lib.HandleGuard(self.device)      # calls on this object are serialised (host lock + device event chain)
+        self._own = _lib.Handle(device, "ParaformerEncoder", self._l.tdx_pfenc_create, self._l.tdx_pfenc_destroy, num_blocks, blob=pack_blob(state_dict))
+        self.device, self._h, self._guard = self._own.device, self._own.ptr, self._own.guard
         self._graphs = _lib.GraphRunner(self.device)
         self.fbank = Fbank("asr", self.device)
         # am.mvn vectors (funasr WavFrontend.apply_cmvn): (x + shift) * scale; identity if absent
@@ -64,12 +54,9 @@ class ParaformerEncoder:
     def __call__(self, wav: torch.Tensor) -> torch.Tensor:
         return self.encode(self.features(wav))
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._l.tdx_pfenc_destroy(self._h); self._h = None
-        except Exception:
-            pass
+    def close(self):
+        self._own.close()
+        self.fbank.close()
 
 
 class ParaformerDecoder:
@@ -82,9 +69,6 @@ class ParaformerDecoder:
     FRAME_MS = 60.0
 
     def __init__(self, state_dict, device="cuda:0", num_blocks: int | None = None, vocab: int | None = None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.TdxError("ParaformerDecoder needs a HIP device")
         if num_blocks is None:
             num_blocks = 1 + max(int(k.split("decoders.")[1].split(".")[0]) for k in state_dict if "decoder.decoders." in k)
         if vocab is None:
@@ -92,14 +76,8 @@ class ParaformerDecoder:
         self.num_blocks, self.vocab = num_blocks, vocab
         self._l = _lib.lib()
         keep = {k: v for k, v in state_dict.items() if k.startswith(("predictor.cif_", "decoder.decoders", "decoder.after_norm", "decoder.output_layer"))}
-        blob = pack_blob(keep)
-        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        h = C.c_void_p()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        _lib.check(self._l.tdx_pfdec_create(num_blocks, vocab, buf, len(blob), idx, C.byref(h)))
-        self._h = h
-        self._guard = _lib.HandleGuard(self.device)      # calls on this object are serialised (host lock + device event chain)
+        self._own = _lib.Handle(device, "ParaformerDecoder", self._l.tdx_pfdec_create, self._l.tdx_pfdec_destroy, num_blocks, vocab, blob=pack_blob(keep))
+        self.device, self._h, self._guard = self._own.device, self._own.ptr, self._own.guard
 
     def predict(self, enc: torch.Tensor):
         """enc [B,T,512] -> (alphas [B,T+1], embeds [B,T+1,512], counts int32 [B], peaks int32 [B,T+1]) on the device"""
@@ -155,9 +133,5 @@ class ParaformerDecoder:
             out.append({"token_ids": [int(t) for t in ids_h[b, :n]], "scores": [float(s) for s in score_h[b, :n]], "timestamp": ts})
         return out
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._l.tdx_pfdec_destroy(self._h); self._h = None
-        except Exception:
-            pass
+    def close(self):
+        self._own.close()

@@ -9,7 +9,6 @@ the punctuated text are host logic restated from the published funasr code [upst
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Callable, Optional, Sequence, Union
 
 import numpy as np
@@ -53,11 +52,6 @@ def split_to_mini_sentence(words: Sequence, word_limit: int = 20):
 class CTTransformer:
     def __init__(self, state_dict, device="cuda:0", vocab: Union[dict, Callable, None] = None, punc_list: Sequence[str] = PUNC_LIST,
                  sentence_end_id: int = 3, unk_id: int = 0, num_blocks: Optional[int] = None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.TdxError("CTTransformer needs a HIP device")
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
         self._l = _lib.lib()
         if num_blocks is None:
             num_blocks = 2 + max([int(k.split("encoders.")[1].split(".")[0]) for k in state_dict if ".encoders." in k] + [-1])
@@ -68,13 +62,9 @@ class CTTransformer:
         self.sentence_end_id, self.unk_id = sentence_end_id, unk_id
         self.vocab = vocab
         self._marks = ["" if p == "_" else p for p in self.punc_list]
-        blob = pack_blob(state_dict)
-        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        h = C.c_void_p()
-        with torch.cuda.device(idx):
-            _lib.check(self._l.tdx_punc_create(num_blocks, self.vocab_size, len(self.punc_list), buf, len(blob), idx, C.byref(h)))
-        self._h = h
-        self._guard = _lib.HandleGuard(self.device)
+        self._own = _lib.Handle(device, "CTTransformer", self._l.tdx_punc_create, self._l.tdx_punc_destroy,
+                                num_blocks, self.vocab_size, len(self.punc_list), blob=pack_blob(state_dict))
+        self.device, self._h, self._guard = self._own.device, self._own.ptr, self._own.guard
 
     @staticmethod
     def _is_ascii(w: str) -> bool:
@@ -231,9 +221,5 @@ class CTTransformer:
             return [r[0] for r in self.inference_batch(list(text))]
         return self.inference(text)[0] if text else text
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._l.tdx_punc_destroy(self._h); self._h = None
-        except Exception:
-            pass
+    def close(self):
+        self._own.close()

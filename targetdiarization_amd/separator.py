@@ -20,22 +20,13 @@ class MossFormer2Separator:
         """graph_rows: forwards with B*S <= graph_rows token rows (the reference's own call pattern: ONE window per call) are
         captured once per (B, T) as a HIP graph and replayed — the ~450 launches of a forward are then one submission (at
         S = 17 000 the kernels are 20-100 us each and the launch gaps are a tenth of the time); 0 disables."""
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.TdxError("MossFormer2Separator needs a HIP device (cuda:N); there is no CPU path")
         if num_blocks is None:
             num_blocks = 1 + max(int(k.split("layers.")[1].split(".")[0]) for k in state_dict if ".layers." in k)
         self.num_blocks = num_blocks
         self._l = _lib.lib()
-        blob = pack_blob(state_dict)
         cfg = _lib.Mf2Config(num_blocks=num_blocks, channels=512, kernel_size=16, num_spks=2, group_size=256)
-        h = C.c_void_p()
-        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        with torch.cuda.device(idx):
-            _lib.check(self._l.tdx_mf2_create(C.byref(cfg), buf, len(blob), idx, C.byref(h)))
-        self._h = h
-        self._guard = _lib.HandleGuard(self.device)      # calls on this object are serialised (host lock + device event chain)
+        self._own = _lib.Handle(device, "MossFormer2Separator", self._l.tdx_mf2_create, self._l.tdx_mf2_destroy, C.byref(cfg), blob=pack_blob(state_dict))
+        self.device, self._h, self._guard = self._own.device, self._own.ptr, self._own.guard
         self._ws = None
         self._taps = False
         self._profiling = False
@@ -140,10 +131,5 @@ class MossFormer2Separator:
             return dst.view(self.num_blocks, 2)
         return dst.view(2, B, S, 512) if name == "mask" else dst.view(B, S, 512)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._l.tdx_mf2_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+    def close(self):
+        self._own.close()

@@ -2,7 +2,6 @@
 TargetASR-compatible host methods (TargetASR.py:144-163)."""
 from __future__ import annotations
 
-import ctypes as C
 
 import numpy as np
 import torch
@@ -15,20 +14,10 @@ from .weights import drop_num_batches_tracked, pack_blob
 class ERes2NetV2:
     def __init__(self, state_dict, device="cuda:0", graph_frames: int = 4000):
         """graph_frames: forwards with B*F <= graph_frames fbank frames are replayed as HIP graphs (_lib.GraphRunner); 0 disables"""
-        self.device = torch.device(device)
         self.graph_frames = graph_frames
-        if self.device.type != "cuda":
-            raise _lib.TdxError("ERes2NetV2 needs a HIP device")
         self._l = _lib.lib()
-        blob = pack_blob(state_dict)
-        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        h = C.c_void_p()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        with torch.cuda.device(idx):
-            _lib.check(self._l.tdx_eres2net_create(buf, len(blob), idx, C.byref(h)))
-        self._h = h
-        self._guard = _lib.HandleGuard(self.device)      # calls on this object are serialised (host lock + device event chain)
+        self._own = _lib.Handle(device, "ERes2NetV2", self._l.tdx_eres2net_create, self._l.tdx_eres2net_destroy, blob=pack_blob(state_dict))
+        self.device, self._h, self._guard = self._own.device, self._own.ptr, self._own.guard
         self._graphs = _lib.GraphRunner(self.device)
         self.fbank = Fbank("sv", self.device)
 
@@ -61,31 +50,19 @@ class ERes2NetV2:
             wav = wav[None]
         return self.embed_features(self.fbank(wav))
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._l.tdx_eres2net_destroy(self._h); self._h = None
-        except Exception:
-            pass
+    def close(self):
+        self._own.close()
+        self.fbank.close()
 
 
 class CAMPPlus:
     """CAM++ (csrc/campplus.hip): the same front end and surface as ERes2NetV2; state_dict with 3D-Speaker's names."""
 
     def __init__(self, state_dict, device="cuda:0"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.TdxError("CAMPPlus needs a HIP device")
         self._l = _lib.lib()
-        blob = pack_blob(drop_num_batches_tracked(state_dict))
-        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        h = C.c_void_p()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        with torch.cuda.device(idx):
-            _lib.check(self._l.tdx_campp_create(buf, len(blob), idx, C.byref(h)))
-        self._h = h
-        self._guard = _lib.HandleGuard(self.device)      # calls on this object are serialised (host lock + device event chain)
+        self._own = _lib.Handle(device, "CAMPPlus", self._l.tdx_campp_create, self._l.tdx_campp_destroy,
+                                blob=pack_blob(drop_num_batches_tracked(state_dict)))
+        self.device, self._h, self._guard = self._own.device, self._own.ptr, self._own.guard
         self.fbank = Fbank("sv", self.device)
 
     def flops(self, B, F):
@@ -111,12 +88,9 @@ class CAMPPlus:
             wav = wav[None]
         return self.embed_features(self.fbank(wav))
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._l.tdx_campp_destroy(self._h); self._h = None
-        except Exception:
-            pass
+    def close(self):
+        self._own.close()
+        self.fbank.close()
 
 
 class SpeakerEmbedder:

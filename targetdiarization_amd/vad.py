@@ -8,7 +8,6 @@ drives it: one whole clip, detect_mode 1, is_final.  Its decibel / SNR gates are
 thresholds, with the 1e-6 floor in the frame energy, they cannot fire for audio in [-1, 1]."""
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Sequence
 
@@ -125,19 +124,9 @@ class FsmnVad:
     prefix); cmvn = (shift[400], scale[400]) of am.mvn, None = identity."""
 
     def __init__(self, state_dict, cmvn=None, device="cuda:0"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.TdxError("FsmnVad needs a HIP device")
         self._l = _lib.lib()
-        blob = pack_fsmn_vad_blob(state_dict, cmvn)
-        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        h = C.c_void_p()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        with torch.cuda.device(idx):
-            _lib.check(self._l.tdx_fsmnvad_create(buf, len(blob), idx, C.byref(h)))
-        self._h = h
-        self._guard = _lib.HandleGuard(self.device)      # calls on this object are serialised (host lock + device event chain)
+        self._own = _lib.Handle(device, "FsmnVad", self._l.tdx_fsmnvad_create, self._l.tdx_fsmnvad_destroy, blob=pack_fsmn_vad_blob(state_dict, cmvn))
+        self.device, self._h, self._guard = self._own.device, self._own.ptr, self._own.guard
         self.fbank = Fbank("asr", self.device)
 
     def flops(self, rows: int) -> float:
@@ -210,12 +199,9 @@ class FsmnVad:
     def __call__(self, audio, min_silence_sec: float = 0.5):
         return self.detect_batch([audio], min_silence_sec)[0]
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._l.tdx_fsmnvad_destroy(self._h); self._h = None
-        except Exception:
-            pass
+    def close(self):
+        self._own.close()
+        self.fbank.close()
 
 
 def build_vad(vad_state_dict=None, vad_cmvn=None, vad_model_dir=None, cuda_device: int = 0):
