@@ -349,6 +349,32 @@ double tdx_fsmnvad_flops(const tdx_fsmnvad* h, int rows);
 int tdx_fsmnvad_forward(tdx_fsmnvad* h, const float* feat_dev, const int32_t* starts_dev, int nclips, int rows,
                         float* p0_dev, float* post_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * N6   PyanNet speaker segmentation — the network inside `self.od_pipeline` (pyannote speaker-diarization-3.1,
+ *      TargetDiarization.py:84,132,143; pyannote segmentation-3.0, third-party; parity unpinned [upstream-recall]):
+ *      InstanceNorm1d(1) on the waveform, SincNet (80 sinc filters of 251 taps at stride 10, two k5 convolutions, each
+ *      stage abs/-, MaxPool3, InstanceNorm1d, leaky_relu), a 4-layer bidirectional LSTM of 128 units, linears 256->128->128
+ *      with leaky_relu, a 7-class classifier and log-softmax.  The classes are the powerset of at most 2 of 3 local
+ *      speakers: {}, {0}, {1}, {2}, {0,1}, {0,2}, {1,2}.  Chunking, clustering and track building run on the host
+ *      (targetdiarization_amd/overlap.py).
+ *      blob: TDXW container with pyannote's state-dict names (sincnet.*, lstm.*, linear.*, classifier.*; without the
+ *      derived filterbank.n_ / window_ buffers); strict both ways like the other models.
+ *      wav_dev [B,T]: 16 kHz chunks, 1261 <= T <= 160000 and 1 <= B <= 1024 (frames / workspace_bytes return 0 outside);
+ *      logp_dev [B,F,7] with F = tdx_pyannet_frames(T) (one frame per 270 samples, receptive field 991);
+ *      tap_sincnet [B,F,60] and tap_lstm [B,F,256] are NULL or receive the SincNet and the LSTM output.
+ *      A chunk's result does not depend on the other chunks of the batch.  22 launches per call whatever B and T;
+ *      the recurrence is one launch per LSTM layer.
+ * ---------------------------------------------------------------------------------- */
+typedef struct tdx_pyannet tdx_pyannet;
+int tdx_pyannet_create(const void* weights_blob, size_t blob_bytes, int device, tdx_pyannet** out);
+int tdx_pyannet_destroy(tdx_pyannet* h);
+int tdx_pyannet_frames(int T);
+int tdx_pyannet_chunk_tile(void);      /* chunks one workgroup of the recurrence kernel walks (a launch has ceil(B / tile) x 2 workgroups) */
+size_t tdx_pyannet_workspace_bytes(const tdx_pyannet* h, int B, int T);
+double tdx_pyannet_flops(const tdx_pyannet* h, int B, int T);
+int tdx_pyannet_forward(tdx_pyannet* h, const float* wav_dev, int B, int T, float* logp_dev, float* tap_sincnet,
+                        float* tap_lstm, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,13 @@ SIGNATURES = {
     "tdx_fsmnvad_workspace_bytes": (_sz, [_vp, _i]),
     "tdx_fsmnvad_flops": (C.c_double, [_vp, _i]),
     "tdx_fsmnvad_forward": (_i, [_vp, _fp, _vp, _i, _i, _fp, _fp, _vp, _sz, _vp]),
+    "tdx_pyannet_create": (_i, [_vp, _sz, _i, C.POINTER(_vp)]),
+    "tdx_pyannet_destroy": (_i, [_vp]),
+    "tdx_pyannet_frames": (_i, [_i]),
+    "tdx_pyannet_chunk_tile": (_i, []),
+    "tdx_pyannet_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "tdx_pyannet_flops": (C.c_double, [_vp, _i, _i]),
+    "tdx_pyannet_forward": (_i, [_vp, _fp, _i, _i, _fp, _fp, _fp, _vp, _sz, _vp]),
 }
 
 

@@ -669,3 +669,62 @@ def parse_kaldi_cmvn(path: str):
     if out[0].shape != out[1].shape:
         raise ValueError(f"{path}: <AddShift> and <Rescale> differ in length")
     return out[0], out[1]
+
+
+# ---------------------------------------------------------------------------------------
+# PyanNet (pyannote.audio models/segmentation/PyanNet.py, the segmentation-3.0 configuration: SincNet stride 10, a 4-layer
+# bidirectional LSTM of 128 units, linears 128/128, 7 powerset classes)
+# [upstream-recall]: the source is not vendored and no checkpoint is at hand, parity is unpinned; tests/pyannet_oracle.py
+# restates the forward and csrc/pyannet.hip loads exactly these names (strict both ways).
+# ---------------------------------------------------------------------------------------
+def pyannet_param_shapes(hidden: int = 128, layers: int = 4, classes: int = 7) -> "OrderedDict[str, tuple]":
+    s = OrderedDict()
+    s["sincnet.wav_norm1d.weight"] = (1,); s["sincnet.wav_norm1d.bias"] = (1,)
+    s["sincnet.conv1d.0.filterbank.low_hz_"] = (40, 1); s["sincnet.conv1d.0.filterbank.band_hz_"] = (40, 1)
+    s["sincnet.conv1d.1.weight"] = (60, 80, 5); s["sincnet.conv1d.1.bias"] = (60,)
+    s["sincnet.conv1d.2.weight"] = (60, 60, 5); s["sincnet.conv1d.2.bias"] = (60,)
+    for i, c in enumerate((80, 60, 60)):
+        s[f"sincnet.norm1d.{i}.weight"] = (c,); s[f"sincnet.norm1d.{i}.bias"] = (c,)
+    for l in range(layers):
+        for sfx in ("", "_reverse"):
+            s[f"lstm.weight_ih_l{l}{sfx}"] = (4 * hidden, 60 if l == 0 else 2 * hidden)
+            s[f"lstm.weight_hh_l{l}{sfx}"] = (4 * hidden, hidden)
+            s[f"lstm.bias_ih_l{l}{sfx}"] = (4 * hidden,); s[f"lstm.bias_hh_l{l}{sfx}"] = (4 * hidden,)
+    s["linear.0.weight"] = (hidden, 2 * hidden); s["linear.0.bias"] = (hidden,)
+    s["linear.1.weight"] = (hidden, hidden); s["linear.1.bias"] = (hidden,)
+    s["classifier.weight"] = (classes, hidden); s["classifier.bias"] = (classes,)
+    return s
+
+
+def recipe_pyannet_state_dict(seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Deterministic fp32 weights for the PyanNet layout (Philox keyed by the tensor name).  The sinc band edges are
+    asteroid's mel-spaced initialisation (30 Hz .. 7900 Hz).  torch's default 1/sqrt(hidden) scale makes this network almost
+    ignore its input (logit standard deviation ~1e-3 over a clip), so the matrices are fan-in scaled with gains that keep the
+    signal alive through the stack: 3 on the LSTM's input matrices, 1.5 on the recurrent ones, 2 before a leaky_relu, 4 on
+    the classifier.  tests/golden/pyannet_calibration.json holds the classifier gain and bias that do the rest."""
+    out = OrderedDict()
+    mel = np.linspace(2595.0 * np.log10(1.0 + 30.0 / 700.0), 2595.0 * np.log10(1.0 + 7900.0 / 700.0), 41)
+    hz = 700.0 * (10.0 ** (mel / 2595.0) - 1.0)
+    for name, shape in pyannet_param_shapes().items():
+        n = int(np.prod(shape))
+        u = torch.from_numpy(philox_uniform("pyannet:" + name, n, seed)).reshape(shape)
+        if name.endswith("low_hz_"):
+            t = torch.from_numpy(hz[:-1]).reshape(shape)
+        elif name.endswith("band_hz_"):
+            t = torch.from_numpy(np.diff(hz)).reshape(shape)
+        elif "norm1d" in name:
+            t = (1.0 + 0.2 * u) if name.endswith("weight") else 0.1 * u
+        elif "bias" in name:
+            t = 0.1 * u
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            gain = 3.0 if "weight_ih" in name else 1.5 if "weight_hh" in name else 4.0 if name.startswith("classifier") else 2.0
+            t = u * float(np.sqrt(3.0 * gain / fan_in))
+        out[name] = t.to(torch.float32).contiguous()
+    return out
+
+
+def pack_pyannet_blob(state_dict) -> bytes:
+    """The TDXW blob tdx_pyannet_create reads: pyannote's names; the filterbank's derived buffers (n_, window_), which a
+    checkpoint carries next to low_hz_ / band_hz_, are dropped (the device rebuilds the filters in fp64)"""
+    return pack_blob(OrderedDict((k, v) for k, v in state_dict.items() if not k.endswith(("filterbank.n_", "filterbank.window_"))))
