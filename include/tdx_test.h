@@ -31,6 +31,11 @@ int tdx_h3_gemm_variant(const void* pa, const float* sa, const void* pb, const f
                         float* c_dev, int M, int N, int K, int variant, void* stream);
 /* timing variants of the fp32-MFMA core (gemm.hpp VARIANT) and the x6 core (variant 6) */
 int tdx_linear_variant(const float* a_dev, const float* w_dev, int M, int N, int K, float* c_dev, int variant, void* stream);
+/* the shared epilogue family (csrc/epilogues.hpp) on the fp32-MFMA core: out[M][Npad] = act((a[M][K] w[Npad][K]^T + bias) + res),
+ * columns >= nreal left untouched.  bias_or_null, res_or_null may be NULL; res may be out.  Picks EpiBiasAct / EpiBiasActN /
+ * EpiBiasRes(N) from the arguments.  act: 0 none, 1 relu, 2 relu20, 3 silu, 4 leaky_relu(0.01).  Npad % 128 == 0, K % 32 == 0. */
+int tdx_linear_epi(const float* a_dev, const float* w_dev, const float* bias_or_null, const float* res_or_null, float* out_dev,
+                   int M, int Npad, int nreal, int K, int act, void* stream);
 
 /* per-CU operand fill rates (tools/fill_bench*.py) */
 int tdx_fill_bench(int mode, const void* src_dev, long bytes_per_block, int blocks, int iters, float* sink_dev, void* stream);

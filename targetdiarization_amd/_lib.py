@@ -145,6 +145,7 @@ DIAG_SIGNATURES = {
     "tdx_h3_gemm": (_i, [_vp] * 6 + [_i] * 3 + [_vp]),
     "tdx_h3_gemm_variant": (_i, [_vp] * 6 + [_i] * 4 + [_vp]),
     "tdx_linear_variant": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "tdx_linear_epi": (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
     "tdx_fill_bench": (_i, [_i, _vp, _l, _i, _i, _vp, _vp]),
     "tdx_fill_bench2": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
     "tdx_fill_bench3": (_i, [_vp, _l, _i, _l, _i, _i, _i, _vp, _vp]),

@@ -17,9 +17,7 @@
 #include <vector>
 
 #include "../../include/tdx.h"
-#include "gemm.hpp"
-#include "devutil.hpp"
-#include "tdx_common.hpp"
+#include "epilogues.hpp"
 
 using namespace tdx;
 
@@ -137,8 +135,7 @@ __global__ __launch_bounds__(256) void ap_attn_kernel(const float* __restrict__ 
         for (int i = w; i < NB; i += 4) {
             const float a = p[i][lane], b = lane < NB - 64 ? p[i][64 + lane] : -INFINITY;
             float mx = fmaxf(a, b);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+            mx = wave_max(mx);
             const float ea = expf(a - mx), eb = lane < NB - 64 ? expf(b - mx) : 0.f;
             const float inv = 1.0f / wave_sum(ea + eb);
             p[i][lane] = ea * inv;
@@ -219,10 +216,6 @@ __global__ __launch_bounds__(256) void ap_ola_kernel(const float* __restrict__ F
 }
 
 // ---- GEMM epilogues ----
-struct EpiStore { float* out;                                          // out = v
-    __device__ EpiNone col(int, int) const { return EpiNone{}; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, EpiNone) const { out[(long)m * KP + n] = v; } };
 struct EpiRow { const float* r; float* out; int ld;                    // out = v * r[m]          (RMSNorm rsqrt of the row)
     __device__ EpiNone col(int, int) const { return EpiNone{}; }
     __device__ float row(int, int m) const { return r[m]; }
@@ -242,20 +235,6 @@ struct EpiRowBiasSilu { const float* r; const float* b; float* out;     // out =
         const float a = fmaf(v, rw, c);
         out[(long)m * (4 * AD) + n] = a / (1.0f + expf(-a));
     } };
-struct EpiRes { const float* b; float* x;                              // x += v (+ b[n])
-    __device__ float col(int, int n) const { return b ? b[n] : 0.f; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ float aux(int, int m, int n, EpiNone) const { return x[(long)m * AD + n]; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c, float a) const { x[(long)m * AD + n] = a + (v + c); } };
-
-template <bool PAIRED, class Epi>
-int lin(const float* A, long lda, const float* W, int M, int N, int K, Epi e, hipStream_t st, int pair_off = 0) {
-    GemmArgs g = make_args(M, N, make_seg(A, lda, W, K, K));
-    g.pair_off = pair_off;
-    if (launch_gemm<false, false, PAIRED, false>(g, 1, e, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
-    return TDX_OK;
-}
-
 struct AIcb { size_t w7, b7, Wa, ba, Wb, bb; };
 struct ALayer { size_t cosT, sinT, Wqkv, Wo, W1, W2; AIcb icb[3]; };
 
@@ -425,30 +404,30 @@ int tdx_apollo_forward(tdx_apollo* h, const float* x, const int64_t* lens, int n
 
     hipLaunchKernelGGL(ap_frames_kernel, dim3(F), dim3(256), 0, st, x, it, fr, finfo);
     LAUNCH_CHECK();
-    TRY(lin<false>(fr, KP, d + h->bana, F, KP, KP, EpiStore{S}, st));
+    TRY(linear_f32(fr, KP, d + h->bana, F, KP, KP, EpiStoreZ{S, KP, 0}, st));
     hipLaunchKernelGGL(ap_band_in_kernel, dim3(F), dim3(256), 0, st, S, d + h->Wt, d + h->bin, X);
     LAUNCH_CHECK();
     for (const ALayer& w : h->layers) {
         hipLaunchKernelGGL(ap_rms_kernel, dim3(rows4), dim3(256), 0, st, X, r, R);
         LAUNCH_CHECK();
-        TRY(lin<false>(X, AD, d + w.Wqkv, (int)R, 3 * AD, AD, EpiRow{r, U, 3 * AD}, st));
+        TRY(linear_f32(X, AD, d + w.Wqkv, (int)R, 3 * AD, AD, EpiRow{r, U, 3 * AD}, st));
         hipLaunchKernelGGL(ap_attn_kernel, dim3(F, 8), dim3(256), 0, st, U, d + w.cosT, d + w.sinT, Y);
         LAUNCH_CHECK();
-        TRY(lin<false>(Y, AD, d + w.Wo, (int)R, AD, AD, EpiRes{nullptr, X}, st));
+        TRY(linear_f32(Y, AD, d + w.Wo, (int)R, AD, AD, EpiBiasRes<>{nullptr, X, X, AD}, st));
         hipLaunchKernelGGL(ap_rms_kernel, dim3(rows4), dim3(256), 0, st, X, r, R);
         LAUNCH_CHECK();
-        TRY(lin<true>(X, AD, d + w.W1, (int)R, 4 * AD, AD, EpiGate{r, U}, st, 4 * AD));
-        TRY(lin<false>(U, 4 * AD, d + w.W2, (int)R, AD, 4 * AD, EpiRes{nullptr, X}, st));
+        TRY(linear_f32<true>(X, AD, d + w.W1, (int)R, 4 * AD, AD, EpiGate{r, U}, st, 0, 4 * AD));
+        TRY(linear_f32(U, 4 * AD, d + w.W2, (int)R, AD, 4 * AD, EpiBiasRes<>{nullptr, X, X, AD}, st));
         for (const AIcb& c : w.icb) {
             hipLaunchKernelGGL(ap_conv7_kernel, dim3(rows4), dim3(256), 0, st, X, d + c.w7, d + c.b7, finfo, Y, r, R);
             LAUNCH_CHECK();
-            TRY(lin<false>(Y, AD, d + c.Wa, (int)R, 4 * AD, AD, EpiRowBiasSilu{r, d + c.ba, U}, st));
-            TRY(lin<false>(U, 4 * AD, d + c.Wb, (int)R, AD, 4 * AD, EpiRes{d + c.bb, X}, st));
+            TRY(linear_f32(Y, AD, d + c.Wa, (int)R, 4 * AD, AD, EpiRowBiasSilu{r, d + c.ba, U}, st));
+            TRY(linear_f32(U, 4 * AD, d + c.Wb, (int)R, AD, 4 * AD, EpiBiasRes<>{d + c.bb, X, X, AD}, st));
         }
     }
     hipLaunchKernelGGL(ap_head_kernel, dim3(F), dim3(256), 0, st, X, d + h->Wh, d + h->bh, fr);
     LAUNCH_CHECK();
-    TRY(lin<false>(fr, KP, d + h->bsyn, F, KP, KP, EpiStore{S}, st));
+    TRY(linear_f32(fr, KP, d + h->bsyn, F, KP, KP, EpiStoreZ{S, KP, 0}, st));
     hipLaunchKernelGGL(ap_ola_kernel, dim3((span + 255) / 256, nitems), dim3(256), 0, st, S, it, d + h->w2, y);
     LAUNCH_CHECK();
     return TDX_OK;

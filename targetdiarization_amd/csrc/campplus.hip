@@ -24,9 +24,7 @@
 #include <vector>
 
 #include "../../include/tdx.h"
-#include "gemm.hpp"
-#include "devutil.hpp"
-#include "tdx_common.hpp"
+#include "epilogues.hpp"
 
 using namespace tdx;
 
@@ -198,21 +196,6 @@ __global__ __launch_bounds__(256) void dense_kernel(const float* __restrict__ st
 }
 
 // ---------------------------------------------------------------- epilogues
-struct EpiBias {        // v + b (optionally ReLU), columns < nreal
-    const float* b; float* out; long ld; int nreal; int relu;
-    __device__ float col(int, int n) const { return b ? b[n] : 0.f; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const {
-        if (n < nreal) out[(long)m * ld + n] = relu ? fmaxf(v + c, 0.f) : v + c;
-    }
-};
-struct EpiResRelu {     // relu(v + b + residual), columns < nreal; residual and output share the pitch
-    const float* b; const float* res; float* out; long ld; int nreal;
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ float aux(int, int m, int n, EpiNone) const { return n < nreal ? res[(long)m * ld + n] : 0.f; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c, float r) const { if (n < nreal) out[(long)m * ld + n] = fmaxf(v + c + r, 0.f); }
-};
 struct EpiHeadOut {     // head.conv2: row (b, f, t) of [B, Hf, T], channel n -> out[(b*T + t)*(Hf*32) + f*32 + n], relu(v + b)
     const float* b; float* out; int Hf, T;
     __device__ float col(int, int n) const { return b[n]; }
@@ -240,10 +223,7 @@ int head_conv(const float* A, const float* dev, const ConvW& cw, int B, int Hin,
 }
 template <class Epi>
 int plain_gemm(const float* A, long lda, const float* dev, const ConvW& cw, long M, Epi e, hipStream_t st) {
-    GemmArgs g = make_args((int)M, cw.Npad, make_seg(A, lda, dev + cw.w, cw.cinp, cw.cinp));
-    g.n_valid = up(cw.N, 32);
-    if (launch_gemm<false, false, false, false>(g, 1, e, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
-    return TDX_OK;
+    return linear_f32(A, lda, dev + cw.w, (int)M, cw.Npad, cw.cinp, e, st, up(cw.N, 32));
 }
 
 }  // namespace
@@ -436,19 +416,19 @@ int tdx_campp_forward(tdx_campp* h, const float* feat, int B, int F, float* emb,
     hipLaunchKernelGGL(stem_kernel, dim3((unsigned)((rows0 * 8 + 255) / 256)), dim3(256), 0, st, feat, dev + h->stem_w, dev + h->stem_b, P[0], F, rows0);
     LAUNCH_CHECK();
     // layer1.0 (80 -> 40): x = P0
-    TRY(head_conv(P[0], dev, h->l_c1[0], B, 80, 40, T, 2, EpiBias{dev + h->l_c1[0].b, P[1], HC, HC, 1}, st));
-    TRY(head_conv(P[0], dev, h->l_sc[0], B, 80, 40, T, 2, EpiBias{dev + h->l_sc[0].b, P[2], HC, HC, 0}, st));
-    TRY(head_conv(P[1], dev, h->l_c2[0], B, 40, 40, T, 1, EpiResRelu{dev + h->l_c2[0].b, P[2], P[3], HC, HC}, st));
+    TRY(head_conv(P[0], dev, h->l_c1[0], B, 80, 40, T, 2, EpiBiasActN<ActRelu>{dev + h->l_c1[0].b, P[1], HC, HC}, st));
+    TRY(head_conv(P[0], dev, h->l_sc[0], B, 80, 40, T, 2, EpiBiasActN<>{dev + h->l_sc[0].b, P[2], HC, HC}, st));
+    TRY(head_conv(P[1], dev, h->l_c2[0], B, 40, 40, T, 1, EpiBiasResN<ActRelu>{dev + h->l_c2[0].b, P[2], P[3], HC, HC}, st));
     // layer1.1: x = P3
-    TRY(head_conv(P[3], dev, h->l_c1[1], B, 40, 40, T, 1, EpiBias{dev + h->l_c1[1].b, P[1], HC, HC, 1}, st));
-    TRY(head_conv(P[1], dev, h->l_c2[1], B, 40, 40, T, 1, EpiResRelu{dev + h->l_c2[1].b, P[3], P[2], HC, HC}, st));
+    TRY(head_conv(P[3], dev, h->l_c1[1], B, 40, 40, T, 1, EpiBiasActN<ActRelu>{dev + h->l_c1[1].b, P[1], HC, HC}, st));
+    TRY(head_conv(P[1], dev, h->l_c2[1], B, 40, 40, T, 1, EpiBiasResN<ActRelu>{dev + h->l_c2[1].b, P[3], P[2], HC, HC}, st));
     // layer2.0 (40 -> 20): x = P2
-    TRY(head_conv(P[2], dev, h->l_c1[2], B, 40, 20, T, 2, EpiBias{dev + h->l_c1[2].b, P[1], HC, HC, 1}, st));
-    TRY(head_conv(P[2], dev, h->l_sc[1], B, 40, 20, T, 2, EpiBias{dev + h->l_sc[1].b, P[3], HC, HC, 0}, st));
-    TRY(head_conv(P[1], dev, h->l_c2[2], B, 20, 20, T, 1, EpiResRelu{dev + h->l_c2[2].b, P[3], P[0], HC, HC}, st));
+    TRY(head_conv(P[2], dev, h->l_c1[2], B, 40, 20, T, 2, EpiBiasActN<ActRelu>{dev + h->l_c1[2].b, P[1], HC, HC}, st));
+    TRY(head_conv(P[2], dev, h->l_sc[1], B, 40, 20, T, 2, EpiBiasActN<>{dev + h->l_sc[1].b, P[3], HC, HC}, st));
+    TRY(head_conv(P[1], dev, h->l_c2[2], B, 20, 20, T, 1, EpiBiasResN<ActRelu>{dev + h->l_c2[2].b, P[3], P[0], HC, HC}, st));
     // layer2.1: x = P0
-    TRY(head_conv(P[0], dev, h->l_c1[3], B, 20, 20, T, 1, EpiBias{dev + h->l_c1[3].b, P[1], HC, HC, 1}, st));
-    TRY(head_conv(P[1], dev, h->l_c2[3], B, 20, 20, T, 1, EpiResRelu{dev + h->l_c2[3].b, P[0], P[2], HC, HC}, st));
+    TRY(head_conv(P[0], dev, h->l_c1[3], B, 20, 20, T, 1, EpiBiasActN<ActRelu>{dev + h->l_c1[3].b, P[1], HC, HC}, st));
+    TRY(head_conv(P[1], dev, h->l_c2[3], B, 20, 20, T, 1, EpiBiasResN<ActRelu>{dev + h->l_c2[3].b, P[0], P[2], HC, HC}, st));
     // head.conv2 (20 -> 10) -> x320 [B*T][f*32 + c]
     TRY(head_conv(P[2], dev, h->head2, B, 20, 10, T, 2, EpiHeadOut{dev + h->head2.b, x320, 10, T}, st));
 
@@ -457,7 +437,7 @@ int tdx_campp_forward(tdx_campp* h, const float* feat, int B, int F, float* emb,
         const long total4 = M * 400;
         hipLaunchKernelGGL(tdnn_gather_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, x320, im, T, Tp, total4);
         LAUNCH_CHECK();
-        TRY(plain_gemm(im, 1600, dev, h->tdnn, M, EpiBias{dev + h->tdnn.b, xb[0], (long)kLd[0], BNC, 1}, st));
+        TRY(plain_gemm(im, 1600, dev, h->tdnn, M, EpiBiasActN<ActRelu>{dev + h->tdnn.b, xb[0], kLd[0], BNC}, st));
     }
     // ---- dense blocks
     size_t li = 0;
@@ -468,7 +448,7 @@ int tdx_campp_forward(tdx_campp* h, const float* feat, int B, int F, float* emb,
             const LayerW& L = h->layers[li];
             hipLaunchKernelGGL(bnrelu_kernel, dim3((unsigned)((M * (L.cin / 4) + 255) / 256)), dim3(256), 0, st, x, dev + L.s1, dev + L.sh1, xa, M, L.cin, ld);
             LAUNCH_CHECK();
-            TRY(plain_gemm(xa, ld, dev, L.lin1, M, EpiBias{dev + L.lin1.b, hb, (long)BNC, BNC, 1}, st));
+            TRY(plain_gemm(xa, ld, dev, L.lin1, M, EpiBiasActN<ActRelu>{dev + L.lin1.b, hb, BNC, BNC}, st));
             hipLaunchKernelGGL(cam_mask_kernel, dim3(B), dim3(128), 0, st, hb, dev + L.cw1, dev + L.cb1, dev + L.cw2, dev + L.cb2, mask, Tp, nseg);
             LAUNCH_CHECK();
             hipLaunchKernelGGL(cam_local_kernel, dim3((unsigned)((M + 127) / 128)), dim3(256), 0, st, hb, dev + L.wl, mask, x, ld, L.cin, M, Tp, nseg, kDil[bi]);
@@ -477,8 +457,8 @@ int tdx_campp_forward(tdx_campp* h, const float* feat, int B, int F, float* emb,
         const TransW& t = h->trans[bi];
         hipLaunchKernelGGL(bnrelu_kernel, dim3((unsigned)((M * (t.cin / 4) + 255) / 256)), dim3(256), 0, st, x, dev + t.s, dev + t.sh, xa, M, t.cin, ld);
         LAUNCH_CHECK();
-        if (bi + 1 < NBLOCK) TRY(plain_gemm(xa, ld, dev, t.lin, M, EpiBias{nullptr, xb[bi + 1], (long)kLd[bi + 1], t.cin / 2, 0}, st));
-        else TRY(plain_gemm(xa, ld, dev, t.lin, M, EpiBias{dev + t.lin.b, xb[0], 512L, 512, 1}, st));      // out_nonlinear -> xb[0] as [M][512]
+        if (bi + 1 < NBLOCK) TRY(plain_gemm(xa, ld, dev, t.lin, M, EpiBiasActN<>{nullptr, xb[bi + 1], kLd[bi + 1], t.cin / 2}, st));
+        else TRY(plain_gemm(xa, ld, dev, t.lin, M, EpiBiasActN<ActRelu>{dev + t.lin.b, xb[0], 512, 512}, st));      // out_nonlinear -> xb[0] as [M][512]
     }
     // ---- statistics pooling + dense
     hipLaunchKernelGGL(stats_kernel, dim3(2, B), dim3(256), 0, st, xb[0], stats, Tp, 512);

@@ -41,8 +41,12 @@ __device__ __forceinline__ float h3_wave_sum(float v) {
     return (h3_lane(v, 0) + h3_lane(v, 16)) + (h3_lane(v, 32) + h3_lane(v, 48));
 }
 
-// sum over the 64 lanes of a (fully active) wave, the same value in every lane
+// sum / max over the 64 lanes of a (fully active) wave, the same value in every lane
 __device__ __forceinline__ float wave_sum(float v) { return h3_wave_sum(v); }
+__device__ __forceinline__ float wave_max(float v) {
+    v = h3_row16_max(v);
+    return fmaxf(fmaxf(h3_lane(v, 0), h3_lane(v, 16)), fmaxf(h3_lane(v, 32), h3_lane(v, 48)));
+}
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -55,5 +59,9 @@ __device__ __forceinline__ float sigmoidf_acc(float x) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
 }
 __device__ __forceinline__ float siluf_acc(float x) { return x * sigmoidf_acc(x); }
+__device__ __forceinline__ float relu20(float v) { return fminf(fmaxf(v, 0.f), 20.f); }
+__device__ __forceinline__ float leaky(float v, float slope) { return v >= 0.f ? v : slope * v; }
+
+struct Col2 { float a, b; };      // two per-column constants of a GEMM epilogue (gain and bias, scale and shift ...)
 
 }  // namespace tdx

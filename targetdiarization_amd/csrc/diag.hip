@@ -7,27 +7,18 @@
 
 #include "../../include/tdx.h"
 #include "../../include/tdx_test.h"
-#include "gemm.hpp"
-#include "gemm_x6.hpp"
-#include "gemm_h3.hpp"
-#include "tdx_common.hpp"
+#include "epilogues.hpp"
 
 using namespace tdx;
 
 namespace {
-struct EpiStore {    // plain store, per-batch stride
-    float* out; long ld; long strideZ;
-    __device__ EpiNone col(int, int) const { return EpiNone{}; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int z, int m, int n, float v, EpiNone, EpiNone) const { out[(long)z * strideZ + (long)m * (int)ld + n] = v; }
-};
-struct EpiBias { const float* b; float* out; long ld;   // b may be null
-    __device__ float col(int, int n) const { return b ? b[n] : 0.f; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const { out[(long)m * (int)ld + n] = v + c; }
-    __device__ float* ptr(int, int m, int n) const { return out + (long)m * (int)ld + n; }
-    __device__ long ldm() const { return ld; }
-    __device__ void put(float* p, float v, EpiNone, float c) const { *p = v + c; } };
+template <class Act>
+int linear_epi(const float* a, const float* w, const float* bias, const float* res, float* out, int M, int Npad, int nreal, int K, hipStream_t st) {
+    if (res && nreal < Npad) return linear_f32(a, K, w, M, Npad, K, EpiBiasResN<Act>{bias, res, out, Npad, nreal}, st);
+    if (res) return linear_f32(a, K, w, M, Npad, K, EpiBiasRes<Act>{bias, res, out, Npad}, st);
+    if (nreal < Npad) return linear_f32(a, K, w, M, Npad, K, EpiBiasActN<Act>{bias, out, Npad, nreal}, st);
+    return linear_f32(a, K, w, M, Npad, K, EpiBiasAct<Act>{bias, out, Npad}, st);
+}
 }  // namespace
 
 extern "C" {
@@ -37,15 +28,31 @@ const char* tdx_diag_last_error(void) { return tdx::last_error().c_str(); }
 // timing-only diagnostic: see gemm.hpp VARIANT
 int tdx_linear_variant(const float* a, const float* w, int M, int N, int K, float* c, int variant, void* stream) {
     GemmArgs g = make_args(M, N, make_seg(a, K, w, K, K));
-    EpiStore e{c, (long)N, 0};
+    EpiStoreZ e{c, (long)N, 0};
     hipError_t r;
-    if (variant == 1) r = launch_gemm<false, false, false, false, EpiStore, 1>(g, 1, e, (hipStream_t)stream);
-    else if (variant == 2) r = launch_gemm<false, false, false, false, EpiStore, 2>(g, 1, e, (hipStream_t)stream);
-    else if (variant == 3) r = launch_gemm<false, false, false, false, EpiStore, 3>(g, 1, e, (hipStream_t)stream);
-    else if (variant == 4) r = launch_gemm<false, false, false, false, EpiStore, 4>(g, 1, e, (hipStream_t)stream);
+    if (variant == 1) r = launch_gemm<false, false, false, false, EpiStoreZ, 1>(g, 1, e, (hipStream_t)stream);
+    else if (variant == 2) r = launch_gemm<false, false, false, false, EpiStoreZ, 2>(g, 1, e, (hipStream_t)stream);
+    else if (variant == 3) r = launch_gemm<false, false, false, false, EpiStoreZ, 3>(g, 1, e, (hipStream_t)stream);
+    else if (variant == 4) r = launch_gemm<false, false, false, false, EpiStoreZ, 4>(g, 1, e, (hipStream_t)stream);
     else if (variant == 6) r = launch_gemm_x6<false>(g, e, (hipStream_t)stream);
-    else r = launch_gemm<false, false, false, false, EpiStore, 0>(g, 1, e, (hipStream_t)stream);
+    else r = launch_gemm<false, false, false, false, EpiStoreZ, 0>(g, 1, e, (hipStream_t)stream);
     return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
+}
+
+// the shared epilogue family (epilogues.hpp) on the fp32 core: tests/test_gpu_epilogues.py.  out [M][Npad] =
+// act((a [M][K] x w [Npad][K]^T + bias) + res); bias and res may be null, res may be out; columns >= nreal are left alone.
+// act: 0 none, 1 relu, 2 relu20, 3 silu, 4 leaky(0.01)
+int tdx_linear_epi(const float* a, const float* w, const float* bias, const float* res, float* out, int M, int Npad, int nreal, int K, int act, void* stream) {
+    if (!a || !w || !out || M < 1 || Npad < 128 || Npad % 128 || nreal < 1 || nreal > Npad || K < 32 || K % 32 || act < 0 || act > 4)
+        return tdx::fail(TDX_E_INVALID, "tdx_linear_epi: need Npad%128==0, 1<=nreal<=Npad, K%32==0, act in 0..4");
+    hipStream_t st = (hipStream_t)stream;
+    switch (act) {
+    case 1: return linear_epi<ActRelu>(a, w, bias, res, out, M, Npad, nreal, K, st);
+    case 2: return linear_epi<ActRelu20>(a, w, bias, res, out, M, Npad, nreal, K, st);
+    case 3: return linear_epi<ActSilu>(a, w, bias, res, out, M, Npad, nreal, K, st);
+    case 4: return linear_epi<ActLeaky<1, 100>>(a, w, bias, res, out, M, Npad, nreal, K, st);
+    default: return linear_epi<ActNone>(a, w, bias, res, out, M, Npad, nreal, K, st);
+    }
 }
 
 // diagnostics for the split-f16 x3 core: tests/test_gpu_h3.py, tools/h3_test.py
@@ -71,7 +78,7 @@ int tdx_h3_gemm_x(int mode, const void* pa, const float* sa, const void* pb, con
     if (atr) g.seg[0].sa_mul = 0;
     if (btr) g.seg[0].sb_mul = 0;
     g.nseg = 1; g.M = M; g.N = N;
-    EpiBias e{nullptr, c, N};
+    EpiBiasAct<> e{nullptr, c, N};
     hipError_t r;
     if (atr && btr) r = tdx::launch_gemm_h3x<true, true, false, false>(g, 1, e, (hipStream_t)stream);
     else if (atr) r = tdx::launch_gemm_h3x<true, false, false, false>(g, 1, e, (hipStream_t)stream);
@@ -83,16 +90,16 @@ int tdx_h3_gemm_variant(const void* pa, const float* sa, const void* pb, const f
     tdx::H3Args g{};
     g.seg[0] = tdx::h3_seg(pa, sa, 4L * K, pb, sb, 4L * K, K);
     g.nseg = 1; g.M = M; g.N = N;
-    EpiBias e{bias, c, N};
+    EpiBiasAct<> e{bias, c, N};
     hipError_t r;
-    if (variant == 1) r = tdx::launch_gemm_h3<false, EpiBias, 1>(g, 1, e, (hipStream_t)stream);
-    else if (variant == 2) r = tdx::launch_gemm_h3<false, EpiBias, 2>(g, 1, e, (hipStream_t)stream);
-    else if (variant == 3) r = tdx::launch_gemm_h3<false, EpiBias, 3>(g, 1, e, (hipStream_t)stream);
-    else if (variant == 4) r = tdx::launch_gemm_h3<false, EpiBias, 4>(g, 1, e, (hipStream_t)stream);
-    else if (variant == 9) r = tdx::launch_gemm_h3<false, EpiBias, 9>(g, 1, e, (hipStream_t)stream);
-    else if (variant == 5) r = tdx::launch_gemm_h3<false, EpiBias, 5>(g, 1, e, (hipStream_t)stream);
-    else if (variant == 6) r = tdx::launch_gemm_h3<false, EpiBias, 6>(g, 1, e, (hipStream_t)stream);
-    else r = tdx::launch_gemm_h3<false, EpiBias, 0>(g, 1, e, (hipStream_t)stream);
+    if (variant == 1) r = tdx::launch_gemm_h3<false, EpiBiasAct<>, 1>(g, 1, e, (hipStream_t)stream);
+    else if (variant == 2) r = tdx::launch_gemm_h3<false, EpiBiasAct<>, 2>(g, 1, e, (hipStream_t)stream);
+    else if (variant == 3) r = tdx::launch_gemm_h3<false, EpiBiasAct<>, 3>(g, 1, e, (hipStream_t)stream);
+    else if (variant == 4) r = tdx::launch_gemm_h3<false, EpiBiasAct<>, 4>(g, 1, e, (hipStream_t)stream);
+    else if (variant == 9) r = tdx::launch_gemm_h3<false, EpiBiasAct<>, 9>(g, 1, e, (hipStream_t)stream);
+    else if (variant == 5) r = tdx::launch_gemm_h3<false, EpiBiasAct<>, 5>(g, 1, e, (hipStream_t)stream);
+    else if (variant == 6) r = tdx::launch_gemm_h3<false, EpiBiasAct<>, 6>(g, 1, e, (hipStream_t)stream);
+    else r = tdx::launch_gemm_h3<false, EpiBiasAct<>, 0>(g, 1, e, (hipStream_t)stream);
     return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
 }
 int tdx_h3_gemm(const void* pa, const float* sa, const void* pb, const float* sb, const float* bias, float* c, int M, int N, int K, void* stream) {
@@ -100,7 +107,7 @@ int tdx_h3_gemm(const void* pa, const float* sa, const void* pb, const float* sb
     tdx::H3Args g{};
     g.seg[0] = tdx::h3_seg(pa, sa, 4L * K, pb, sb, 4L * K, K);
     g.nseg = 1; g.M = M; g.N = N;
-    hipError_t r = tdx::launch_gemm_h3<false>(g, 1, EpiBias{bias, c, N}, (hipStream_t)stream);
+    hipError_t r = tdx::launch_gemm_h3<false>(g, 1, EpiBiasAct<>{bias, c, N}, (hipStream_t)stream);
     return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
 }
 

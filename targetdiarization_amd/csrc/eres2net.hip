@@ -18,10 +18,7 @@
 #include <vector>
 
 #include "../../include/tdx.h"
-#include "gemm.hpp"
-#include "gemm_h3.hpp"
-#include "devutil.hpp"
-#include "tdx_common.hpp"
+#include "epilogues.hpp"
 #include "weight_planes.hpp"
 
 using namespace tdx;
@@ -32,10 +29,6 @@ constexpr int NSTAGE = 4, SCALE = 4, EMB = 192;
 const int kBlocks[NSTAGE] = {3, 4, 6, 3};
 const int kPlanes[NSTAGE] = {64, 128, 256, 512};
 const int kStride[NSTAGE] = {1, 2, 2, 2};
-
-
-
-__device__ __forceinline__ float relu20(float v) { return fminf(fmaxf(v, 0.f), 20.f); }
 
 // stem: conv3x3(1->64, pad 1) + BN + ReLU on x[b, h=freq, w=time] = feat[b, w, h]
 __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ feat, const float* __restrict__ w9,   // [9][64]
@@ -94,24 +87,6 @@ __global__ __launch_bounds__(256) void seg_kernel(const float* __restrict__ stat
 }
 
 // ---------------------------------------------------------------- epilogues
-struct EpiRelu20 {      // clamp(v + b, 0, 20), columns < nreal
-    const float* b; float* out; long ld; int nreal;
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const { if (n < nreal) out[(long)m * (int)ld + n] = relu20(v + c); }
-};
-struct EpiBiasG {       // v + b, columns < nreal
-    const float* b; float* out; long ld; int nreal;
-    __device__ float col(int, int n) const { return b ? b[n] : 0.f; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const { if (n < nreal) out[(long)m * (int)ld + n] = v + c; }
-};
-struct EpiSlabZ {        // split over the taps: partial sums of batch z -> slab[z][m][n]
-    float* slab; long ld; long strideZ;
-    __device__ EpiNone col(int, int) const { return EpiNone{}; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int z, int m, int n, float v, EpiNone, EpiNone) const { slab[(long)z * strideZ + (long)m * (int)ld + n] = v; }
-};
 // out[m][n] = sum_z slab[z][m][n] (+ bias[n])
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slab, int nz, long MN, int N, const float* __restrict__ bias, float* __restrict__ out) {
     const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
@@ -136,19 +111,6 @@ struct EpiChain {       // Res2Net chain: sp = relu20(v+b) -> cat[:, coff+n]; ne
         if (n < width) cat[(long)m * (int)ldcat + coff + n] = sp;
         if (spin) spin[(long)m * wpad + n] = n < width ? sp + nxt : 0.f;
     }
-};
-struct EpiConv3 {       // relu20(v + b + residual)
-    const float* b; const float* res; float* out; long ld;
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ float aux(int, int m, int n, EpiNone) const { return res[(long)m * (int)ld + n]; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c, float r) const { out[(long)m * (int)ld + n] = relu20(v + c + r); }
-};
-struct EpiAffSilu {     // t = silu(v + b), columns < ipad
-    const float* b; float* t; int ipad;
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const { if (n < ipad) t[(long)m * ipad + n] = siluf_acc(v + c); }
 };
 struct EpiAffGate {     // att = 1 + tanh(v+b); out = x*att + y*(2-att), columns < C
     const float* b; const float* x; long ldx; const float* y; long ldy; float* out; long ldo; int C;
@@ -579,7 +541,7 @@ inline int conv_gemm_h3_tapsplit(const unsigned char* Ap, const float* inv_scale
     g.cv_Hin = Hin; g.cv_Win = Win; g.cv_Hout = Hout; g.cv_Wout = Wout; g.cv_stride = stride; g.cv_ntaps = tpb; g.cv_cin = cw.cinp;
     g.cv_taps_total = cw.taps;
     g.zero_row = zero_row;
-    if (launch_gemm_h3x<false, false, false, false, EpiSlabZ, 0, true>(g, DS_SPLIT, EpiSlabZ{slab, (long)cw.Npad, M * cw.Npad}, st) != hipSuccess)
+    if (launch_gemm_h3x<false, false, false, false, EpiStoreZ, 0, true>(g, DS_SPLIT, EpiStoreZ{slab, (long)cw.Npad, M * cw.Npad}, st) != hipSuccess)
         return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
     const long MN = M * cw.Npad;
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((MN / 4 + 255) / 256)), dim3(256), 0, st, slab, DS_SPLIT, MN, cw.Npad, bias, out);
@@ -610,13 +572,10 @@ int run_aff(const tdx_eres2net* h, const AffW& a, const float* x, long ldx, cons
         GemmSeg s1 = make_seg(y, ldy, h->dev + a.c0.w + a.C, 2L * a.C, a.C);
         GemmArgs g = make_args((int)M, a.c0.Npad, s0);
         g.seg[1] = s1; g.nseg = 2;
-        if (launch_gemm<false, false, false, false>(g, 1, EpiAffSilu{h->dev + a.c0.b, tbuf, a.ipad}, st) != hipSuccess)
+        if (launch_gemm<false, false, false, false>(g, 1, EpiBiasActN<ActSilu>{h->dev + a.c0.b, tbuf, a.ipad, a.ipad}, st) != hipSuccess)
             return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
     }
-    GemmArgs g = make_args((int)M, a.c3.Npad, make_seg(tbuf, a.ipad, h->dev + a.c3.w, a.ipad, a.ipad));
-    if (launch_gemm<false, false, false, false>(g, 1, EpiAffGate{h->dev + a.c3.b, x, ldx, y, ldy, out, ldo, a.C}, st) != hipSuccess)
-        return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
-    return TDX_OK;
+    return linear_f32(tbuf, a.ipad, h->dev + a.c3.w, (int)M, a.c3.Npad, a.ipad, EpiAffGate{h->dev + a.c3.b, x, ldx, y, ldy, out, ldo, a.C}, st);
 }
 
 // fuse34 (C = 2048, M >= 8192 rows) on the x3 core: GEMM1 as TWO K segments — x (a ReLU20 output) as planes with the static scale 2^10,
@@ -633,7 +592,7 @@ int run_aff34_x3(const tdx_eres2net* h, const AffW& a, const float* x, const flo
         g.seg[0].sa_mul = 0;
         g.seg[1] = h3_seg(yP, ys, 4L * C, a.c0.hp + 4L * C, a.c0.hs, 4L * 2 * C, C);
         g.nseg = 2; g.M = (int)M; g.N = a.c0.Npad;
-        if (launch_gemm_h3x<false, false, false, true>(g, 1, EpiAffSilu{h->dev + a.c0.b, tbuf, IP}, st) != hipSuccess)
+        if (launch_gemm_h3x<false, false, false, true>(g, 1, EpiBiasActN<ActSilu>{h->dev + a.c0.b, tbuf, IP, IP}, st) != hipSuccess)
             return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
     }
     if (tdx::launch_h3_split_rows(tbuf, IP, tP, ts, M, IP, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
@@ -856,16 +815,16 @@ int tdx_eres2net_forward(tdx_eres2net* h, const float* feat, int B, int F, float
                 Hc = Ho; Wc = Wo; sc_ = 1;
             } else if (tdx::launch_h3_split_rows_static(x, b.cin, hx, (long)B * Hin * Win, b.cin, 1024.0f, st) != hipSuccess)
                 return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
-            TRY(conv_gemm_h3(hx, inv20, zero_row, b.conv1, B, Hc, Wc, Ho, Wo, sc_, EpiRelu20{h->dev + b.conv1.b, o1, b.w4, b.w4}, st));
+            TRY(conv_gemm_h3(hx, inv20, zero_row, b.conv1, B, Hc, Wc, Ho, Wo, sc_, EpiBiasActN<ActRelu20>{h->dev + b.conv1.b, o1, b.w4, b.w4}, st));
             if (b.has_sc) {
-                TRY(conv_gemm_h3(hx, inv20, zero_row, b.sc, B, Hc, Wc, Ho, Wo, sc_, EpiBiasG{h->dev + b.sc.b, res, b.cout, b.cout}, st));
+                TRY(conv_gemm_h3(hx, inv20, zero_row, b.sc, B, Hc, Wc, Ho, Wo, sc_, EpiBiasActN<>{h->dev + b.sc.b, res, b.cout, b.cout}, st));
                 resid = res;
             }
         } else {
             // conv1 (1x1, stride) + bn1 + relu20 -> o1 [M, w4]
-            TRY(conv_gemm(x, b.cin, h->dev, b.conv1, B, Hin, Win, Ho, Wo, b.stride, EpiRelu20{h->dev + b.conv1.b, o1, b.w4, b.w4}, st));
+            TRY(conv_gemm(x, b.cin, h->dev, b.conv1, B, Hin, Win, Ho, Wo, b.stride, EpiBiasActN<ActRelu20>{h->dev + b.conv1.b, o1, b.w4, b.w4}, st));
             if (b.has_sc) {
-                TRY(conv_gemm(x, b.cin, h->dev, b.sc, B, Hin, Win, Ho, Wo, b.stride, EpiBiasG{h->dev + b.sc.b, res, b.cout, b.cout}, st));
+                TRY(conv_gemm(x, b.cin, h->dev, b.sc, B, Hin, Win, Ho, Wo, b.stride, EpiBiasActN<>{h->dev + b.sc.b, res, b.cout, b.cout}, st));
                 resid = res;
             }
         }
@@ -895,11 +854,9 @@ int tdx_eres2net_forward(tdx_eres2net* h, const float* feat, int B, int F, float
         if (x3) {   // conv3 + bn3 + residual + relu20 -> y   (cat = ReLU20 outputs)
             if (tdx::launch_h3_split_rows_static(cat, b.w4, hcat, M, b.w4, 1024.0f, st) != hipSuccess)
                 return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
-            TRY(conv_gemm_h3(hcat, inv20, zero_row, b.conv3, B, Ho, Wo, Ho, Wo, 1, EpiConv3{h->dev + b.conv3.b, resid, y, b.cout}, st));
+            TRY(conv_gemm_h3(hcat, inv20, zero_row, b.conv3, B, Ho, Wo, Ho, Wo, 1, EpiBiasRes<ActRelu20>{h->dev + b.conv3.b, resid, y, b.cout}, st));
         } else {
-            GemmArgs g = make_args((int)M, b.conv3.Npad, make_seg(cat, b.w4, h->dev + b.conv3.w, b.conv3.cinp, b.conv3.cinp));
-            if (launch_gemm<false, false, false, false>(g, 1, EpiConv3{h->dev + b.conv3.b, resid, y, b.cout}, st) != hipSuccess)
-                return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
+            TRY(linear_f32(cat, b.w4, h->dev + b.conv3.w, (int)M, b.conv3.Npad, b.conv3.cinp, EpiBiasRes<ActRelu20>{h->dev + b.conv3.b, resid, y, b.cout}, st));
         }
         x = y;
         cur = last_of_stage3 ? -1 : iy;
@@ -913,7 +870,7 @@ int tdx_eres2net_forward(tdx_eres2net* h, const float* feat, int B, int F, float
     if (wp.slab && h->ds.taps == 9 && h->ds.Npad == 2048)
         TRY(conv_gemm_h3_tapsplit(hx, inv20, zero_row, h->ds, B, d.H[3], d.W[3], d.H[4], d.W[4], 2, slab, nullptr, P[i_ds], st));
     else
-        TRY(conv_gemm_h3(hx, inv20, zero_row, h->ds, B, d.H[3], d.W[3], d.H[4], d.W[4], 2, EpiBiasG{nullptr, P[i_ds], 2048, 2048}, st));
+        TRY(conv_gemm_h3(hx, inv20, zero_row, h->ds, B, d.H[3], d.W[3], d.H[4], d.W[4], 2, EpiBiasActN<>{nullptr, P[i_ds], 2048, 2048}, st));
     const char* aff34_env = getenv("TDX_ERES_AFF34_ROWS");             // (tests force the x3 path at small sizes)
     const long aff34_min = aff34_env ? atol(aff34_env) : 8192;
     if (M4 >= aff34_min && 2 * M4 <= (long)B * 40960 && h->fuse34.c0.hp && h->fuse34.ipad == 512)      // (fewer rows: a handful of 256-row tiles with 256 k steps each — the fp32 core's smaller tiles win)

@@ -25,9 +25,7 @@
 #include <vector>
 
 #include "../../include/tdx.h"
-#include "gemm.hpp"
-#include "devutil.hpp"
-#include "tdx_common.hpp"
+#include "epilogues.hpp"
 
 using namespace tdx;
 
@@ -112,10 +110,6 @@ __global__ __launch_bounds__(256) void memory_kernel(const float* __restrict__ p
 }
 
 // (c) softmax over the 248 classes of a row, one wave per row: p0[t] = posterior of class 0; post[t][0..247] when post != NULL
-__device__ __forceinline__ float wave_max(float v) {
-    v = h3_row16_max(v);
-    return fmaxf(fmaxf(h3_lane(v, 0), h3_lane(v, 16)), fmaxf(h3_lane(v, 32), h3_lane(v, 48)));
-}
 __global__ __launch_bounds__(256) void softmax_kernel(const float* __restrict__ logits, float* __restrict__ p0, float* __restrict__ post, int rows) {
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -132,22 +126,13 @@ __global__ __launch_bounds__(256) void softmax_kernel(const float* __restrict__ 
     if (post && on) *reinterpret_cast<f32x4*>(post + (long)t * NCLS + lane * 4) = e * inv;
 }
 
-struct EpiBias {        // v + b (optionally ReLU); every column of the padded width is stored (see the file comment)
-    const float* b; float* out; long ld; int relu;
-    __device__ float col(int, int n) const { return b ? b[n] : 0.f; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const {
-        out[(long)m * ld + n] = relu ? fmaxf(v + c, 0.f) : v + c;
-    }
-};
-
 struct Lin { size_t w, b; int Np, Kp; bool bias; };
 
-int dense(const float* A, const float* dev, const Lin& l, int M, float* out, int relu, hipStream_t st) {
-    GemmArgs g = make_args(M, l.Np, make_seg(A, l.Kp, dev + l.w, l.Kp, l.Kp));
-    if (launch_gemm<false, false, false, false>(g, 1, EpiBias{l.bias ? dev + l.b : nullptr, out, (long)l.Np, relu}, st) != hipSuccess)
-        return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
-    return TDX_OK;
+// v + b (optionally ReLU); every column of the padded width is stored (see the file comment)
+int dense(const float* A, const float* dev, const Lin& l, int M, float* out, bool relu, hipStream_t st) {
+    const float* b = l.bias ? dev + l.b : nullptr;
+    if (relu) return linear_f32(A, l.Kp, dev + l.w, M, l.Np, l.Kp, EpiBiasAct<ActRelu>{b, out, l.Np}, st);
+    return linear_f32(A, l.Kp, dev + l.w, M, l.Np, l.Kp, EpiBiasAct<>{b, out, l.Np}, st);
 }
 
 }  // namespace
@@ -270,15 +255,15 @@ int tdx_fsmnvad_forward(tdx_fsmnvad* h, const float* feat, const int32_t* starts
     hipLaunchKernelGGL(lfr_cmvn_kernel, dim3((unsigned)((rows + LFR_ROWS - 1) / LFR_ROWS)), dim3(256), 0, st, feat, (const int*)starts, nclips,
                        dev + h->shift, dev + h->scale, a0, cstart, rows);
     LAUNCH_CHECK();
-    TRY(dense(a0, dev, h->in, rows, x[0], 1, st));
+    TRY(dense(a0, dev, h->in, rows, x[0], true, st));
     int cur = 0;
     for (int i = 0; i < NLAYER; ++i, cur ^= 1) {
-        TRY(dense(x[cur], dev, h->lin[i], rows, p, 0, st));
+        TRY(dense(x[cur], dev, h->lin[i], rows, p, false, st));
         hipLaunchKernelGGL(memory_kernel, dim3((unsigned)((rows + 8 * MEM_ROWS - 1) / (8 * MEM_ROWS))), dim3(256), 0, st, p, dev + h->mem[i], cstart, m, rows);
         LAUNCH_CHECK();
-        TRY(dense(m, dev, h->aff[i], rows, x[cur ^ 1], 1, st));
+        TRY(dense(m, dev, h->aff[i], rows, x[cur ^ 1], true, st));
     }
-    TRY(dense(x[cur], dev, h->out, rows, x[cur ^ 1], 0, st));
+    TRY(dense(x[cur], dev, h->out, rows, x[cur ^ 1], false, st));
     hipLaunchKernelGGL(softmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x[cur ^ 1], p0, post, rows);
     LAUNCH_CHECK();
     return TDX_OK;

@@ -377,10 +377,6 @@ __device__ __forceinline__ void h3_emit4_pred(unsigned char* prow, int q, float4
     const uint4 w = h3_pair16(q, v, s);
     if (ok) *reinterpret_cast<uint4*>(prow + (q >> 1) * 32 + ((q & 1) ? 16 : 0)) = w;
 }
-__device__ __forceinline__ float h3_wave_max(float v) {
-    v = h3_row16_max(v);
-    return fmaxf(fmaxf(h3_lane(v, 0), h3_lane(v, 16)), fmaxf(h3_lane(v, 32), h3_lane(v, 48)));
-}
 __device__ __forceinline__ float h3_absmax4(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
 
 
@@ -1100,7 +1096,7 @@ __global__ __launch_bounds__(H3_THREADS, 2) void gemm_h3_kernel(H3Args g, Epi ep
                     const long pr = (!CHECK || m < g.M) ? epi.prow(z, min(m, g.M - 1)) : -1L;      // (wave-uniform)
                     const f32x4 v4 = *reinterpret_cast<const f32x4*>(T + rl * 256 + ((4 * lane) ^ (((rl >> 2) & 1) << 5)));
                     const float4 v = make_float4(v4[0], v4[1], v4[2], v4[3]);
-                    const float mu = h3_wave_max(h3_absmax4(v));
+                    const float mu = wave_max(h3_absmax4(v));
                     float q2 = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
                     if (po.ss) q2 = h3_wave_sum(q2);
                     float inv;
@@ -1487,7 +1483,7 @@ __global__ __launch_bounds__(256) void h3_split_rows_long_kernel(const float* __
     const float* xr = x + row * ld;
     float mu = 0.f;
     for (int k = threadIdx.x * 4; k < K; k += 1024) mu = fmaxf(mu, h3_absmax4(*reinterpret_cast<const float4*>(xr + k)));
-    mu = h3_wave_max(mu);
+    mu = wave_max(mu);
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mu;
     __syncthreads();
     mu = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
@@ -1546,7 +1542,7 @@ template <int UNUSED = 0>
 __global__ __launch_bounds__(256) void h3_absmax_kernel(const float* __restrict__ x, long n, unsigned* __restrict__ mx) {
     float m = 0.f;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
-    m = h3_wave_max(m);
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) atomicMax(mx, __float_as_uint(m));
 }
 

@@ -21,8 +21,7 @@
 #include <vector>
 
 #include "../../include/tdx.h"
-#include "gemm.hpp"
-#include "tdx_common.hpp"
+#include "epilogues.hpp"
 
 using namespace tdx;
 
@@ -35,19 +34,12 @@ struct TdfW { size_t w1 = 0, w2 = 0, b1 = 0, b2 = 0, s1 = 0, t1 = 0, s2 = 0, t2 
 struct BlockW { std::vector<GW> conv; TdfW tdf; int c = 0, f = 0; };
 
 // ---------------------------------------------------------------- epilogues
-struct EpiBiasRelu {     // relu(v + b[n]), columns < nreal
-    const float* b; float* out; long ld; int nreal;
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const { if (n < nreal) out[(long)m * (int)ld + n] = fmaxf(v + c, 0.f); }
-};
-struct Col2 { float s, t; };
 struct EpiTdf1 {         // t[z][m][n] = relu((v + b1[m]) * s[n] + t[n])       (Linear over f, BatchNorm over channels)
     const float* b1; const float* s; const float* t; float* out; long ld; long strideZ; int nreal;
     __device__ Col2 col(int, int n) const { return Col2{s[n], t[n]}; }
     __device__ float row(int, int m) const { return b1[m]; }
     __device__ void store(int z, int m, int n, float v, float r, Col2 c) const {
-        if (n < nreal) out[(long)z * strideZ + (long)m * (int)ld + n] = fmaxf((v + r) * c.s + c.t, 0.f);
+        if (n < nreal) out[(long)z * strideZ + (long)m * (int)ld + n] = fmaxf((v + r) * c.a + c.b, 0.f);
     }
 };
 struct EpiTdf2 {         // x[z][m][n] += relu((v + b2[m]) * s[n] + t[n])
@@ -56,7 +48,7 @@ struct EpiTdf2 {         // x[z][m][n] += relu((v + b2[m]) * s[n] + t[n])
     __device__ float row(int, int m) const { return b2[m]; }
     __device__ float aux(int z, int m, int n, float) const { return n < nreal ? x[(long)z * strideZ + (long)m * (int)ld + n] : 0.f; }
     __device__ void store(int z, int m, int n, float v, float r, Col2 c, float xo) const {
-        if (n < nreal) x[(long)z * strideZ + (long)m * (int)ld + n] = xo + fmaxf((v + r) * c.s + c.t, 0.f);
+        if (n < nreal) x[(long)z * strideZ + (long)m * (int)ld + n] = xo + fmaxf((v + r) * c.a + c.b, 0.f);
     }
 };
 struct EpiUp {           // transposed 2x2 stride-2 conv: row m = input pixel (b, t, f), column r = tap * cg + n ->
@@ -170,7 +162,7 @@ int run_tfc_tdf(const tdx_mdx* h, const BlockW& bw, int B, int T, int F, float**
         GemmArgs g = make_args((int)M, cw.Npad, make_seg(*px, c, h->dev + cw.w, cw.K, c));
         g.n_valid = up(c, 32);
         g.cv_Hin = T; g.cv_Win = F; g.cv_Hout = T; g.cv_Wout = F; g.cv_stride = 1; g.cv_ntaps = 9; g.cv_cin = c;
-        if (launch_gemm<false, false, false, false, EpiBiasRelu, 0, true>(g, 1, EpiBiasRelu{h->dev + cw.b, *py, c, c}, st) != hipSuccess)
+        if (launch_gemm<false, false, false, false, EpiBiasActN<ActRelu>, 0, true>(g, 1, EpiBiasActN<ActRelu>{h->dev + cw.b, *py, c, c}, st) != hipSuccess)
             return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
         std::swap(*px, *py);
     }
@@ -357,9 +349,7 @@ int tdx_mdx_forward(tdx_mdx* h, const float* spec, int B, float* out, void* ws_,
         hipLaunchKernelGGL(mdx_s2d_kernel, dim3((unsigned)((Po * c + 255) / 256)), dim3(256), 0, st, x, s2d, Po, p.t[i + 1], p.f[i + 1], c);
         LAUNCH_CHECK();
         const GW& dw = h->ds[i];
-        GemmArgs ga = make_args((int)Po, dw.Npad, make_seg(s2d, 4L * c, h->dev + dw.w, dw.K, dw.K));
-        ga.n_valid = up(dw.N, 32);
-        if (launch_gemm<false, false, false, false>(ga, 1, EpiBiasRelu{h->dev + dw.b, y, dw.N, dw.N}, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
+        TRY(linear_f32(s2d, 4L * c, h->dev + dw.w, (int)Po, dw.Npad, dw.K, EpiBiasActN<ActRelu>{h->dev + dw.b, y, dw.N, dw.N}, st, up(dw.N, 32)));
         std::swap(x, y);
     }
     TRY(run_tfc_tdf(h, h->bott, B, p.t[h->n], p.f[h->n], &x, &y, tmid, st));
@@ -367,10 +357,7 @@ int tdx_mdx_forward(tdx_mdx* h, const float* spec, int B, float* out, void* ws_,
         const int lv = h->n - i;                     // input level
         const GW& uw = h->us[i];
         const int c = p.c[lv], cg = p.c[lv - 1];
-        GemmArgs ga = make_args((int)p.P[lv], uw.Npad, make_seg(x, c, h->dev + uw.w, c, c));
-        ga.n_valid = up(uw.N, 32);
-        if (launch_gemm<false, false, false, false>(ga, 1, EpiUp{h->dev + uw.b, ws + p.skip[lv - 1], y, p.t[lv], p.f[lv], cg}, st) != hipSuccess)
-            return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
+        TRY(linear_f32(x, c, h->dev + uw.w, (int)p.P[lv], uw.Npad, c, EpiUp{h->dev + uw.b, ws + p.skip[lv - 1], y, p.t[lv], p.f[lv], cg}, st, up(uw.N, 32)));
         std::swap(x, y);
         TRY(run_tfc_tdf(h, h->dec[i], B, p.t[lv - 1], p.f[lv - 1], &x, &y, tmid, st));
     }

@@ -24,6 +24,7 @@
 #include "mf2_kernels.hpp"
 #include "tdx_common.hpp"
 #include "weight_planes.hpp"
+#include "epilogues.hpp"
 
 using namespace tdx;
 
@@ -33,7 +34,6 @@ constexpr int C = 512, HID = 2048, QK = 128, HQ = HID + QK, INNER = 256;
 
 // ------------------------------------------------------------------ GEMM epilogues
 // (concept in gemm.hpp: col()/row() fetch per-column / per-row constants once, store() writes)
-struct Col2 { float a, b; };
 template <bool ACT>
 struct EpiHiddenT {  // silu(acc*rs[m]*g[n] + b[n])                      mossformer_block.py:89-102
     // ACT = false: the pre-activation is stored and the consuming depthwise convolution applies SiLU as it loads (Conv17Args::silu_in)
@@ -120,12 +120,6 @@ struct EpiQuadSimPl {  // the same, written as row-major planes + row scales (PL
     __device__ tdx::H3PlOut plout(int) const { return tdx::H3PlOut{P, 1024, sc, nullptr, 0}; }
     __device__ long prow(int z, int m) const { return (long)z * 256 + m; }
 };
-struct EpiStore {    // plain store, per-batch stride
-    float* out; long ld; long strideZ;
-    __device__ EpiNone col(int, int) const { return EpiNone{}; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int z, int m, int n, float v, EpiNone, EpiNone) const { out[(long)z * strideZ + (long)m * (int)ld + n] = v; }
-};
 struct EpiAttnGate { // o = (att_u*v)*sigmoid(att_v*u)                       mossformer_block.py:217
     const float* vu; float* o; float* att_v; float* att_u; int G; int S; int E;
     __device__ EpiNone col(int, int) const { return EpiNone{}; }
@@ -204,42 +198,16 @@ struct EpiBiasPrelu { // prelu_scalar(acc + b[n])                            mos
     __device__ long ldm() const { return ld; }
     __device__ void put(float* p, float v, EpiNone, Col2 c) const { v += c.a; *p = v >= 0.f ? v : c.b * v; }
 };
-struct EpiBiasSilu { const float* b; float* out; long ld;
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const { out[(long)m * (int)ld + n] = siluf_acc(v + c); }
-    __device__ float* ptr(int, int m, int n) const { return out + (long)m * (int)ld + n; }
-    __device__ long ldm() const { return ld; }
-    __device__ void put(float* p, float v, EpiNone, float c) const { *p = siluf_acc(v + c); } };
-struct EpiBiasRelu { const float* b; float* out; long ld;
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const { out[(long)m * (int)ld + n] = fmaxf(v + c, 0.f); }
-    __device__ float* ptr(int, int m, int n) const { return out + (long)m * (int)ld + n; }
-    __device__ long ldm() const { return ld; }
-    __device__ void put(float* p, float v, EpiNone, float c) const { *p = fmaxf(v + c, 0.f); } };
 struct EpiBiasReluPl { const float* b; unsigned char* P; float* sc;   // relu(acc + b) as row-major planes (N = 256 = one tile: whole rows)
     __device__ float col(int, int n) const { return b[n]; }
     __device__ EpiNone row(int, int) const { return EpiNone{}; }
     __device__ float val(int, int, int, float v, EpiNone, float c) const { return fmaxf(v + c, 0.f); }
     __device__ tdx::H3PlOut plout(int) const { return tdx::H3PlOut{P, 1024, sc, nullptr, 0}; }
     __device__ long prow(int, int m) const { return m; } };
-struct EpiBias { const float* b; float* out; long ld;   // b may be null
-    __device__ float col(int, int n) const { return b ? b[n] : 0.f; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const { out[(long)m * (int)ld + n] = v + c; }
-    __device__ float* ptr(int, int m, int n) const { return out + (long)m * (int)ld + n; }
-    __device__ long ldm() const { return ld; }
-    __device__ void put(float* p, float v, EpiNone, float c) const { *p = v + c; } };
 struct EpiBiasHalves { const float* b; float* out; long M;   // [M][2C] written as [2][M][C] (the two mask branches)
     __device__ float col(int, int n) const { return b[n]; }
     __device__ EpiNone row(int, int) const { return EpiNone{}; }
     __device__ void store(int, int m, int n, float v, EpiNone, float c) const { out[(long)(n >> 9) * M * C + (long)m * C + (n & 511)] = v + c; } };
-struct EpiBiasResidual { const float* b; float* x; long ld;   // x += acc + b   mossformer_block.py:424-425
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ float aux(int, int m, int n, EpiNone) const { return x[(long)m * (int)ld + n]; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c, float xo) const { x[(long)m * (int)ld + n] = xo + (v + c); } };
 struct EpiBiasResidualPl {   // the same, and the new x rows also as planes with one scale + sum of squares per (row, 256-channel half):
     // the A operand and the ScaleNorm statistics of the next layer's to_hidden (PLOUT; N = 512 = two tiles = the two halves)
     const float* b; float* x; long ld; unsigned char* xp; float* xs; float* xss; long M;
@@ -332,7 +300,7 @@ __global__ void concat_vu_kernel(const float* __restrict__ v, const float* __res
 __global__ void planes_absmax_kernel(const _Float16* __restrict__ p, long n, unsigned* __restrict__ out) {
     float m = 0.f;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf((float)p[i]));
-    for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
 }
 __global__ void zero_words_kernel(unsigned* __restrict__ p, int n) {
@@ -341,7 +309,6 @@ __global__ void zero_words_kernel(unsigned* __restrict__ p, int n) {
 }
 
 // ------------------------------------------------------------------ model
-struct H3W { const unsigned char* p; const float* s; };
 struct LayerW {
     // FLASH
     const float *Whq, *ghq, *bhq, *cw_h, *cw_qk, *gamma, *beta, *Wo, *go, *bo, *cw_o;
@@ -519,7 +486,7 @@ int attention_core(const float* qk4, const float* vu, int B, int S, int E, int s
         GemmSeg s = make_seg(lin_k, QK, vu, 2L * E, kchunk, (long)Sp * QK, (long)S * 2 * E);
         s.zdiv = splits; s.strideA2 = (long)kchunk * QK; s.strideB2 = (long)kchunk * 2 * E; s.kchunk = kchunk; s.ktotal = S;
         GemmArgs g = make_args(QK, 2 * E, s);
-        EpiStore e{slab, 2L * E, (long)QK * 2 * E};
+        EpiStoreZ e{slab, 2L * E, (long)QK * 2 * E};
         if (launch_gemm<true, true, false, false>(g, B * splits, e, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
         const long per = (long)QK * 2 * E;
         hipLaunchKernelGGL(kvu_reduce_kernel, dim3((unsigned)((per / 4 + 255) / 256), B), dim3(256), 0, st, slab, kvu, splits, per, (float)S);
@@ -591,7 +558,7 @@ int attention_core_h3(const unsigned char* qkP, const float* qks, const unsigned
         g.seg[0].strideB = (long)Sp * 4 * 2 * E; g.seg[0].strideB2 = (long)kchunk * 4 * 2 * E;
         g.seg[0].kchunk = kchunk; g.seg[0].ktotal = Sp;
         g.nseg = 1; g.M = QK; g.N = 2 * E;
-        EpiStore e{slab, 2L * E, (long)QK * 2 * E};
+        EpiStoreZ e{slab, 2L * E, (long)QK * 2 * E};
         if (use_h3a() && tdx::h3a_fits<false>(g, false)) {      // 128-row tiles, two blocks per CU: every wave has rows
             if (tdx::launch_gemm_h3a<false>(g, B * splits, e, st_) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
         } else if (tdx::launch_gemm_h3x<false, true, false, false>(g, B * splits, e, st_) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
@@ -674,36 +641,12 @@ int ddn_core(const float* p, int B, int S, const float* w1T, const float* w2T, c
     return TDX_OK;
 }
 
-// every nn.Linear / 1x1 Conv1d with a K-contiguous weight goes through the split-bf16 x6 kernel
-// (gemm_x6.hpp); W must be readable up to the next multiple of 256 rows.
-template <class Epi>
-int linear_gemm(const float* A, long lda, const float* W, int M, int N, int K, Epi e, hipStream_t st) {
-    GemmArgs g = make_args(M, N, make_seg(A, lda, W, K, K));
-    if (launch_gemm_x6<false>(g, e, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
-    return TDX_OK;
-}
-// nn.Linear on the split-f16 x3 core (gemm_h3.hpp): A already in planes
-template <class Epi>
-int linear_h3(const unsigned char* Ap, const float* As, int M, const H3W& W, int N, int K, Epi e, hipStream_t st) {
-    tdx::H3Args g{};
-    g.seg[0] = tdx::h3_seg(Ap, As, 4L * K, W.p, W.s, 4L * K, K);
-    g.nseg = 1; g.M = M; g.N = N;
-    if (tdx::launch_gemm_h3<false>(g, 1, e, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
-    return TDX_OK;
-}
-// ... A in fp32: split pass first (rows whose producer does not own whole rows)
+// nn.Linear on the split-f16 x3 core with A in fp32: split pass first (rows whose producer does not own whole rows)
 template <class Epi>
 int split_linear_h3(const float* A, long lda, unsigned char* hp, float* hs, int M, const H3W& W, int N, int K, Epi e, hipStream_t st) {
     if (tdx::launch_h3_split_rows(A, lda, hp, hs, M, K, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
     return linear_h3(hp, hs, M, W, N, K, e, st);
 }
-template <class Epi>
-int linear_gemm_f32(const float* A, long lda, const float* W, int M, int N, int K, Epi e, hipStream_t st) {
-    GemmArgs g = make_args(M, N, make_seg(A, lda, W, K, K));
-    if (launch_gemm<false, false, false, false>(g, 1, e, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
-    return TDX_OK;
-}
-
 
 // A/B switch: the depthwise convolution of v|u fused into the to_hidden epilogue (gemm_h3.hpp H3Conv).  TDX_FUSE_CONV=0 restores the
 // separate conv17<4> pass (same arithmetic in the same order: bit-identical results).
@@ -1126,7 +1069,7 @@ int tdx_mf2_forward(tdx_mf2* h, const float* wav, int B, int T, float* out, void
         hipLaunchKernelGGL((layernorm_kernel<INNER, true>), rows4(M), dim3(256), 0, st, hraw, w.ln1g, w.ln1b, hh, (float*)nullptr, M, 1e-5f,
                            hp, hs);
         LAUNCH_CHECK();
-        TRY(linear_h3(hp, hs, (int)M, w.hWuv, C, INNER, EpiBiasSilu{w.buv, uvpre, C}, st));
+        TRY(linear_h3(hp, hs, (int)M, w.hWuv, C, INNER, EpiBiasAct<ActSilu>{w.buv, uvpre, C}, st));
         {
             Conv17Args a{};
             a.in = uvpre; a.ld_in = C; a.col0 = 0; a.wT = w.cw_uv; a.C = C; a.out = uv; a.ld_out = C; a.S = S; a.Sp = Sp;
@@ -1134,7 +1077,7 @@ int tdx_mf2_forward(tdx_mf2* h, const float* wav, int B, int T, float* out, void
             TRY(launch_conv17<0>(a, B, st));
         }
         TRY(linear_h3(hp, hs, (int)M, w.hWl, INNER, INNER, EpiBiasReluPl{w.bl, fP, fs}, st));       // f = relu(.) as planes
-        TRY(linear_h3(fP, fs, (int)M, w.hWp, INNER, INNER, EpiBias{nullptr, p, INNER}, st));
+        TRY(linear_h3(fP, fs, (int)M, w.hWp, INNER, INNER, EpiBiasAct<>{nullptr, p, INNER}, st));
         TRY(ddn_core(p, B, S, w.w1T, w.w2T, w.ing, w.inb, w.pre, c1, c2, stat1, stat2, part, st));
         hipLaunchKernelGGL(fsmn_tail_kernel, rows4(M), dim3(256), 0, st, c2, stat2, w.ing + INNER, w.inb + INNER, w.pre + INNER, uv, hh,
                            w.ln2g, w.ln2b, hp, hs, M, S);
@@ -1333,8 +1276,8 @@ int tdx_dilated_dense_net(const float* p, int B, int S, const float* w1, const f
 int tdx_linear(const float* a, const float* w, const float* bias, int M, int N, int K, float* c, void* stream) {
     if (!a || !w || !c) return tdx::fail(TDX_E_INVALID, "tdx_linear: null argument");
     if (M < 1 || N % 128 || K % 32 || N < 128 || K < 32) return tdx::fail(TDX_E_INVALID, "tdx_linear: need N%128==0, K%32==0");
-    if (N % 256 == 0) return linear_gemm(a, K, w, M, N, K, EpiBias{bias, c, N}, (hipStream_t)stream);     // split-bf16 x6 core
-    return linear_gemm_f32(a, K, w, M, N, K, EpiBias{bias, c, N}, (hipStream_t)stream);                   // fp32-MFMA core
+    if (N % 256 == 0) return linear_x6(a, K, w, M, N, K, EpiBiasAct<>{bias, c, N}, (hipStream_t)stream);     // split-bf16 x6 core
+    return linear_f32(a, K, w, M, N, K, EpiBiasAct<>{bias, c, N}, (hipStream_t)stream);                   // fp32-MFMA core
 }
 
 int tdx_cosine_scores(const float* emb, const float* ref, int N, int D, float* scores, void* stream) {

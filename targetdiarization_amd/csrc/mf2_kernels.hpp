@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void rowscale_split_kernel(const float* __rest
     }
     acc = wave_sum(acc);
     float inv;
-    const float sc = h3_row_scale(h3_wave_max(mu), inv);
+    const float sc = h3_row_scale(wave_max(mu), inv);
 #pragma unroll
     for (int i = 0; i < C / 256; ++i) h3_emit4(hp + m * (4L * C), i * 64 + lane, v[i], sc);
     if (lane == 0) {
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void xplanes_kernel(const float* __restrict__ 
     const float4 v = *reinterpret_cast<const float4*>(x + m * 512 + hf * 256 + lane * 4);
     const float q2 = wave_sum((v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w));
     float inv;
-    const float sc = h3_row_scale(h3_wave_max(h3_absmax4(v)), inv);
+    const float sc = h3_row_scale(wave_max(h3_absmax4(v)), inv);
     h3_emit4(xp + m * 2048, hf * 64 + lane, v, sc);
     if (lane == 0) { xs[(long)hf * M + m] = inv; xss[(long)hf * M + m] = q2; }
 }
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(256) void fsmn_tail_kernel(const float* __restrict_
     r.z = g[2] * rstd * lg.z + lb.z; r.w = g[3] * rstd * lg.w + lb.w;
     // the only consumer is the conv2 1x1 GEMM: written as split-f16 planes (gemm_h3.hpp)
     float inv;
-    const float sc = h3_row_scale(h3_wave_max(h3_absmax4(r)), inv);
+    const float sc = h3_row_scale(wave_max(h3_absmax4(r)), inv);
     h3_emit4(hp + m * 1024L, lane, r, sc);
     if (lane == 0) hs[m] = inv;
 }
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(256) void kvu_reduce_t_kernel(const float* __restri
         *reinterpret_cast<float4*>(kvu + (long)b * per + i4 * 4) = acc;
         m = h3_absmax4(acc);
     }
-    m = h3_wave_max(m);
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) bmax[(long)b * gridDim.x + blockIdx.x] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
@@ -510,7 +510,7 @@ __global__ __launch_bounds__(256) void kvu_planes_kernel(const float* __restrict
     const int b = blockIdx.y;
     float mu = 0.f;
     for (int i = threadIdx.x; i < nbmax; i += 256) mu = fmaxf(mu, bmax[(long)b * nbmax + i]);
-    mu = h3_wave_max(mu);
+    mu = wave_max(mu);
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mu;
     __syncthreads();
     mu = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));

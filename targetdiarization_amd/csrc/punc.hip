@@ -13,9 +13,7 @@
 #include <vector>
 
 #include "../../include/tdx.h"
-#include "gemm.hpp"
-#include "devutil.hpp"
-#include "tdx_common.hpp"
+#include "epilogues.hpp"
 
 using namespace tdx;
 
@@ -94,8 +92,7 @@ __global__ __launch_bounds__(256) void punc_attn_kernel(const float* __restrict_
             float* row = p[2 * w + rr];
             float mx = -INFINITY;
             for (int c = lane; c < L; c += 64) mx = fmaxf(mx, row[c]);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+            mx = wave_max(mx);
             float sum = 0.f;
             for (int c = lane; c < L; c += 64) { const float e = expf(row[c] - mx); row[c] = e; sum += e; }
             sum = wave_sum(sum);
@@ -111,27 +108,6 @@ __global__ __launch_bounds__(256) void punc_attn_kernel(const float* __restrict_
         for (int j = 0; j < L; ++j) acc = fmaf(p[r][j], vp[(long)j * (3 * PD)], acc);
         if (r0 + r < T) ctx[((long)b * T + r0 + r) * PD + h * PDK + d] = acc;
     }
-}
-
-struct EpiB { const float* b; float* out; long ld; int nreal;
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const { if (n < nreal) out[(long)m * (int)ld + n] = v + c; } };
-struct EpiBRelu { const float* b; float* out; long ld;
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const { out[(long)m * (int)ld + n] = fmaxf(v + c, 0.f); } };
-struct EpiBRes { const float* b; const float* mem; float* x;       // x += v + b (+ mem)
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ float aux(int, int m, int n, EpiNone) const { const long i = (long)m * PD + n; return mem ? x[i] + mem[i] : x[i]; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c, float a) const { x[(long)m * PD + n] = a + (v + c); } };
-
-template <class Epi>
-int lin(const float* A, long lda, const float* W, int M, int N, int K, Epi e, hipStream_t st) {
-    GemmArgs g = make_args(M, N, make_seg(A, lda, W, K, K));
-    if (launch_gemm<false, false, false, false>(g, 1, e, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
-    return TDX_OK;
 }
 
 struct PLayer { size_t Wqkv, bqkv, fsmnT, Wo, bo, W1, b1, W2, b2, n1g, n1b, n2g, n2b; };
@@ -208,20 +184,20 @@ int tdx_punc_forward(tdx_punc* h, const int* ids, const int* lens, int B, int T,
     for (const PLayer& w : h->layers) {
         hipLaunchKernelGGL(punc_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, d + w.n1g, d + w.n1b, hn, M, 1e-12f);
         LAUNCH_CHECK();
-        TRY(lin(hn, PD, d + w.Wqkv, (int)M, 3 * PD, PD, EpiB{d + w.bqkv, qkv, 3 * PD, 3 * PD}, st));
+        TRY(linear_f32(hn, PD, d + w.Wqkv, (int)M, 3 * PD, PD, EpiBiasAct<>{d + w.bqkv, qkv, 3 * PD}, st));
         hipLaunchKernelGGL(punc_fsmn_kernel, dim3((unsigned)M), dim3(256), 0, st, qkv, d + w.fsmnT, mem, T, lens);
         LAUNCH_CHECK();
         hipLaunchKernelGGL(punc_attn_kernel, dim3((T + 7) / 8, PH, B), dim3(256), 0, st, qkv, ctx, T, lens);
         LAUNCH_CHECK();
-        TRY(lin(ctx, PD, d + w.Wo, (int)M, PD, PD, EpiBRes{d + w.bo, mem, x}, st));                 // x += att W_o + b_o + mem
+        TRY(linear_f32(ctx, PD, d + w.Wo, (int)M, PD, PD, EpiBiasRes2<>{d + w.bo, x, mem, x, PD}, st));                 // x += att W_o + b_o + mem
         hipLaunchKernelGGL(punc_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, d + w.n2g, d + w.n2b, hn, M, 1e-12f);
         LAUNCH_CHECK();
-        TRY(lin(hn, PD, d + w.W1, (int)M, PFFN, PD, EpiBRelu{d + w.b1, ffn, PFFN}, st));
-        TRY(lin(ffn, PFFN, d + w.W2, (int)M, PD, PFFN, EpiBRes{d + w.b2, nullptr, x}, st));
+        TRY(linear_f32(hn, PD, d + w.W1, (int)M, PFFN, PD, EpiBiasAct<ActRelu>{d + w.b1, ffn, PFFN}, st));
+        TRY(linear_f32(ffn, PFFN, d + w.W2, (int)M, PD, PFFN, EpiBiasRes<>{d + w.b2, x, x, PD}, st));
     }
     hipLaunchKernelGGL(punc_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, d + h->ang, d + h->anb, hn, M, 1e-12f);
     LAUNCH_CHECK();
-    TRY(lin(hn, PD, d + h->Wd, (int)M, 128, PD, EpiB{d + h->bd, logits, h->npunc, h->npunc}, st));
+    TRY(linear_f32(hn, PD, d + h->Wd, (int)M, 128, PD, EpiBiasActN<>{d + h->bd, logits, h->npunc, h->npunc}, st));
     return TDX_OK;
 }
 

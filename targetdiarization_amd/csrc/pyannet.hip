@@ -37,9 +37,7 @@
 #include <vector>
 
 #include "../../include/tdx.h"
-#include "gemm.hpp"
-#include "devutil.hpp"
-#include "tdx_common.hpp"
+#include "epilogues.hpp"
 
 using namespace tdx;
 
@@ -62,6 +60,7 @@ constexpr int REC_TILE = TDX_PYANNET_REC_TILE, REC_THREADS = 512, H_PITCH = 4 * 
 static_assert(REC_TILE >= 1 && REC_TILE * H_PITCH <= REC_THREADS, "one thread zeroes one float of the first h buffer");
 constexpr int SLACK = 64;                      // floats after a conv input for the last rows' K-padding over-read (<= 20)
 constexpr float EPS = 1e-5f, SLOPE = 0.01f;
+static_assert(SLOPE == 1.0f / 100.0f, "dense() applies the slope as ActLeaky<1, 100>");
 
 struct Dims { int n1, p1, n2, p2, n3, F; };
 inline Dims dims_of(int T) {
@@ -71,8 +70,6 @@ inline Dims dims_of(int T) {
     d.n3 = d.p2 - (KCONV - 1); d.F = d.n3 / 3;
     return d;
 }
-
-__device__ __forceinline__ float leaky(float v) { return v >= 0.f ? v : SLOPE * v; }
 
 // sum over the 256 threads of a block, the same value in every thread; s4: 4 floats of LDS
 __device__ __forceinline__ float block_sum256(float v, float* s4) {
@@ -234,7 +231,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* in, const 
         const int fl = i / ldo, c = i - fl * ldo, f = f0 + fl;
         float v = 0.f;
         if (c < C) {
-            v = leaky(fmaf(pooled<C, POOL>(x, f, c), sa[c], sc[c]));
+            v = leaky(fmaf(pooled<C, POOL>(x, f, c), sa[c], sc[c]), SLOPE);
             if (tap) tap[((size_t)b * P + f) * C + c] = v;
         }
         out[((size_t)b * P + f) * ldo + c] = v;
@@ -331,14 +328,6 @@ __global__ __launch_bounds__(256) void logsoftmax_kernel(const float* __restrict
     for (int i = 0; i < NCLS; ++i) logp[(size_t)r * NCLS + i] = x[i] - lse;
 }
 
-struct EpiDense {       // columns < nvalid: out[m][n] = v + b[n], optionally leaky_relu
-    const float* b; float* out; long ld; int nvalid, act;
-    __device__ float col(int, int n) const { return b[n]; }
-    __device__ EpiNone row(int, int) const { return EpiNone{}; }
-    __device__ void store(int, int m, int n, float v, EpiNone, float c) const {
-        if (n < nvalid) out[(long)m * ld + n] = act ? leaky(v + c) : v + c;
-    }
-};
 struct EpiConv {        // batch z = chunk: out[z][m][n] = v + b[n], n < 60
     const float* b; float* out; long rows;
     __device__ float col(int, int n) const { return b[n]; }
@@ -350,12 +339,10 @@ struct EpiConv {        // batch z = chunk: out[z][m][n] = v + b[n], n < 60
 
 struct Lin { size_t w, b; int Np, Kp, N; };
 
-int dense(const float* A, long lda, const float* dev, const Lin& l, int M, float* out, long ldo, int act, hipStream_t st) {
-    GemmArgs g = make_args(M, l.Np, make_seg(A, lda, dev + l.w, l.Kp, l.Kp));
-    g.n_valid = up(l.N, 32);
-    if (launch_gemm<false, false, false, false>(g, 1, EpiDense{dev + l.b, out, ldo, l.N, act}, st) != hipSuccess)
-        return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
-    return TDX_OK;
+// columns < l.N: out[m][n] = v + b[n], optionally leaky_relu
+int dense(const float* A, long lda, const float* dev, const Lin& l, int M, float* out, long ldo, bool act, hipStream_t st) {
+    if (act) return linear_f32(A, lda, dev + l.w, M, l.Np, l.Kp, EpiBiasActN<ActLeaky<1, 100>>{dev + l.b, out, ldo, l.N}, st, up(l.N, 32));
+    return linear_f32(A, lda, dev + l.w, M, l.Np, l.Kp, EpiBiasActN<>{dev + l.b, out, ldo, l.N}, st, up(l.N, 32));
 }
 
 // the k5 convolution of B chunks: in [B][rows_in][C] (normalised), out [B][rows_in - 4][60]
@@ -573,15 +560,15 @@ int tdx_pyannet_forward(tdx_pyannet* h, const float* wav, int B, int T, float* l
     const float* x = s;
     long ldx = SIN;
     for (int l = 0; l < NLAYER; ++l) {
-        TRY(dense(x, ldx, dev, h->proj[l], rows, xp, XP, 0, st));
+        TRY(dense(x, ldx, dev, h->proj[l], rows, xp, XP, false, st));
         float* yo = (l == NLAYER - 1 && tap_lstm) ? tap_lstm : y[l & 1];
         hipLaunchKernelGGL(lstm_rec_kernel, dim3(blocks(B, REC_TILE), NDIR), dim3(REC_THREADS), 0, st, (const float*)xp, dev + h->whh[l], yo, B, d.F);
         LAUNCH_CHECK();
         x = yo; ldx = LSTM_OUT;
     }
-    TRY(dense(x, LSTM_OUT, dev, h->lin[0], rows, hd[0], HID, 1, st));
-    TRY(dense(hd[0], HID, dev, h->lin[1], rows, hd[1], HID, 1, st));
-    TRY(dense(hd[1], HID, dev, h->cls, rows, logits, LOGIT_LD, 0, st));
+    TRY(dense(x, LSTM_OUT, dev, h->lin[0], rows, hd[0], HID, true, st));
+    TRY(dense(hd[0], HID, dev, h->lin[1], rows, hd[1], HID, true, st));
+    TRY(dense(hd[1], HID, dev, h->cls, rows, logits, LOGIT_LD, false, st));
     hipLaunchKernelGGL(logsoftmax_kernel, dim3(blocks(rows, 256)), dim3(256), 0, st, (const float*)logits, logp, rows);
     LAUNCH_CHECK();
     return TDX_OK;
