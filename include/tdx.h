@@ -375,6 +375,33 @@ double tdx_pyannet_flops(const tdx_pyannet* h, int B, int T);
 int tdx_pyannet_forward(tdx_pyannet* h, const float* wav_dev, int B, int T, float* logp_dev, float* tap_sincnet,
                         float* tap_lstm, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * N7   silero-VAD per-chunk speech probabilities — the network inside `get_speech_timestamps(audio, self.vad_model)`
+ *      (TargetDiarizationStream.py:128-131, AudioProcessor.py:903-905; silero-vad v5, 16 kHz branch, third-party; parity
+ *      unpinned [upstream-recall]).  Per 512-sample chunk: a 640-sample window (64 samples of context, zeros at a clip's
+ *      first chunk; the chunk; 64 samples of right reflect pad of the chunk's own tail), 4 frames of 256 at hop 128 against
+ *      the stored STFT basis -> magnitudes [129,4], four Conv1d(k=3, pad=1) + ReLU with strides 1, 2, 2, 1
+ *      ([129,4] -> [128,4] -> [64,2] -> [64,1] -> [128,1], zero padding per chunk), LSTMCell(128,128) with (h, c) zero at
+ *      the clip's first chunk and carried chunk to chunk, p = sigmoid(w . relu(h) + b).  The state machine that turns
+ *      probabilities into timestamps runs on the host (targetdiarization_amd/silero.py).
+ *      blob: TDXW container with the 16 kHz branch's state-dict names without the `_model.` prefix
+ *      (stft.forward_basis_buffer, encoder.{0..3}.reparam_conv.*, decoder.rnn.*, decoder.decoder.2.*); strict both ways
+ *      like the other models.
+ *      wav_dev [total_chunks*512]: the clips packed back to back, each already zero-padded to whole chunks;
+ *      chunk_starts_dev int32 [nclips+1] on the DEVICE, strictly ascending, starts[0] = 0, starts[nclips] = total_chunks:
+ *      clip c owns chunks [starts[c], starts[c+1]).  prob_dev [total_chunks]; tap_feat / tap_h: NULL or [total_chunks,128],
+ *      the encoder output and the LSTM h.  1 <= nclips <= 1024, every clip >= 1 chunk, total_chunks <= 2^20
+ *      (workspace_bytes returns 0 outside, forward TDX_E_INVALID).  A clip's result does not depend on the other clips of
+ *      the batch.  9 launches per call whatever nclips and total_chunks; the recurrence is one launch, one workgroup per clip.
+ * ---------------------------------------------------------------------------------- */
+typedef struct tdx_silero tdx_silero;
+int tdx_silero_create(const void* weights_blob, size_t blob_bytes, int device, tdx_silero** out);
+int tdx_silero_destroy(tdx_silero* h);
+size_t tdx_silero_workspace_bytes(const tdx_silero* h, int nclips, int total_chunks);
+double tdx_silero_flops(const tdx_silero* h, int total_chunks);
+int tdx_silero_forward(tdx_silero* h, const float* wav_dev, const int* chunk_starts_dev, int nclips, int total_chunks,
+                       float* prob_dev, float* tap_feat, float* tap_h, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

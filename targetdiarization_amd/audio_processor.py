@@ -38,14 +38,16 @@ class AudioProcessor:
                  is_restore_audio: bool = False, restorer_weights_folder: str = "JusperLee/Apollo",
                  verbose_log: bool = True, cuda_device: int = 0, quality: int = 2,
                  separater_state_dict=None, mdx_model=None, mdx_dim_f: int = 3072, mdx_n_fft: int = 6144, silero_vad=None,
-                 mdx_state_dict=None, mdx_args=None, restorer_state_dict=None):
+                 mdx_state_dict=None, mdx_args=None, restorer_state_dict=None, silero_state_dict=None, silero_model_file=None):
         """`separater_state_dict` (extension): an in-memory state_dict instead of
         `<separater_weights_folder>/best_model.pth` — no checkpoint ships with the reference.
         `mdx_model` (extension): the MDX net body as a callable on device tensors, spec[n,4,dim_f,256] -> spec (the
         reference runs the ONNX file through onnxruntime, AudioProcessor.py:231-233,630); without it the denoiser is off,
         like a failed `init_mdx_model` (:171-176).  `mdx_dim_f` / `mdx_n_fft`: the ONNX metadata the reference reads (:234-237).
         `restorer_state_dict` (extension): the Apollo weights in memory instead of `<restorer_weights_folder>/pytorch_model.bin`
-        (the reference's 6 layers, or as many as the dict holds)."""
+        (the reference's 6 layers, or as many as the dict holds).
+        `silero_state_dict` / `silero_model_file` (extension): silero-VAD's weights in memory or as a file; without a `silero_vad`
+        plug-in they put the device detector (silero.SileroVad.frames) behind `separate_speaker(low_gpu_ram=True)`."""
         if is_denoise_vocal and mdx_model is None and mdx_state_dict is not None:
             # the ConvTDFNet body on the device (mdx.ConvTDFNetBody, csrc/mdx.hip) from a state dict with the PyTorch module names;
             # `mdx_args`: its geometry (L, l, g, k, bn, dim_f, dim_t, max_blocks_per_launch).  A failure prints and leaves the denoiser
@@ -58,6 +60,13 @@ class AudioProcessor:
         self.is_denoise_vocal = bool(is_denoise_vocal and mdx_model is not None)
         self.mdx_model = mdx_model
         self.silero_vad = silero_vad            # low_gpu_ram plug-in: silero_vad(audio[n] f32 @16 kHz) -> [[start, end], ...] in samples (:903-905)
+        if silero_vad is None and (silero_state_dict is not None or silero_model_file is not None):
+            try:                                # the device silero-VAD (silero.py, tdx_silero_*); a source that fails prints and leaves None
+                from .silero import build_silero
+                model = build_silero(silero_state_dict, silero_model_file, 0 if cuda_device is None else cuda_device)
+                self.silero_vad = model.frames if model is not None else None
+            except Exception as e:
+                print(f"Failed to load silero VAD model: {e}")
         self.mdx_net = None
         self._mdx_geom = (mdx_n_fft, {1: 256, 2: 1024, 3: 2048}.get(quality, 1024), mdx_dim_f)        # :225-240
         if is_denoise_vocal and mdx_model is None:
@@ -387,9 +396,10 @@ class AudioProcessor:
             print(f"Window size: {window_size}")
             print(f"Use VAD: {is_vad}")
         if is_vad:
-            # :903-905 — silero VAD (third-party) is a plug-in: silero_vad(audio[n] f32) -> [[start, end], ...] in samples
+            # :903-905 — silero VAD: the device detector (silero_state_dict / silero_model_file) or a plug-in,
+            # silero_vad(audio[n] f32) -> [[start, end], ...] in samples
             if self.silero_vad is None:
-                print("separate_speaker: low_gpu_ram needs a silero_vad plug-in; treating the whole clip as one speech frame")
+                print("separate_speaker: low_gpu_ram needs silero-VAD weights or a silero_vad plug-in; treating the whole clip as one speech frame")
                 vad_frames = [[0, audio_data.shape[0]]]
             else:
                 vad_frames = [[int(a), int(b)] for a, b in self.silero_vad(audio_data)]

@@ -135,6 +135,7 @@ def env_to_kwargs(environ=None) -> Dict[str, Any]:
         "embedding_model_dir": env.get("EMBEDDING_MODEL_DIR"),
         "asr_model_dir": env.get("ASR_MODEL_DIR"),
         "vad_model_dir": env.get("VAD_MODEL_DIR"),
+        "silero_model_file": env.get("SILERO_VAD_MODEL"),
         "separater_weights_folder": env.get("SEPARATER_WEIGHTS_FOLDER"),
         "restorer_weights_folder": env.get("RESTORER_WEIGHTS_FOLDER"),
         "is_vad_buffer": env.get("IS_VAD_BUFFER") != "0",
@@ -151,7 +152,8 @@ def model_from_env(dotenv_path: str = ".env", environ=None, **plugins):
     """main.py:101-137 (the startup hook): `.env` -> constructor kwargs -> TargetDiarizationStream.  `plugins`: what the environment
     cannot carry here — the state dicts (no checkpoint ships with the reference) and the third-party detectors
     (sep_state_dict, spk_state_dict, asr_state_dict, sd_state_dict — the CAM++ diarizer's weights —, vad_state_dict / vad_cmvn — the device
-    FSMN-VAD's; VAD_MODEL_DIR naming a directory with model.pt and am.mvn loads it as well —, sd_pipeline, od_pipeline, vad, stream_vad, ...)."""
+    FSMN-VAD's; VAD_MODEL_DIR naming a directory with model.pt and am.mvn loads it as well —, silero_state_dict — the device silero-VAD's;
+    SILERO_VAD_MODEL naming a weight file loads it as well —, sd_pipeline, od_pipeline, vad, stream_vad, ...)."""
     from .target_diarization_stream import TargetDiarizationStream
     load_dotenv(dotenv_path, environ)
     kwargs = env_to_kwargs(environ)

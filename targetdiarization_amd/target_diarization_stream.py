@@ -4,6 +4,7 @@ router, per-buffer overlap detection, separation / speaker check / ASR of each r
 The arithmetic stages are the base class's (HotPath: MossFormer2, ERes2NetV2, Paraformer, BS.1770 loudness); the third-party
 detectors are plug-ins with the reference's result formats:
     stream_vad(audio) -> [[start_s, end_s], ...]     silero-VAD `get_speech_timestamps(..., threshold 0.5, min_silence 100 ms)` (:132-133)
+                                                     (`silero_state_dict=` / `silero_model_file=` put the device detector silero.SileroVad here)
     vad(audio)        -> [[start_s, end_s], ...]     FunASR FSMN-VAD (`tasr.asrp.vad_detection`, :58, :135, :209)
                                                      (`vad_state_dict=` / `vad_cmvn=` put the device detector vad.FsmnVad here)
     od_pipeline(audio)-> [(start, end, "SPEAKER_xx")] pyannote overlap detection (:179-184)
@@ -25,8 +26,16 @@ from .target_diarization import TargetDiarization, _whole_clip_vad
 
 class TargetDiarizationStream(TargetDiarization):
     def __init__(self, is_vad_buffer: bool = True, use_asr_prompt: bool = False, similarity_threshold: float = 0.4, vad_min_silence: float = 0.3,
-                 max_buffer_duration: float = 30.0, loudness_diff_threshold: float = 12.0, *args, stream_vad: Optional[Callable] = None, **kwargs):
+                 max_buffer_duration: float = 30.0, loudness_diff_threshold: float = 12.0, *args, stream_vad: Optional[Callable] = None,
+                 silero_state_dict=None, silero_model_file: Optional[str] = None, **kwargs):
         super().__init__(*args, **kwargs)
+        if stream_vad is None and (silero_state_dict is not None or silero_model_file is not None):
+            # the device silero-VAD (silero.py, tdx_silero_*) from weights or a weight file; a source that fails prints and leaves the default
+            try:
+                from .silero import build_silero
+                stream_vad = build_silero(silero_state_dict, silero_model_file, self.cuda_device)
+            except Exception as e:
+                print(f"Failed to load silero VAD model: {e}")
         # configuration (the reference's attribute names: callers read and tune them between sessions)
         for name, value in (("is_vad_buffer", is_vad_buffer), ("use_asr_prompt", use_asr_prompt), ("similarity_threshold", similarity_threshold),
                             ("max_buffer_duration", max_buffer_duration), ("vad_min_silence", vad_min_silence),

@@ -728,3 +728,58 @@ def pack_pyannet_blob(state_dict) -> bytes:
     """The TDXW blob tdx_pyannet_create reads: pyannote's names; the filterbank's derived buffers (n_, window_), which a
     checkpoint carries next to low_hz_ / band_hz_, are dropped (the device rebuilds the filters in fp64)"""
     return pack_blob(OrderedDict((k, v) for k, v in state_dict.items() if not k.endswith(("filterbank.n_", "filterbank.window_"))))
+
+
+# ---------------------------------------------------------------------------------------
+# silero-VAD v5, 16 kHz branch (the `silero_vad` package's model: STFT magnitude, four Conv1d(k=3) + ReLU, LSTMCell(128,128),
+# a 128 -> 1 sigmoid head)
+# [upstream-recall]: the source is not vendored and no checkpoint is at hand, parity is unpinned; tests/silero_vad_oracle.py
+# restates the forward and csrc/silero_vad.hip loads exactly these names (strict both ways).
+# ---------------------------------------------------------------------------------------
+def silero_vad_param_shapes() -> "OrderedDict[str, tuple]":
+    s = OrderedDict()
+    s["stft.forward_basis_buffer"] = (258, 1, 256)
+    for i, (co, ci) in enumerate(((128, 129), (64, 128), (64, 64), (128, 64))):
+        s[f"encoder.{i}.reparam_conv.weight"] = (co, ci, 3); s[f"encoder.{i}.reparam_conv.bias"] = (co,)
+    s["decoder.rnn.weight_ih"] = (512, 128); s["decoder.rnn.weight_hh"] = (512, 128)
+    s["decoder.rnn.bias_ih"] = (512,); s["decoder.rnn.bias_hh"] = (512,)
+    s["decoder.decoder.2.weight"] = (1, 128, 1); s["decoder.decoder.2.bias"] = (1,)
+    return s
+
+
+def recipe_silero_vad_state_dict(seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Deterministic fp32 weights for the silero-VAD layout (Philox keyed by the tensor name).  The basis is what upstream
+    stores: cos / -sin of the 256-point DFT, rows 0..128, times a periodic Hann window.  The matrices are fan-in scaled with
+    gains that keep the signal alive through the stack — 2 before a ReLU, 8 on the first convolution (magnitudes of quiet audio
+    are small), 3 on the LSTM's input matrix, 1.5 on the recurrent one — so that the network does not ignore its input;
+    tests/golden/silero_vad_calibration.json holds the head that does the rest."""
+    out = OrderedDict()
+    n = np.arange(256, dtype=np.float64)
+    k = np.arange(129, dtype=np.float64)[:, None]
+    hann = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / 256.0)
+    ang = 2.0 * np.pi * k * n[None, :] / 256.0
+    basis = np.concatenate([np.cos(ang) * hann, -np.sin(ang) * hann])[:, None, :]
+    for name, shape in silero_vad_param_shapes().items():
+        if name == "stft.forward_basis_buffer":
+            out[name] = torch.from_numpy(basis).to(torch.float32).contiguous()
+            continue
+        u = torch.from_numpy(philox_uniform("silero:" + name, int(np.prod(shape)), seed)).reshape(shape)
+        if "bias" in name:
+            t = 0.1 * u
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            gain = 8.0 if name.startswith("encoder.0.") else 3.0 if "weight_ih" in name else 1.5 if "weight_hh" in name else 2.0
+            t = u * float(np.sqrt(3.0 * gain / fan_in))
+        out[name] = t.to(torch.float32).contiguous()
+    return out
+
+
+def pack_silero_vad_blob(state_dict) -> bytes:
+    """The TDXW blob tdx_silero_create reads: the 16 kHz branch under its bare names (a `_model.` prefix is stripped, the
+    8 kHz branch `_model_8k.*` dropped)"""
+    sd = OrderedDict()
+    for k, v in state_dict.items():
+        if k.startswith("_model_8k."):
+            continue
+        sd[k[len("_model."):] if k.startswith("_model.") else k] = v
+    return pack_blob(sd)
