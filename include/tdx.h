@@ -125,6 +125,7 @@ int tdx_linear(const float* a_dev, const float* w_dev, const float* bias_dev, in
  *     funasr's WavFrontend (reached from ASRProcessor.py:424).  [third-party algorithm]
  *     mode 0 = speaker front-end: povey window, input in [-1,1], per-utterance mean removed
  *     mode 1 = ASR front-end: hamming window, input x32768 (LFR/CMVN: tdx_lfr_cmvn)
+ *     mode 2 = WeSpeaker front-end: mode 1's window and scale, mode 0's mean removal
  *     wav_dev [B,N] -> feat_dev [B,F,80], F = tdx_fbank_frames(N) = 1 + (N-400)/160.
  * ---------------------------------------------------------------------------------- */
 typedef struct tdx_fbank tdx_fbank;
@@ -401,6 +402,33 @@ size_t tdx_silero_workspace_bytes(const tdx_silero* h, int nclips, int total_chu
 double tdx_silero_flops(const tdx_silero* h, int total_chunks);
 int tdx_silero_forward(tdx_silero* h, const float* wav_dev, const int* chunk_starts_dev, int nclips, int total_chunks,
                        float* prob_dev, float* tap_feat, float* tap_h, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * N8   WeSpeaker ResNet34 with masked statistics pooling — the embedding inside `self.od_pipeline` (pyannote
+ *      speaker-diarization-3.1's `pyannote/wespeaker-voxceleb-resnet34-LM`, TargetDiarization.py:84; wespeaker ResNet34 with
+ *      m_channels 32, feat_dim 80, embed_dim 256, TSTP, one embedding layer; third-party, parity unpinned [upstream-recall]):
+ *      conv3x3(1->32) + BN + ReLU, BasicBlock stages of 3/4/6/3 blocks at 32/64/128/256 channels (the first block of stages
+ *      2-4 with stride 2 and a conv1x1 + BN shortcut), pyannote's StatsPool over time under a per-frame weight, Linear
+ *      5120 -> 256.  Eval BatchNorm (eps 1e-5) is folded into the convolution in front of it.
+ *      blob: TDXW container with upstream's state-dict names (resnet.conv1.weight, resnet.bn1.*, resnet.layerL.i.*,
+ *      resnet.seg_1.*; num_batches_tracked dropped); strict both ways like the other models, before any device work.
+ *      feat_dev [B,F,80] = tdx_fbank mode-2 output.  weights_dev [B,S,Fw]: S per-frame masks of every chunk on any frame
+ *      grid (resampled to the trunk's T' = ceil(F/8) frames by nearest neighbour, w'[i] = w[(i*Fw)/T']), or NULL with S = 1
+ *      for all ones (plain TSTP, unbiased std).  The trunk runs once per chunk and is pooled under each mask:
+ *        v1 = sum w', v2 = sum w'^2, mean = sum w' x / v1, std = sqrt(sum w' (x-mean)^2 / (v1 - v2/v1 + 1e-8))
+ *      emb_dev [B,S,256]; a row whose resampled weights sum to zero is NaN throughout, as upstream's 0/0 is.
+ *      1 <= B <= 64, F >= 1, B*F*2560 < 2^31, 1 <= S <= 8, Fw >= 1 (workspace_bytes returns 0 outside, forward
+ *      TDX_E_INVALID).  A (b, s) result does not depend on the other chunks or masks of the call.  All launches go on the
+ *      caller's stream: no atomics, no memset, no allocation.  TDX_WESPK_NARROW in the environment of tdx_wespk_create
+ *      picks the kernel of the 13 stride-1 3x3 convolutions of the 32- and 64-channel stages (a property of the handle):
+ *      1 = conv3x3_narrow_kernel, 0 = the shared GEMM core; unset = the faster of the two as measured.
+ * ---------------------------------------------------------------------------------- */
+typedef struct tdx_wespk tdx_wespk;
+int tdx_wespk_create(const void* weights_blob, size_t blob_bytes, int device, tdx_wespk** out);
+int tdx_wespk_destroy(tdx_wespk* h);
+size_t tdx_wespk_workspace_bytes(const tdx_wespk* h, int B, int F, int S);
+int tdx_wespk_forward(tdx_wespk* h, const float* feat_dev, int B, int F, const float* weights_dev, int S, int Fw,
+                      float* emb_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,10 @@ SIGNATURES = {
     "tdx_silero_workspace_bytes": (_sz, [_vp, _i, _i]),
     "tdx_silero_flops": (C.c_double, [_vp, _i]),
     "tdx_silero_forward": (_i, [_vp, _fp, _vp, _i, _i, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "tdx_wespk_create": (_i, [_vp, _sz, _i, C.POINTER(_vp)]),
+    "tdx_wespk_destroy": (_i, [_vp]),
+    "tdx_wespk_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "tdx_wespk_forward": (_i, [_vp, _fp, _i, _i, _fp, _i, _i, _fp, _vp, _sz, _vp]),
 }
 
 

@@ -68,7 +68,7 @@ struct EpiLogMel {  // log(max(mel energy, eps)), 80 of the 128 padded columns k
     }
 };
 
-// SV: feat -= mean over frames (per utterance, per bin).  one block per utterance.
+// SV / WeSpeaker: feat -= mean over frames (per utterance, per bin).  one block per utterance.
 __global__ __launch_bounds__(320) void fbank_submean_kernel(float* __restrict__ feat, int F) {
     __shared__ double part[4][NMEL];
     const int b = blockIdx.x, d = threadIdx.x % NMEL, g = threadIdx.x / NMEL;
@@ -154,7 +154,7 @@ struct tdx_stft {
 extern "C" {
 
 int tdx_fbank_create(int mode, int device, tdx_fbank** out) {
-    if (!out || (mode != 0 && mode != 1)) return tdx::fail(TDX_E_INVALID, "tdx_fbank_create: mode must be 0 (SV) or 1 (ASR)");
+    if (!out || mode < 0 || mode > 2) return tdx::fail(TDX_E_INVALID, "tdx_fbank_create: mode must be 0 (SV), 1 (ASR) or 2 (WeSpeaker)");
     tdx::Loader ld;       // (no blob: the tables are computed here, then staged and uploaded like weights)
     std::vector<float>& host = ld.host;
     const size_t oW = 0, nW = (size_t)2 * NBIN_PAD * NF;
@@ -193,7 +193,7 @@ int tdx_fbank_create(int mode, int device, tdx_fbank** out) {
     TRY(ld.finish("tdx_fbank_create", false, device, h->dev));
     const float* dev = h->dev;
     h->device = device;
-    h->mode = mode; h->scale = mode == 1 ? 32768.0f : 1.0f; h->Wdft = dev + oW; h->mel = dev + oM; h->win = dev + oWin;
+    h->mode = mode; h->scale = mode != 0 ? 32768.0f : 1.0f; h->Wdft = dev + oW; h->mel = dev + oM; h->win = dev + oWin;
     *out = h.release();
     return TDX_OK;
 }
@@ -233,7 +233,7 @@ int tdx_fbank_forward(tdx_fbank* h, const float* wav, int B, int N, float* feat,
         GemmArgs g = make_args(M, 128, make_seg(P, NBIN_PAD, h->mel, NBIN_PAD, NBIN_PAD));
         if (launch_gemm<false, false, false, false>(g, 1, EpiLogMel{feat}, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
     }
-    if (h->mode == 0) {
+    if (h->mode != 1) {
         hipLaunchKernelGGL(fbank_submean_kernel, dim3(B), dim3(320), 0, st, feat, F);
         LAUNCH_CHECK();
     }

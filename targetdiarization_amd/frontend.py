@@ -14,11 +14,12 @@ def _st(dev):
 
 class Fbank:
     """mode "sv": povey window, no scaling, per-utterance mean removed (ERes2NetV2 front-end);
-    mode "asr": hamming window, input x32768 (funasr WavFrontend before LFR/CMVN)."""
+    mode "asr": hamming window, input x32768 (funasr WavFrontend before LFR/CMVN);
+    mode "wespeaker": hamming window, input x32768, per-utterance mean removed (WeSpeaker ResNet34 front-end)."""
 
     def __init__(self, mode: str = "sv", device="cuda:0"):
         self._l = _lib.lib()
-        self._own = _lib.Handle(device, "Fbank", self._l.tdx_fbank_create, self._l.tdx_fbank_destroy, {"sv": 0, "asr": 1}[mode])
+        self._own = _lib.Handle(device, "Fbank", self._l.tdx_fbank_create, self._l.tdx_fbank_destroy, {"sv": 0, "asr": 1, "wespeaker": 2}[mode])
         self.device, self._h = self._own.device, self._own.ptr
 
     def frames(self, N: int) -> int:

@@ -7,10 +7,16 @@ Plain functions over two callables, so the whole pipeline runs on the CPU agains
     embed(list of 1-D clips)           -> [n,D] speaker embeddings (speaker.SpeakerEmbedder.get_speaker_embeddings)
 `PyannoteDiarizer` binds them to the device models.
 
-Deviations from pyannote: the embedder is the project's own (ERes2NetV2 on the samples of a speaker's frames, instead of
-wespeaker ResNet34 with a frame mask in its pooling), so the published clustering threshold is uncalibrated for it; a
-(chunk, speaker) without an embedding joins the cluster that the other chunks hear on its active frames (pyannote's
-distance to a NaN vector falls to cluster 0)."""
+A third, optional callable makes step (4) pyannote's own:
+    embed_masked(chunks [n,160000], masks [n,3,589]) -> [n,3,D]: every chunk embedded under the frame mask of each local
+    speaker (speaker.WeSpeakerResNet34: one trunk pass per chunk, pooled under the three masks); a non-finite row is a
+    missing embedding.  With WeSpeaker weights the published clustering threshold applies (parity with the published
+    checkpoint is unpinned: no weights can be fetched).
+
+Deviations from pyannote: without `embed_masked` the embedder is the project's own (ERes2NetV2 on the samples of a
+speaker's frames, instead of wespeaker ResNet34 with a frame mask in its pooling), and the published clustering threshold
+is uncalibrated for it; a (chunk, speaker) without an embedding joins the cluster that the other chunks hear on its active
+frames (pyannote's distance to a NaN vector falls to cluster 0)."""
 from __future__ import annotations
 
 import numpy as np
@@ -24,6 +30,7 @@ FRAMES = 589                   # frames of one chunk
 POWERSET = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1], [1, 1, 0], [1, 0, 1], [0, 1, 1]], dtype=np.int8)
 DEFAULT_THRESHOLD = 0.7045654963945799      # speaker-diarization-3.1's published clustering threshold
 MIN_CLUSTER_SIZE = 12
+MIN_NUM_FRAMES = 2             # ceil(589 * 400 / 160000): 400 samples is the shortest clip that yields one fbank frame [upstream-recall]
 
 
 def chunk_plan(n: int):
@@ -92,6 +99,24 @@ def gather_clips(chunks: np.ndarray, seg: np.ndarray, min_embed_sec: float = 0.4
             clips.append(np.concatenate(parts))
             owner.append((k, j))
     return clips, owner
+
+
+def pooling_masks(seg: np.ndarray, min_num_frames: int = MIN_NUM_FRAMES) -> np.ndarray:
+    """[n,F,S] binary -> [n,S,F] float32 pooling masks: a speaker's frames without overlap (`clean`) when there are more than
+    min_num_frames of them, else all its active frames"""
+    clean = seg * (seg.sum(axis=-1, keepdims=True) < 2)
+    few = clean.sum(axis=1, keepdims=True) <= min_num_frames
+    return np.ascontiguousarray(np.where(few, seg, clean).transpose(0, 2, 1), dtype=np.float32)
+
+
+def masked_embeddings(chunks: np.ndarray, seg: np.ndarray, embed_masked, min_num_frames: int = MIN_NUM_FRAMES):
+    """pyannote's step (4): -> (emb [m,D], [(chunk, speaker), ...]) of the speakers that are active somewhere in their chunk
+    and whose embedding came back finite; the others have none"""
+    E = np.asarray(embed_masked(chunks, pooling_masks(seg, min_num_frames)), dtype=np.float64)
+    active = seg.sum(axis=1) > 0
+    owner = [(k, j) for k in range(seg.shape[0]) for j in range(seg.shape[2]) if active[k, j] and np.isfinite(E[k, j]).all()]
+    emb = np.stack([E[k, j] for k, j in owner]) if owner else np.zeros((0, 1))
+    return emb, owner
 
 
 def _unit(x):
@@ -188,8 +213,10 @@ def tracks_of(on: np.ndarray, n_samples: int):
     return [(round(float(s), 3), round(float(e), 3), names[c]) for s, e, c in runs]
 
 
-def diarize(wave, segment, embed, threshold: float = DEFAULT_THRESHOLD, min_embed_sec: float = 0.4, min_cluster_size: int = MIN_CLUSTER_SIZE):
-    """16 kHz mono clip -> [(start_s, end_s, "SPEAKER_xx"), ...] (what od_result_parser reads)"""
+def diarize(wave, segment, embed, threshold: float = DEFAULT_THRESHOLD, min_embed_sec: float = 0.4, min_cluster_size: int = MIN_CLUSTER_SIZE,
+            embed_masked=None):
+    """16 kHz mono clip -> [(start_s, end_s, "SPEAKER_xx"), ...] (what od_result_parser reads).  With `embed_masked` the
+    embeddings are pooled under frame masks (module docstring) and `embed` / min_embed_sec are not used."""
     wave = np.asarray(wave, dtype=np.float32).reshape(-1)
     if wave.shape[0] == 0:
         return []
@@ -199,19 +226,25 @@ def diarize(wave, segment, embed, threshold: float = DEFAULT_THRESHOLD, min_embe
     count = speaker_count(seg, starts, total)
     if not count.any():
         return []
-    clips, owner = gather_clips(chunks, seg, min_embed_sec)
-    emb = np.asarray(embed(clips)) if clips else np.zeros((0, 1))
+    if embed_masked is not None:
+        emb, owner = masked_embeddings(chunks, seg, embed_masked)
+    else:
+        clips, owner = gather_clips(chunks, seg, min_embed_sec)
+        emb = np.asarray(embed(clips)) if clips else np.zeros((0, 1))
     clusters = assign_speakers(seg, starts, total, emb, owner, threshold, min_cluster_size)
     return tracks_of(reconstruct(seg, starts, total, clusters, count), wave.shape[0])
 
 
 class PyannoteDiarizer:
     """`od_pipeline(audio) -> [(start, end, "SPEAKER_xx"), ...]` on the device: segmentation.PyanNet for the chunks, `embed`
-    (HotPath.spk.get_speaker_embeddings, or any callable) for the cross-chunk identity.  threshold <= 0: the published one."""
+    (HotPath.spk.get_speaker_embeddings, or any callable) for the cross-chunk identity, or `embedder`
+    (speaker.WeSpeakerResNet34), which takes its place with masked pooling.  threshold <= 0: the published one."""
 
-    def __init__(self, model, embed, threshold: float = 0.0, min_embed_sec: float = 0.4, min_cluster_size: int = MIN_CLUSTER_SIZE):
+    def __init__(self, model, embed, threshold: float = 0.0, min_embed_sec: float = 0.4, min_cluster_size: int = MIN_CLUSTER_SIZE,
+                 embedder=None):
         self.model = model
         self.embed = embed
+        self.embedder = embedder
         self.threshold = float(threshold) if threshold and threshold > 0 else DEFAULT_THRESHOLD
         self.min_embed_sec = min_embed_sec
         self.min_cluster_size = min_cluster_size
@@ -220,15 +253,24 @@ class PyannoteDiarizer:
         import torch
         return self.model.log_probs(torch.from_numpy(np.ascontiguousarray(chunks, dtype=np.float32)).to(self.model.device)).cpu().numpy()
 
+    def embed_masked(self, chunks: np.ndarray, masks: np.ndarray) -> np.ndarray:
+        import torch
+        dev = self.embedder.device
+        return self.embedder(torch.from_numpy(np.ascontiguousarray(chunks, dtype=np.float32)).to(dev),
+                             torch.from_numpy(np.ascontiguousarray(masks, dtype=np.float32)).to(dev)).cpu().numpy()
+
     def __call__(self, audio):
-        return diarize(audio, self.segment, self.embed, self.threshold, self.min_embed_sec, self.min_cluster_size)
+        return diarize(audio, self.segment, self.embed, self.threshold, self.min_embed_sec, self.min_cluster_size,
+                       embed_masked=self.embed_masked if self.embedder is not None else None)
 
     def close(self):
         self.model.close()
+        if self.embedder is not None:
+            self.embedder.close()
 
 
 def load_model_dir(path):
-    """pyannote's segmentation checkpoint in a directory: pytorch_model.bin (the state dict, bare or under "state_dict");
+    """a pyannote checkpoint (segmentation or embedding) in a directory: pytorch_model.bin (the state dict, bare or under "state_dict");
     None when `path` is not such a directory"""
     import os
     if not isinstance(path, str) or not os.path.isdir(path):
@@ -243,16 +285,42 @@ def load_model_dir(path):
     return sd
 
 
-def build_od_pipeline(od_state_dict=None, od_model_dir=None, embed=None, threshold: float = 0.0, cuda_device: int = 0):
+def build_od_pipeline(od_state_dict=None, od_model_dir=None, embed=None, threshold: float = 0.0, cuda_device: int = 0,
+                      od_embed_state_dict=None, od_embed_model_dir=None):
     """The device overlap detector from weights, or from a directory holding pytorch_model.bin; None when there is neither
     source.  A directory that fails — an unreadable file, a checkpoint the loader rejects, no embedder to share — is reported
-    and leaves None, like the reference's other optional stages; weights handed in directly fail loudly."""
+    and leaves None, like the reference's other optional stages; weights handed in directly fail loudly.
+    od_embed_state_dict / od_embed_model_dir: WeSpeaker ResNet34 weights for the masked-pooling embedder, which then takes
+    the place of `embed`; a directory that fails is reported and leaves the `embed` path."""
     from .segmentation import PyanNet
 
+    def make_embedder():
+        from .speaker import WeSpeakerResNet34
+        if od_embed_state_dict is not None:
+            return WeSpeakerResNet34(od_embed_state_dict, device=f"cuda:{cuda_device}")
+        if od_embed_model_dir is None:
+            return None
+        try:
+            sd = load_model_dir(od_embed_model_dir)
+            if sd is None:
+                raise FileNotFoundError("no pytorch_model.bin")
+            return WeSpeakerResNet34(sd, device=f"cuda:{cuda_device}")
+        except Exception as e:
+            print(f"Failed to load the overlap detector's embedder from {od_embed_model_dir}: {e}")
+            return None
+
     def make(sd):
-        if embed is None:
-            raise ValueError("the overlap detector needs a speaker embedder: pass spk_state_dict or od_embed")
-        return PyannoteDiarizer(PyanNet(sd, device=f"cuda:{cuda_device}"), embed, threshold)
+        if embed is None and od_embed_state_dict is None and od_embed_model_dir is None:
+            raise ValueError("the overlap detector needs a speaker embedder: pass spk_state_dict, od_embed or od_embed_state_dict")
+        model = PyanNet(sd, device=f"cuda:{cuda_device}")
+        try:
+            embedder = make_embedder()
+            if embedder is None and embed is None:
+                raise ValueError("the overlap detector needs a speaker embedder: pass spk_state_dict or od_embed")
+        except BaseException:
+            model.close()
+            raise
+        return PyannoteDiarizer(model, embed, threshold, embedder=embedder)
 
     if od_state_dict is not None:
         return make(od_state_dict)

@@ -131,6 +131,7 @@ def env_to_kwargs(environ=None) -> Dict[str, Any]:
         "pyannote_clustering_threshold": num("PYANNOTE_CLUSTERING_THRESHOLD", float),
         "diarization_pipeline_dir": env.get("DIARIZATION_PIPELINE_DIR"),
         "od_model_dir": env.get("OD_MODEL_DIR"),
+        "od_embed_model_dir": env.get("OD_EMBED_MODEL_DIR"),
         "mdx_weights_file": env.get("MDX_WEIGHTS_FILE"),
         "embedding_model_dir": env.get("EMBEDDING_MODEL_DIR"),
         "asr_model_dir": env.get("ASR_MODEL_DIR"),

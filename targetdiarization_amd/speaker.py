@@ -1,5 +1,5 @@
-"""ERes2NetV2 and CAM++ speaker-embedding extractors over the C-ABI (tdx_eres2net_*, tdx_campp_*) and the
-TargetASR-compatible host methods (TargetASR.py:144-163)."""
+"""ERes2NetV2, CAM++ and WeSpeaker ResNet34 speaker-embedding extractors over the C-ABI (tdx_eres2net_*, tdx_campp_*,
+tdx_wespk_*) and the TargetASR-compatible host methods (TargetASR.py:144-163)."""
 from __future__ import annotations
 
 
@@ -87,6 +87,72 @@ class CAMPPlus:
         if wav.ndim == 1:
             wav = wav[None]
         return self.embed_features(self.fbank(wav))
+
+    def close(self):
+        self._own.close()
+        self.fbank.close()
+
+
+class WeSpeakerResNet34:
+    """WeSpeaker ResNet34 with pyannote's masked statistics pooling (csrc/wespeaker.hip): the embedder of pyannote
+    speaker-diarization-3.1; state_dict with upstream's names under `resnet.`.  One trunk pass per chunk, pooled under each of
+    the S frame masks.  Batches above max_chunks_per_launch are cut on the host."""
+
+    EMB = 256
+
+    def __init__(self, state_dict, device="cuda:0", max_chunks_per_launch: int = 16):
+        self._l = _lib.lib()
+        self._own = _lib.Handle(device, "WeSpeakerResNet34", self._l.tdx_wespk_create, self._l.tdx_wespk_destroy,
+                                blob=pack_blob(drop_num_batches_tracked(state_dict)))
+        self.device, self._h, self._guard = self._own.device, self._own.ptr, self._own.guard
+        self.max_chunks_per_launch = max(1, min(int(max_chunks_per_launch), 64))
+        self.fbank = Fbank("wespeaker", self.device)
+
+    @staticmethod
+    def flops(B, F):
+        """multiply-adds x 2 of the trunk and seg_1 for B chunks of F frames (one pooling)"""
+        fl, H, W, cin = 2.0 * 80 * F * 9 * 32, 80, F, 32
+        for li, nb in enumerate((3, 4, 6, 3)):
+            cout = 32 << li
+            for i in range(nb):
+                stride = 2 if (i == 0 and li > 0) else 1
+                H, W = (H - 1) // stride + 1, (W - 1) // stride + 1
+                fl += 2.0 * H * W * cout * (9 * cin + 9 * cout + (cin if (stride != 1 or cin != cout) else 0))
+                cin = cout
+        return float(B) * (fl + 2.0 * 5120 * 256)
+
+    def workspace_bytes(self, B, F, S=1):
+        return int(self._l.tdx_wespk_workspace_bytes(self._h, B, F, S))
+
+    def embed_features(self, feat: torch.Tensor, weights: torch.Tensor = None) -> torch.Tensor:
+        """feat [B,F,80] (Fbank("wespeaker")), weights None | [B,S,Fw] per-frame masks on any frame grid -> [B,S,256]
+        ([B,256] without weights); a row whose mask vanishes on the trunk's frames is NaN"""
+        feat = feat.to(self.device, torch.float32).contiguous()
+        B, F, _ = feat.shape
+        if weights is not None:
+            weights = weights.to(self.device, torch.float32).contiguous()
+            if weights.ndim != 3 or weights.shape[0] != B:
+                raise _lib.TdxError(f"WeSpeakerResNet34: weights must be [B,S,Fw] with B = {B}, got {tuple(weights.shape)}")
+        S, Fw = (1, 1) if weights is None else (int(weights.shape[1]), int(weights.shape[2]))
+        out = torch.empty(B, S, self.EMB, device=self.device)
+        with torch.cuda.device(self.device), self._guard.call():
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            for b0 in range(0, max(B, 1), self.max_chunks_per_launch):
+                nb_ = min(self.max_chunks_per_launch, B - b0)
+                nbytes = self.workspace_bytes(nb_, F, S) if self._h else 1
+                if nbytes == 0:
+                    raise _lib.TdxError("WeSpeakerResNet34: need 1 <= B, F >= 1, 1 <= S <= 8, Fw >= 1 and B*F*2560 < 2^31 per launch")
+                ws = self._guard.workspace(nbytes)
+                _lib.check(self._l.tdx_wespk_forward(self._h, feat[b0:b0 + nb_].data_ptr(), nb_, F,
+                                                     None if weights is None else weights[b0:b0 + nb_].data_ptr(), S, Fw,
+                                                     out[b0:b0 + nb_].data_ptr(), ws.data_ptr(), ws.numel(), st))
+        return out[:, 0] if weights is None else out
+
+    def __call__(self, wav: torch.Tensor, weights: torch.Tensor = None) -> torch.Tensor:
+        """wav [B,N] in [-1,1] -> [B,S,256] ([B,256] without weights); all B clips share N"""
+        if wav.ndim == 1:
+            wav = wav[None]
+        return self.embed_features(self.fbank(wav), weights)
 
     def close(self):
         self._own.close()

@@ -10,7 +10,9 @@ order of its steps, with two differences that are the point of the rewrite:
       sd_pipeline(audio) -> {"text": [[start, end, label], ...]}        (CAM++ modelscope pipeline, :73,:126)
       od_pipeline(audio) -> [(start, end, "SPEAKER_xx"), ...]           (pyannote itertracks, :84,:132; `od_state_dict` / an
                                                                             `od_model_dir` holding pytorch_model.bin puts the device
-                                                                            overlap detector here: overlap.PyannoteDiarizer)
+                                                                            overlap detector here: overlap.PyannoteDiarizer;
+                                                                            `od_embed_state_dict` / `od_embed_model_dir` give it
+                                                                            the WeSpeaker ResNet34 masked-pooling embedder)
       vad(audio)         -> [[start, end], ...] in seconds               (ASRProcessor.vad_detection :742; `vad_state_dict` /
                                                                             a funasr `vad_model_dir` puts the device FSMN-VAD here)
       decoder(encoder_out[T',512]) -> (text, [(token, [s, e]), ...][, language])   (CIF + NAR decoder)
@@ -53,7 +55,7 @@ class TargetDiarization:
                  vad: Optional[Callable] = None, decoder: Optional[Callable] = None, mdx_model: Optional[Callable] = None, token_list=None,
                  punctuation: Optional[Callable] = None, mdx_state_dict=None, mdx_args=None,
                  punc_state_dict=None, punc_vocab=None, restorer_state_dict=None, sd_state_dict=None, vad_state_dict=None, vad_cmvn=None,
-                 od_state_dict=None, od_embed: Optional[Callable] = None, **kwargs):
+                 od_state_dict=None, od_embed: Optional[Callable] = None, od_embed_state_dict=None, od_embed_model_dir=None, **kwargs):
         self.target_similarity_threshold = target_similarity_threshold
         self.asr_engine = asr_engine
         self.cuda_device = cuda_device
@@ -87,7 +89,10 @@ class TargetDiarization:
         if od_pipeline is None:               # pyannote's overlap-aware diarization on the device (overlap.py, tdx_pyannet_*); neither source: none
             from .overlap import build_od_pipeline
             embed = od_embed if od_embed is not None else (self.hp.spk.get_speaker_embeddings if self.hp.spk is not None else None)
-            self.od_pipeline = build_od_pipeline(od_state_dict, od_model_dir, embed, pyannote_clustering_threshold, cuda_device)
+            # od_embed_state_dict / od_embed_model_dir: WeSpeaker ResNet34 weights — pyannote's own masked-pooling embedder
+            # (speaker.WeSpeakerResNet34, tdx_wespk_*), under which the published clustering threshold applies; it wins over `embed`
+            self.od_pipeline = build_od_pipeline(od_state_dict, od_model_dir, embed, pyannote_clustering_threshold, cuda_device,
+                                                 od_embed_state_dict=od_embed_state_dict, od_embed_model_dir=od_embed_model_dir)
         # One model serves every request of the reference's server (main.py:42): REST handlers and WebSocket worker threads call
         # into it concurrently.  Each model object of the hot path serialises its own calls (_lib.HandleGuard); this lock keeps a
         # whole infer() — and, in stream mode, the processing of one released buffer — together, so that concurrent requests

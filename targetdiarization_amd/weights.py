@@ -783,3 +783,58 @@ def pack_silero_vad_blob(state_dict) -> bytes:
             continue
         sd[k[len("_model."):] if k.startswith("_model.") else k] = v
     return pack_blob(sd)
+
+
+# ---------------------------------------------------------------------------------------
+# WeSpeaker ResNet34 (wespeaker/models/resnet.py ResNet34: m_channels 32, feat_dim 80, embed_dim 256, TSTP,
+# two_emb_layer False; pyannote.audio WeSpeakerResNet34 keeps it under `resnet.`) [upstream-recall]: the source is not
+# vendored and no checkpoint is at hand, parity is unpinned; tests/wespeaker_oracle.py restates the forward and
+# csrc/wespeaker.hip loads exactly these names (strict both ways; num_batches_tracked is dropped before packing).
+# ---------------------------------------------------------------------------------------
+def wespeaker_param_shapes(m: int = 32, feat_dim: int = 80, emb: int = 256, blocks=(3, 4, 6, 3)) -> "OrderedDict[str, tuple]":
+    s = OrderedDict()
+
+    def bn(p, c):
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            s[p + leaf] = (c,)
+
+    s["resnet.conv1.weight"] = (m, 1, 3, 3); bn("resnet.bn1.", m)
+    cin = m
+    for li, nb in enumerate(blocks):
+        cout = m << li
+        for i in range(nb):
+            p = f"resnet.layer{li + 1}.{i}."
+            stride = 2 if (i == 0 and li > 0) else 1
+            s[p + "conv1.weight"] = (cout, cin, 3, 3); bn(p + "bn1.", cout)
+            s[p + "conv2.weight"] = (cout, cout, 3, 3); bn(p + "bn2.", cout)
+            if stride != 1 or cin != cout:
+                s[p + "shortcut.0.weight"] = (cout, cin, 1, 1); bn(p + "shortcut.1.", cout)
+            cin = cout
+    s["resnet.seg_1.weight"] = (emb, 2 * cin * (feat_dim // 8))
+    s["resnet.seg_1.bias"] = (emb,)
+    return s
+
+
+def recipe_wespeaker_state_dict(seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Deterministic fp32 weights for the WeSpeaker ResNet34 layout: fan-in scaled convolutions, BatchNorm gamma near 1.
+    The running statistics written here do not match the activations; the tests replace them with the ones of
+    tests/golden/wespeaker_calibration.json (one fp64 pass of the oracle over seeded synthetic voices), which keeps all
+    33 convolutions alive."""
+    out = OrderedDict()
+    for name, shape in wespeaker_param_shapes().items():
+        n = int(np.prod(shape))
+        u = torch.from_numpy(philox_uniform("wespk:" + name, n, seed)).reshape(shape)
+        leaf = name.rsplit(".", 1)[-1]
+        if leaf == "running_var":
+            t = 1.0 + 0.3 * u
+        elif leaf == "running_mean":
+            t = 0.1 * u
+        elif len(shape) == 1 and leaf == "weight":
+            t = 1.0 + 0.2 * u                      # BatchNorm gamma
+        elif leaf == "bias":
+            t = 0.1 * u
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            t = u * float(np.sqrt(3.0 / fan_in))
+        out[name] = t.to(torch.float32).contiguous()
+    return out
