@@ -430,6 +430,45 @@ size_t tdx_wespk_workspace_bytes(const tdx_wespk* h, int B, int F, int S);
 int tdx_wespk_forward(tdx_wespk* h, const float* feat_dev, int B, int F, const float* weights_dev, int S, int Fw,
                       float* emb_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * N9   SenseVoiceSmall — replaces `self.asr['sensevoice'].generate(input=wav, language=..., use_itn=True)`
+ *      ASRProcessor.py:398-402 (funasr SenseVoiceSmall: third-party, absent; parity unpinned [upstream-recall], LayerNorm eps
+ *      1e-12, the prompt order and the id tables included).  Rows per utterance: [embed[lid], embed[1], embed[2], embed[textnorm],
+ *      feats(0..T-1)], S = T + 4; x sqrt(512) + sinusoidal positions 1..S; encoders0 + (num_blocks - 1) encoders (the SANM layer
+ *      of tdx_pfenc: d 512, 4 heads, FSMN memory k = 11, FFN 2048), after_norm, tp_blocks tp_encoders, tp_norm; CTC head
+ *      log_softmax(Linear(512, vocab)) with blank = 0 and a greedy decode over all S frames (the four prompt frames yield the
+ *      language / emotion / event / text-norm tags).
+ *      blob: TDXW container with funasr's names (embed.weight [16,560], encoder.encoders0.0.*, encoder.encoders.{i}.*,
+ *      encoder.after_norm.*, encoder.tp_encoders.{i}.*, encoder.tp_norm.*, ctc.ctc_lo.weight [vocab,512], ctc.ctc_lo.bias); a
+ *      missing tensor is TDX_E_BLOB with its name in tdx_last_error(); other tensors of the checkpoint are ignored.
+ *      feats_dev [B,T,560] = tdx_lfr_cmvn output; the utterances of a call share T (callers bucket by length; no padding mask).
+ *      prompt_host: 4 ids in [0,16) = {lid, 1, 2, textnorm}, read during the call (not kept).
+ *      enc_dev: NULL or [B,S,512], the tp_norm output.  frame_ids_dev int32 [B,S] = argmax per frame (ties: the lowest id),
+ *      frame_score_dev [B,S] = log-softmax at the argmax.  tok_ids_dev / tok_frames_dev int32 [B,S], counts_dev int32 [B]: the
+ *      collapse below of frame_ids_dev with blank 0.  B * S < 2^22 (workspace_bytes returns 0 outside).
+ *      The head never stores the logits of a whole call; TDX_SV_HEAD in the environment of tdx_sv_create picks how (a property
+ *      of the handle): 1 = the fused kernel (64 rows staged in LDS, exact-fp32 MFMA sweep over 512-column vocabulary slices, one
+ *      (max, argmax, sum exp) triple per row and slice, merged by a second kernel: 12 * ceil(vocab / 512) workspace bytes per
+ *      row); 0 = chunks of TDX_SV_LOGITS_ROWS rows through the split-f16 x3 Linear into ONE logits buffer of that many rows, then
+ *      a row kernel; unset = the default as measured.  All launches go on the caller's stream, no host wait.
+ *
+ *      tdx_ctc_collapse: frame_ids_dev int32 [B,S] -> per utterance the ids left after dropping every frame whose id equals the
+ *      previous frame's and then every `blank`, compacted at the front of tok_ids_dev [B,S] (the rest `blank`), the first frame
+ *      of each kept run in tok_frames_dev [B,S] (the rest -1), their number in counts_dev [B].  Runs never merge across
+ *      utterances.  One launch, no host wait.
+ * ---------------------------------------------------------------------------------- */
+#define TDX_SV_LOGITS_ROWS 1024      /* cap of the TDX_SV_HEAD=0 logits buffer, in rows of up(vocab, 256) floats */
+typedef struct tdx_sv tdx_sv;
+int tdx_sv_create(int num_blocks, int tp_blocks, int vocab, const void* weights_blob, size_t blob_bytes, int device, tdx_sv** out);
+int tdx_sv_destroy(tdx_sv* h);
+size_t tdx_sv_workspace_bytes(const tdx_sv* h, int B, int T);
+double tdx_sv_flops(const tdx_sv* h, int B, int T);
+int tdx_sv_forward(tdx_sv* h, const float* feats_dev, int B, int T, const int* prompt_host, float* enc_dev, int* frame_ids_dev,
+                   float* frame_score_dev, int* tok_ids_dev, int* tok_frames_dev, int* counts_dev, void* workspace_dev,
+                   size_t workspace_bytes, void* stream);
+int tdx_ctc_collapse(const int* frame_ids_dev, int B, int S, int blank, int* tok_ids_dev, int* tok_frames_dev, int* counts_dev,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

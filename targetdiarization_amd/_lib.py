@@ -116,6 +116,12 @@ SIGNATURES = {
     "tdx_wespk_destroy": (_i, [_vp]),
     "tdx_wespk_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "tdx_wespk_forward": (_i, [_vp, _fp, _i, _i, _fp, _i, _i, _fp, _vp, _sz, _vp]),
+    "tdx_sv_create": (_i, [_i, _i, _i, _vp, _sz, _i, C.POINTER(_vp)]),
+    "tdx_sv_destroy": (_i, [_vp]),
+    "tdx_sv_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "tdx_sv_flops": (C.c_double, [_vp, _i, _i]),
+    "tdx_sv_forward": (_i, [_vp, _fp, _i, _i, C.POINTER(C.c_int), _fp, _vp, _fp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tdx_ctc_collapse": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -19,7 +19,8 @@ class ASRProcessor:
                  is_emotion: bool = False, emotion_model_dir: str = "", is_diarization: bool = False, diarization_model_dir: str = "",
                  is_asr_api: bool = False, api_config_path: str = "", verbose_log: bool = True, cuda_device: int = 0, ap=None,
                  *, asr_state_dict=None, decoder: Optional[Callable] = None, punctuation: Optional[Callable] = None, token_list=None,
-                 punc_state_dict=None, punc_vocab=None, vad_state_dict=None, vad_cmvn=None):
+                 punc_state_dict=None, punc_vocab=None, vad_state_dict=None, vad_cmvn=None,
+                 sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None):
         self.is_asr = is_asr
         self.verbose_log = verbose_log
         self.ap = ap
@@ -57,6 +58,13 @@ class ASRProcessor:
             except Exception as e:                       # ASRProcessor.py:215-264: print, feature off
                 print(f"Load ASR model failed: {e}")
                 self.is_asr = False
+        if is_asr and sensevoice_state_dict is not None:         # ASRProcessor.py:215-264: a second engine next to the first; print, leave it out
+            try:
+                from .sensevoice import build_sensevoice
+                self.asr["sensevoice"] = build_sensevoice(sensevoice_state_dict, sensevoice_token_list, sensevoice_cmvn, cuda_device=cuda_device)
+                self.is_asr = True
+            except Exception as e:
+                print(f"Load ASR model failed: {e}")
 
     def _nar_decode(self, enc_out):
         """encoder output [T',512] -> {"text", "timestamp"} through the device CIF predictor + NAR decoder"""
@@ -155,15 +163,28 @@ class ASRProcessor:
     def asr_detection(self, wav_file, language: str = "auto", prompt: str = "", asr_engine: str = "paraformer", no_punc: bool = False,
                       output_text_only: bool = False, output_raw_result: bool = False):
         result_list = []
-        if not self.is_asr or not self.asr or self.decoder is None:
+        if not self.is_asr or not self.asr:
             print("ASR models haven't been loaded. Return empty result.")
             return "" if output_text_only else result_list
-        if asr_engine.lower() != "paraformer":
+        asr_engine = asr_engine.lower()
+        if asr_engine not in self.asr:                   # :390-391 (an engine that is not loaded falls back too, where the reference raises KeyError)
             asr_engine = list(self.asr.keys())[0]
+        if asr_engine == "paraformer" and self.decoder is None:
+            print("ASR models haven't been loaded. Return empty result.")
+            return "" if output_text_only else result_list
         if isinstance(wav_file, (str, bytes)):
             raise ValueError("asr_detection: pass 16 kHz float32 numpy audio (file decoding is outside the MI355X hot path)")
         import torch
         wavs = wav_file if isinstance(wav_file, list) else [wav_file]
+        if asr_engine == "sensevoice":                   # :398-421
+            from .sensevoice import join_text_only, parse_tagged_text
+            res = self.asr["sensevoice"].generate(wavs, language=language, use_itn=True)
+            if output_raw_result:
+                return res
+            for clip in res:
+                lang, emo, text = parse_tagged_text(clip["text"], no_punc)
+                result_list.append({"key": clip["key"], "language": lang, "text": text, "emotion": emo})
+            return join_text_only(result_list) if output_text_only else result_list
         enc = self.asr["paraformer"]
         for k, w in enumerate(wavs):
             x = torch.from_numpy(np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(1, -1)))

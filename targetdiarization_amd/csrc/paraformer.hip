@@ -19,6 +19,7 @@
 #include "tdx_common.hpp"
 #include "weight_planes.hpp"
 #include "epilogues.hpp"
+#include "pf_sanm.hpp"
 
 using namespace tdx;
 
@@ -29,19 +30,21 @@ constexpr float PF_LN_EPS = 1e-12f;
 
 
 
-// x*sqrt(512) + sinusoidal PE (positions 1..T, [sin|cos] halves over the 560 input dims),
-// zero-padded to 576 columns.   funasr SinusoidalPositionEncoder / SANMEncoder.forward
-__global__ void pf_embed_kernel(const float* __restrict__ feats, float* __restrict__ x, int T) {
-    const int t = blockIdx.x, b = blockIdx.y;
+// x*sqrt(512) + sinusoidal PE (positions 1..S, [sin|cos] halves over the 560 input dims), zero-padded to 576 columns.
+// funasr SinusoidalPositionEncoder / SANMEncoder.forward.  Rows of an utterance: nprompt rows of the embedding table `embed` (ids
+// pr.id[], SenseVoiceSmall's prompt; 0 for Paraformer) and then its T feature rows: S = nprompt + T.
+__global__ void pf_embed_kernel(const float* __restrict__ feats, const float* __restrict__ embed, PfPrompt pr, int nprompt, float* __restrict__ x, int T) {
+    const int t = blockIdx.x, b = blockIdx.y, S = nprompt + T;
     const float pos = (float)(t + 1);
     const float inc = 9.210340371976184f / (float)(DIN / 2 - 1);     // log(10000)/(depth/2-1)
-    const long row = (long)b * T + t;
+    const long row = (long)b * S + t;
+    const float* src = t < nprompt ? embed + (long)pr.id[t] * DIN : feats + ((long)b * T + (t - nprompt)) * DIN;
     for (int c = threadIdx.x; c < DINP; c += blockDim.x) {
         float v = 0.f;
         if (c < DIN) {
             const int i = c < DIN / 2 ? c : c - DIN / 2;
             const float ang = __fmul_rn(pos, expf((float)i * (-inc)));
-            v = feats[row * DIN + c] * 22.627416997969522f + (c < DIN / 2 ? sinf(ang) : cosf(ang));
+            v = src[c] * 22.627416997969522f + (c < DIN / 2 ? sinf(ang) : cosf(ang));
         }
         x[row * DINP + c] = v;
     }
@@ -265,7 +268,6 @@ struct EpiCtx { float* ctx; int S;                      // head h of batch b -> 
     __device__ EpiNone row(int, int) const { return EpiNone{}; }
     __device__ void store(int z, int m, int n, float v, EpiNone, EpiNone) const {
         ctx[((long)(z / H) * S + m) * D + (z % H) * DK + n] = v; } };
-struct PfLayer { const float *Wqkv, *bqkv, *fsmnT, *Wo, *bo, *W1, *b1, *W2, *b2, *n1g, *n1b, *n2g, *n2b; H3W hqkv, ho, h1, h2; };
 
 // SPLIT-K for small row counts.  One clip per call (the reference's call pattern) has a few hundred rows: one or two x3 tiles
 // per Linear, each walking its whole K loop alone (K = 2048: 128 stages ~ 190 us, most CUs idle).  The K range is cut into
@@ -343,24 +345,9 @@ int tdx_pfenc_create(int num_blocks, const void* blob, size_t blob_bytes, int de
     if (!blob || !out || num_blocks < 1) return tdx::fail(TDX_E_INVALID, "tdx_pfenc_create: bad argument");
     tdx::Loader ld;       // (not strict: the encoder's tensors are read out of the whole model's checkpoint)
     if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_pfenc_create: malformed TDXW blob");
-    struct Off { size_t Wqkv, bqkv, fsmnT, Wo, bo, W1, b1, W2, b2, n1g, n1b, n2g, n2b; };
-    std::vector<Off> offs(num_blocks);
-    for (int l = 0; l < num_blocks && ld.ok(); ++l) {
-        const std::string p = l == 0 ? std::string("encoder.encoders0.0.") : "encoder.encoders." + std::to_string(l - 1) + ".";
-        const int din = l == 0 ? DIN : D, dinp = l == 0 ? DINP : D;
-        Off& o = offs[l];
-        o.Wqkv = ld.push_rows_padded(ld.get(p + "self_attn.linear_q_k_v.weight", (size_t)3 * D * din), 3 * D, din, dinp);       // K padded 560 -> 576 with zeros
-        o.bqkv = ld.push(ld.get(p + "self_attn.linear_q_k_v.bias", 3 * D), 3 * D);
-        o.fsmnT = ld.push_tapmajor(ld.get(p + "self_attn.fsmn_block.weight", (size_t)D * KS), D, KS);
-        o.Wo = ld.push(ld.get(p + "self_attn.linear_out.weight", (size_t)D * D), (size_t)D * D);
-        o.bo = ld.push(ld.get(p + "self_attn.linear_out.bias", D), D);
-        o.W1 = ld.push(ld.get(p + "feed_forward.w_1.weight", (size_t)FFN * D), (size_t)FFN * D);
-        o.b1 = ld.push(ld.get(p + "feed_forward.w_1.bias", FFN), FFN);
-        o.W2 = ld.push(ld.get(p + "feed_forward.w_2.weight", (size_t)D * FFN), (size_t)D * FFN);
-        o.b2 = ld.push(ld.get(p + "feed_forward.w_2.bias", D), D);
-        o.n1g = ld.push(ld.get(p + "norm1.weight", din), din); o.n1b = ld.push(ld.get(p + "norm1.bias", din), din);
-        o.n2g = ld.push(ld.get(p + "norm2.weight", D), D); o.n2b = ld.push(ld.get(p + "norm2.bias", D), D);
-    }
+    std::vector<PfLayerOff> offs(num_blocks);
+    for (int l = 0; l < num_blocks && ld.ok(); ++l)
+        pf_stage_layer(ld, l == 0 ? std::string("encoder.encoders0.0.") : "encoder.encoders." + std::to_string(l - 1) + ".", l == 0, offs[l]);
     size_t ang = 0, anb = 0;
     if (ld.ok()) { ang = ld.push(ld.get("encoder.after_norm.weight", D), D); anb = ld.push(ld.get("encoder.after_norm.bias", D), D); }
     std::unique_ptr<tdx_pfenc> h(new tdx_pfenc());
@@ -368,20 +355,10 @@ int tdx_pfenc_create(int num_blocks, const void* blob, size_t blob_bytes, int de
     TRY(ld.finish("tdx_pfenc_create", false, device, h->dev));
     const float* dev = h->dev;
     h->L = num_blocks; h->layers.resize(num_blocks);
-    for (int l = 0; l < num_blocks; ++l) {
-        const Off& o = offs[l]; PfLayer& w = h->layers[l];
-        w.Wqkv = dev + o.Wqkv; w.bqkv = dev + o.bqkv; w.fsmnT = dev + o.fsmnT; w.Wo = dev + o.Wo; w.bo = dev + o.bo; w.W1 = dev + o.W1;
-        w.b1 = dev + o.b1; w.W2 = dev + o.W2; w.b2 = dev + o.b2; w.n1g = dev + o.n1g; w.n1b = dev + o.n1b; w.n2g = dev + o.n2g; w.n2b = dev + o.n2b;
-    }
     h->ang = dev + ang; h->anb = dev + anb;
     {   // every nn.Linear weight as split-f16 planes + row scales, once
         std::vector<tdx::PlaneJob> jobs;
-        auto job = [&](const float* w, int N, int K, H3W& dst) { jobs.push_back({w, N, K, &dst.p, &dst.s}); };
-        for (int l = 0; l < num_blocks; ++l) {
-            PfLayer& w = h->layers[l];
-            job(w.Wqkv, 3 * D, l == 0 ? DINP : D, w.hqkv); job(w.Wo, D, D, w.ho);
-            job(w.W1, FFN, D, w.h1); job(w.W2, D, FFN, w.h2);
-        }
+        for (int l = 0; l < num_blocks; ++l) pf_bind_layer(dev, offs[l], l == 0, h->layers[l], jobs);
         TRY(tdx::split_weight_planes(jobs, device, h->dev_planes));
     }
     *out = h.release();
@@ -395,9 +372,7 @@ int tdx_pfenc_destroy(tdx_pfenc* h) {
 
 size_t tdx_pfenc_workspace_bytes(const tdx_pfenc* h, int B, int T) {
     if (!h || B < 1 || T < 1) return 0;
-    const size_t M = (size_t)B * T, Sp = (size_t)(T + 127) / 128 * 128;
-    return (al(M * D) + al(M * DINP) + al(M * DINP) + al((M + 128) * 3 * D) + al((size_t)B * H * Sp * Sp) + al(M * D) + al(M * D) +
-            al(M * FFN) + al(M * FFN) + al(M) + 8 * al(M) + PF_SLAB) * sizeof(float);      // + planes of the current GEMM's A operand (<= 2048 wide), its row scales, the 8 segment scales of the FFN planes, split-K slab
+    return pf_work_floats(B, T) * sizeof(float);
 }
 
 double tdx_pfenc_flops(const tdx_pfenc* h, int B, int T) {
@@ -418,22 +393,66 @@ int tdx_pfenc_forward(tdx_pfenc* h, const float* feats, const int* lens_host, in
     if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
     hipStream_t st = (hipStream_t)stream;
     const long M = (long)B * T;
-    const int Sp = (T + 127) / 128 * 128;
-    float* ws = (float*)ws_;
-    float* x = ws; float* xin = x + al(M * D); float* hbuf = xin + al(M * DINP); float* qkv = hbuf + al(M * DINP);
-    float* sc = qkv + al((M + 128) * 3 * D); float* ctx = sc + al((size_t)B * H * Sp * Sp); float* mem = ctx + al(M * D);
-    float* ffn = mem + al(M * D);
-    unsigned char* hp = (unsigned char*)(ffn + al(M * FFN));
-    float* hs = (float*)hp + al(M * FFN);
-    const dim3 rows4((unsigned)((M + 3) / 4));
-    float* hs8 = hs + al(M);                        // row scales of the FFN activation planes: one per (row, 256-channel segment), [8][M]
-    float* slab = hs8 + 8 * al(M);                  // split-K partial sums of the small-row path
+    const PfWork k = pf_carve((float*)ws_, M, B, T);
+    float* x = k.x;
+    TRY(pf_embed_rows(feats, nullptr, PfPrompt{}, 0, k.xin, B, T, st));
+    TRY(pf_run_layers(h->layers.data(), h->L, true, x, k, B, T, st));
+    return pf_layernorm_rows(x, h->ang, h->anb, out, M, st);
+}
 
-    hipLaunchKernelGGL(pf_embed_kernel, dim3(T, B), dim3(256), 0, st, feats, xin, T);
-    LAUNCH_CHECK();
-    for (int l = 0; l < h->L; ++l) {
-        const PfLayer& w = h->layers[l];
-        const bool first = l == 0;
+}  // extern "C"
+
+
+// ---- the pieces SenseVoiceSmall shares (pf_sanm.hpp; csrc/sensevoice.hip): ONE SANM layer implementation for both models ----
+size_t pf_work_floats(size_t B, size_t T) {
+    const size_t M = B * T, Sp = (T + 127) / 128 * 128;
+    return al(M * D) + al(M * DINP) + al(M * DINP) + al((M + 128) * 3 * D) + al(B * H * Sp * Sp) + al(M * D) + al(M * D) +
+           al(M * FFN) + al(M * FFN) + al(M) + 8 * al(M) + PF_SLAB;      // + planes of the current GEMM's A operand (<= 2048 wide), its row scales, the 8 segment scales of the FFN planes, split-K slab
+}
+PfWork pf_carve(float* ws, long M, int B, int T) {
+    const int Sp = (T + 127) / 128 * 128;
+    PfWork k;
+    k.x = ws; k.xin = k.x + al(M * D); float* hbuf = k.xin + al(M * DINP); k.qkv = hbuf + al(M * DINP);
+    k.sc = k.qkv + al((M + 128) * 3 * D); k.ctx = k.sc + al((size_t)B * H * Sp * Sp); k.mem = k.ctx + al(M * D);
+    k.ffn = k.mem + al(M * D);
+    k.hp = (unsigned char*)(k.ffn + al(M * FFN));
+    k.hs = (float*)k.hp + al(M * FFN);
+    k.hs8 = k.hs + al(M);                        // row scales of the FFN activation planes: one per (row, 256-channel segment), [8][M]
+    k.slab = k.hs8 + 8 * al(M);                  // split-K partial sums of the small-row path
+    return k;
+}
+void pf_stage_layer(tdx::Loader& ld, const std::string& p, bool wide, PfLayerOff& o) {
+    const int din = wide ? DIN : D, dinp = wide ? DINP : D;
+    o.Wqkv = ld.push_rows_padded(ld.get(p + "self_attn.linear_q_k_v.weight", (size_t)3 * D * din), 3 * D, din, dinp);       // K padded 560 -> 576 with zeros
+    o.bqkv = ld.push(ld.get(p + "self_attn.linear_q_k_v.bias", 3 * D), 3 * D);
+    o.fsmnT = ld.push_tapmajor(ld.get(p + "self_attn.fsmn_block.weight", (size_t)D * KS), D, KS);
+    o.Wo = ld.push(ld.get(p + "self_attn.linear_out.weight", (size_t)D * D), (size_t)D * D);
+    o.bo = ld.push(ld.get(p + "self_attn.linear_out.bias", D), D);
+    o.W1 = ld.push(ld.get(p + "feed_forward.w_1.weight", (size_t)FFN * D), (size_t)FFN * D);
+    o.b1 = ld.push(ld.get(p + "feed_forward.w_1.bias", FFN), FFN);
+    o.W2 = ld.push(ld.get(p + "feed_forward.w_2.weight", (size_t)D * FFN), (size_t)D * FFN);
+    o.b2 = ld.push(ld.get(p + "feed_forward.w_2.bias", D), D);
+    o.n1g = ld.push(ld.get(p + "norm1.weight", din), din); o.n1b = ld.push(ld.get(p + "norm1.bias", din), din);
+    o.n2g = ld.push(ld.get(p + "norm2.weight", D), D); o.n2b = ld.push(ld.get(p + "norm2.bias", D), D);
+}
+void pf_bind_layer(const float* dev, const PfLayerOff& o, bool wide, PfLayer& w, std::vector<tdx::PlaneJob>& jobs) {
+    w.Wqkv = dev + o.Wqkv; w.bqkv = dev + o.bqkv; w.fsmnT = dev + o.fsmnT; w.Wo = dev + o.Wo; w.bo = dev + o.bo; w.W1 = dev + o.W1;
+    w.b1 = dev + o.b1; w.W2 = dev + o.W2; w.b2 = dev + o.b2; w.n1g = dev + o.n1g; w.n1b = dev + o.n1b; w.n2g = dev + o.n2g; w.n2b = dev + o.n2b;
+    auto job = [&](const float* m, int N, int K, H3W& dst) { jobs.push_back({m, N, K, &dst.p, &dst.s}); };
+    job(w.Wqkv, 3 * D, wide ? DINP : D, w.hqkv); job(w.Wo, D, D, w.ho);
+    job(w.W1, FFN, D, w.h1); job(w.W2, D, FFN, w.h2);
+}
+// n SANM layers over the residual stream x [B*T][512], in place.  wide_first: layer 0 is the 560 -> 512 layer (encoders0): it reads
+// k.xin [B*T][576] and has no residual around its attention.
+int pf_run_layers(const PfLayer* layers, int n, bool wide_first, float* x, const PfWork& k, int B, int T, hipStream_t st) {
+    const long M = (long)B * T;
+    const int Sp = (T + 127) / 128 * 128;
+    float *xin = k.xin, *qkv = k.qkv, *sc = k.sc, *ctx = k.ctx, *mem = k.mem, *ffn = k.ffn, *hs = k.hs, *hs8 = k.hs8, *slab = k.slab;
+    unsigned char* hp = k.hp;
+    const dim3 rows4((unsigned)((M + 3) / 4));
+    for (int l = 0; l < n; ++l) {
+        const PfLayer& w = layers[l];
+        const bool first = wide_first && l == 0;
         const float* xl = first ? xin : x;
         const long ldx = first ? DINP : D;
         const int din = first ? DIN : D, dinp = first ? DINP : D;
@@ -501,12 +520,20 @@ int tdx_pfenc_forward(tdx_pfenc* h, const float* feats, const int* lens_host, in
         else TRY(linear_h3(hp, hs, (int)M, w.h2, D, FFN, EpiBiasRes<>{w.b2, x, x, D}, st));
         }
     }
-    hipLaunchKernelGGL(pf_layernorm_kernel, rows4, dim3(256), 0, st, x, (long)D, D, h->ang, h->anb, out, (long)D, D, M, PF_LN_EPS);
+    return TDX_OK;
+}
+// the encoder entry: [B][nprompt + T] rows of [prompt embeddings | feats] -> x [B][nprompt + T][576]
+int pf_embed_rows(const float* feats, const float* embed, PfPrompt pr, int nprompt, float* x, int B, int T, hipStream_t st) {
+    hipLaunchKernelGGL(pf_embed_kernel, dim3(nprompt + T, B), dim3(256), 0, st, feats, embed, pr, nprompt, x, T);
     LAUNCH_CHECK();
     return TDX_OK;
 }
-
-}  // extern "C"
+// out = LayerNorm(x) over rows of 512 (eps 1e-12), fp32
+int pf_layernorm_rows(const float* x, const float* g, const float* b, float* out, long M, hipStream_t st) {
+    hipLaunchKernelGGL(pf_layernorm_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, (long)D, D, g, b, out, (long)D, D, M, PF_LN_EPS);
+    LAUNCH_CHECK();
+    return TDX_OK;
+}
 
 
 // =====================================================================================================================
@@ -684,6 +711,13 @@ __global__ __launch_bounds__(256) void pf_argmax_kernel(const float* __restrict_
 struct PfDecLayer { H3W h1, h2, hq, hkv, ho; const float *W1, *W2, *Wq, *Wkv, *Wo; const float *b1, *fg, *fb, *n1g, *n1b, *n2g, *n2b, *n3g, *n3b, *fsmnT, *bq, *bkv, *bo; };
 
 }  // namespace
+
+// ids[m] = argmax over the first V columns of logits[m] (ties: the lowest id), score[m] = log-softmax there (shared with sensevoice.hip)
+int pf_argmax_rows(const float* logits, long ld, int V, int* ids, float* score, long M, hipStream_t st) {
+    hipLaunchKernelGGL(pf_argmax_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, logits, ld, V, ids, score, M);
+    LAUNCH_CHECK();
+    return TDX_OK;
+}
 
 struct tdx_pfdec {
     int device = 0;
@@ -896,9 +930,7 @@ int tdx_pfdec_decode(tdx_pfdec* h, const float* emb, int emb_rows, const int* co
     hipLaunchKernelGGL(pf_layernorm_planes_kernel_t<2>, rows4, dim3(256), 0, st, tgt, (long)D, D, h->ang, h->anb, hp, hs, D, M, PF_LN_EPS);
     LAUNCH_CHECK();
     TRY(linear_h3(hp, hs, (int)M, h->hout, h->vpad, D, EpiBiasAct<>{h->bout, logits, h->vpad}, st));
-    hipLaunchKernelGGL(pf_argmax_kernel, rows4, dim3(256), 0, st, logits, (long)h->vpad, h->vocab, ids, score, M);
-    LAUNCH_CHECK();
-    return TDX_OK;
+    return pf_argmax_rows(logits, (long)h->vpad, h->vocab, ids, score, M, st);
 }
 
 }  // extern "C"

@@ -62,7 +62,9 @@ class HotPath:
     def __init__(self, sep_state_dict, spk_state_dict=None, asr_state_dict=None, cuda_device: int = 0,
                  asr_segment: int = 480000, cmvn_shift=None, cmvn_scale=None, windows_per_launch: int = 32,
                  asr_rows_per_launch: int = 32768, mdx_model=None, mdx_weights_file: str = "mdx/weights/UVR-MDX-NET-Inst_HQ_3.onnx",
-                 mdx_state_dict=None, mdx_args=None, restorer_state_dict=None, restorer_weights_folder: str | None = None):
+                 mdx_state_dict=None, mdx_args=None, restorer_state_dict=None, restorer_weights_folder: str | None = None,
+                 sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None, sensevoice_model_dir=None,
+                 sensevoice_token_file=None):
         from .audio_processor import AudioProcessor
         self.device = torch.device(f"cuda:{cuda_device}")
         self.ap = AudioProcessor(is_separate_audio=True, separater_state_dict=sep_state_dict, cuda_device=cuda_device, verbose_log=False,
@@ -85,6 +87,9 @@ class HotPath:
             self.asr = ParaformerEncoder(enc_sd, self.device, cmvn_shift=cmvn_shift, cmvn_scale=cmvn_scale)
             if any(k.startswith("decoder.decoders.") for k in asr_state_dict):       # CIF predictor + NAR decoder (N2)
                 self.dec = ParaformerDecoder(asr_state_dict, self.device)
+        # SenseVoiceSmall (sensevoice.py, tdx_sv_*): the recogniser of asr_engine="sensevoice"; None without weights
+        from .sensevoice import build_sensevoice
+        self.sv = build_sensevoice(sensevoice_state_dict, sensevoice_token_list, sensevoice_cmvn, sensevoice_model_dir, sensevoice_token_file, cuda_device)
         self.asr_segment = asr_segment
         self.windows_per_launch = windows_per_launch
         self.asr_rows_per_launch = asr_rows_per_launch
@@ -186,6 +191,25 @@ class HotPath:
                 dres[si].append(r)
         enc = [(r[0] if len(r) == 1 else torch.cat(r, dim=0)) if r else torch.zeros(0, 512, device=self.device) for r in res]
         return (enc, dres) if decode else enc
+
+    def recognise_sensevoice(self, streams, language: str = "auto", use_itn: bool = True):
+        """H3 with SenseVoiceSmall: the streams cut into the same <= 30 s segments, equal-length segments batched (<= asr_rows_per_launch
+        LFR frames per launch sequence) -> per stream the list of its segments' {"text", "token_ids", "frames", "scores"}"""
+        if self.sv is None:
+            from ._lib import TdxError
+            raise TdxError("recognise_sensevoice needs the SenseVoice weights (sensevoice_state_dict / sensevoice_model_dir)")
+        streams = [self._dev(s) for s in streams]
+        segs, owner = [], []
+        for si, s in enumerate(streams):
+            for a in range(0, int(s.shape[0]), self.asr_segment):
+                seg = s[a:a + self.asr_segment]
+                if seg.shape[0] >= 400:
+                    segs.append(seg); owner.append(si)
+        self.sv.rows_per_launch = self.asr_rows_per_launch
+        res = [[] for _ in streams]
+        for si, r in zip(owner, self.sv.generate(segs, language=language, use_itn=use_itn) if segs else []):
+            res[si].append(r)
+        return res
 
     def encode_streams(self, streams):
         """host form: list of [T_i,512] numpy arrays"""

@@ -118,7 +118,9 @@ def load_dotenv(path: str = ".env", environ=None) -> bool:
 def env_to_kwargs(environ=None) -> Dict[str, Any]:
     """main.py:106-129 verbatim in meaning: environment names -> TargetDiarizationStream constructor kwargs; unset variables are left to
     the constructor defaults, EXCEPT the three flags the reference always passes (VERBOSE_LOG == "1"; IS_VAD_BUFFER and
-    USE_ASR_PROMPT true unless "0").  (ASR_ENGINE is in .env.example but main.py does not read it — neither does this.)"""
+    USE_ASR_PROMPT true unless "0").  (ASR_ENGINE is in .env.example but main.py does not read it — neither does this.)
+    SENSEVOICE_MODEL_DIR (funasr's model.pt + am.mvn) and SENSEVOICE_TOKEN_FILE (the piece table) are this project's: where the device
+    SenseVoiceSmall of asr_engine="sensevoice" loads from."""
     import os
     env = os.environ if environ is None else environ
 
@@ -135,6 +137,8 @@ def env_to_kwargs(environ=None) -> Dict[str, Any]:
         "mdx_weights_file": env.get("MDX_WEIGHTS_FILE"),
         "embedding_model_dir": env.get("EMBEDDING_MODEL_DIR"),
         "asr_model_dir": env.get("ASR_MODEL_DIR"),
+        "sensevoice_model_dir": env.get("SENSEVOICE_MODEL_DIR"),
+        "sensevoice_token_file": env.get("SENSEVOICE_TOKEN_FILE"),
         "vad_model_dir": env.get("VAD_MODEL_DIR"),
         "silero_model_file": env.get("SILERO_VAD_MODEL"),
         "separater_weights_folder": env.get("SEPARATER_WEIGHTS_FOLDER"),

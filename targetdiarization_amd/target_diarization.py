@@ -17,6 +17,8 @@ order of its steps, with two differences that are the point of the rewrite:
                                                                             a funasr `vad_model_dir` puts the device FSMN-VAD here)
       decoder(encoder_out[T',512]) -> (text, [(token, [s, e]), ...][, language])   (CIF + NAR decoder)
       punctuation(text)  -> text                                          (CT-Transformer, ASRProcessor.py:880-897)
+    `asr_engine="sensevoice"` with `sensevoice_state_dict` (+ `sensevoice_token_list`, `sensevoice_cmvn`) or a `sensevoice_model_dir` holding
+    funasr's model.pt and am.mvn (+ `sensevoice_token_file`) runs H3 through the device SenseVoiceSmall (sensevoice.py, csrc/sensevoice.hip).
     `sd_state_dict` (CAM++ weights, 3D-Speaker names) or a `diarization_pipeline_dir` holding campplus_cn_common.bin puts the
     device diarizer (diarization.CamppDiarizer, csrc/campplus.hip) behind sd_pipeline.
     Defaults: one segment per utterance / no overlap detector / whole clip is speech / the device decoder / text unchanged.
@@ -55,7 +57,9 @@ class TargetDiarization:
                  vad: Optional[Callable] = None, decoder: Optional[Callable] = None, mdx_model: Optional[Callable] = None, token_list=None,
                  punctuation: Optional[Callable] = None, mdx_state_dict=None, mdx_args=None,
                  punc_state_dict=None, punc_vocab=None, restorer_state_dict=None, sd_state_dict=None, vad_state_dict=None, vad_cmvn=None,
-                 od_state_dict=None, od_embed: Optional[Callable] = None, od_embed_state_dict=None, od_embed_model_dir=None, **kwargs):
+                 od_state_dict=None, od_embed: Optional[Callable] = None, od_embed_state_dict=None, od_embed_model_dir=None,
+                 sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None, sensevoice_model_dir=None,
+                 sensevoice_token_file=None, **kwargs):
         self.target_similarity_threshold = target_similarity_threshold
         self.asr_engine = asr_engine
         self.cuda_device = cuda_device
@@ -85,7 +89,9 @@ class TargetDiarization:
                 self.sd_pipeline = CamppDiarizer(sd_state_dict, cuda_device=cuda_device, vad=self.vad)
         self.hp = HotPath(sep_state_dict, spk_state_dict, asr_state_dict, cuda_device=cuda_device, mdx_model=mdx_model,
                           mdx_weights_file=mdx_weights_file, mdx_state_dict=mdx_state_dict, mdx_args=mdx_args,
-                          restorer_state_dict=restorer_state_dict, restorer_weights_folder=restorer_weights_folder)
+                          restorer_state_dict=restorer_state_dict, restorer_weights_folder=restorer_weights_folder,
+                          sensevoice_state_dict=sensevoice_state_dict, sensevoice_token_list=sensevoice_token_list, sensevoice_cmvn=sensevoice_cmvn,
+                          sensevoice_model_dir=sensevoice_model_dir, sensevoice_token_file=sensevoice_token_file)
         if od_pipeline is None:               # pyannote's overlap-aware diarization on the device (overlap.py, tdx_pyannet_*); neither source: none
             from .overlap import build_od_pipeline
             embed = od_embed if od_embed is not None else (self.hp.spk.get_speaker_embeddings if self.hp.spk is not None else None)
@@ -294,7 +300,12 @@ class TargetDiarization:
         timelines = [self.combine_audio_chunks(items, spk) for spk in spks]
         lines = [t for t in timelines if t is not None]
         encs, dres = [], None
-        if self.hp.asr is not None and lines:
+        # asr_engine="sensevoice" with its weights loaded: H3 is SenseVoiceSmall (sensevoice.py); without them the engine falls back to
+        # the loaded one, like asr_detection (ASRProcessor.py:390-391)
+        svres = None
+        if str(self.asr_engine).lower() == "sensevoice" and getattr(self.hp, "sv", None) is not None:
+            svres = self.hp.recognise_sensevoice(lines) if lines else []
+        elif self.hp.asr is not None and lines:
             if self.decoder is None and self.hp.dec is not None:       # the device CIF + NAR decoder (N2)
                 encs, dres = self.hp.encode_device(lines, decode=True)
             else:
@@ -306,24 +317,33 @@ class TargetDiarization:
             if tl is None:
                 continue
             text, stamps, lang = "", [], []
-            recognised = self.hp.asr is not None and (dres is not None or self.decoder is not None)
-            if not recognised:                       # no recogniser loaded (asr_detection prints and returns nothing): the chunks keep empty texts
-                out.extend(it for it in items if it["speaker"] == spk)
-                continue
-            if self.hp.asr is not None:
-                enc = encs[k]
-                if dres is not None:
-                    tok = lambda i: self.token_list[i] if self.token_list is not None and i < len(self.token_list) else f"<{i}>"
-                    stamps = [(tok(i), [round(a / 1000.0, 3), round(b / 1000.0, 3)]) for seg in dres[k] for i, (a, b) in zip(seg["token_ids"], seg["timestamp"])]
-                    text = " ".join(t for t, _ in stamps)                 # (asr_detection's text: space-separated tokens, ASRProcessor.py:427-437)
-                elif self.decoder is not None:
-                    text, stamps, *lang = self.decoder(enc)             # (an optional third value: the recogniser's language tag)
+            extra = {}
+            if svres is not None:
+                # SenseVoice returns no timestamps, so `stamps` stays empty and the no-timestamp branch below makes the item; the texts of
+                # the timeline's <= 30 s segments are parsed like asr_detection's (:406-414) and joined, the item carries the language tag
+                from .sensevoice import parse_tagged_text
+                parsed = [parse_tagged_text(seg["text"]) for seg in svres[k]]
                 k += 1
+                text, extra = "".join(t for _, _, t in parsed), {"language": next((l for l, _, _ in parsed if l), "")}
+            else:
+                recognised = self.hp.asr is not None and (dres is not None or self.decoder is not None)
+                if not recognised:                       # no recogniser loaded (asr_detection prints and returns nothing): the chunks keep empty texts
+                    out.extend(it for it in items if it["speaker"] == spk)
+                    continue
+                if self.hp.asr is not None:
+                    enc = encs[k]
+                    if dres is not None:
+                        tok = lambda i: self.token_list[i] if self.token_list is not None and i < len(self.token_list) else f"<{i}>"
+                        stamps = [(tok(i), [round(a / 1000.0, 3), round(b / 1000.0, 3)]) for seg in dres[k] for i, (a, b) in zip(seg["token_ids"], seg["timestamp"])]
+                        text = " ".join(t for t, _ in stamps)                 # (asr_detection's text: space-separated tokens, ASRProcessor.py:427-437)
+                    elif self.decoder is not None:
+                        text, stamps, *lang = self.decoder(enc)             # (an optional third value: the recogniser's language tag)
+                    k += 1
             if not stamps:
                 # :787-797 the recogniser returned no timestamps: ONE item per speaker over the whole span of the items, carrying the
                 # speaker's timeline (the reference computes the punctuated text here and then stores the raw one — kept)
                 out.append({"speaker": spk, "timerange": [items[0]["timerange"][0], items[-1]["timerange"][1]], "text": text, "type": "single",
-                            "audio": tl})
+                            "audio": tl, **extra})
                 continue
             # :798-818 tokens go to the chunk whose range, widened to 0.1 s, contains their START; CJK languages join without a space
             joiner = "" if (lang[0] if lang else ASRProcessor.detect_language(text)) in ("zh", "ja", "ko", "yue") else " "

@@ -186,6 +186,47 @@ def recipe_paraformer_state_dict(seed: int = 0, num_blocks: int = 50) -> "Ordere
     return out
 
 
+def sensevoice_param_shapes(num_blocks: int = 50, tp_blocks: int = 20, vocab: int = 25055) -> "OrderedDict[str, tuple]":
+    """funasr SenseVoiceSmall state_dict layout [upstream-recall]: the 16-row prompt embedding, SenseVoiceEncoderSmall (the SANM
+    encoder's layers plus `tp_encoders` and `tp_norm`) and the CTC projection."""
+    s = OrderedDict()
+    s["embed.weight"] = (16, 560)
+    enc = paraformer_encoder_param_shapes(num_blocks)
+    for k, v in enc.items():
+        s[k] = v
+    for i in range(tp_blocks):
+        for k, v in enc.items():
+            if k.startswith("encoder.encoders0.0."):
+                s[f"encoder.tp_encoders.{i}." + k[len("encoder.encoders0.0."):]] = tuple(512 if d == 560 else d for d in v)
+    s["encoder.tp_norm.weight"] = (512,)
+    s["encoder.tp_norm.bias"] = (512,)
+    s["ctc.ctc_lo.weight"] = (vocab, 512)
+    s["ctc.ctc_lo.bias"] = (vocab,)
+    return s
+
+
+def recipe_sensevoice_state_dict(seed: int = 0, num_blocks: int = 50, tp_blocks: int = 20, vocab: int = 25055,
+                                 blank_bias: float = 0.0) -> "OrderedDict[str, torch.Tensor]":
+    """blank_bias is added to the CTC bias of id 0: with random weights it sets the share of blank frames of the greedy decode"""
+    out = OrderedDict()
+    for name, shape in sensevoice_param_shapes(num_blocks, tp_blocks, vocab).items():
+        n = int(np.prod(shape))
+        u = torch.from_numpy(philox_uniform("sv:" + name, n, seed)).reshape(shape)
+        leaf = name.rsplit(".", 1)[-1]
+        if ".norm" in name or "_norm" in name:
+            t = (1.0 + 0.2 * u) if leaf == "weight" else 0.1 * u
+        elif leaf == "bias":
+            t = 0.1 * u
+        elif name == "embed.weight":
+            t = u
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            t = u * float(1.0 / np.sqrt(fan_in))
+        out[name] = t.to(torch.float32).contiguous()
+    out["ctc.ctc_lo.bias"][0] += blank_bias
+    return out
+
+
 def paraformer_decoder_param_shapes(num_blocks: int = 16, d: int = 512, ffn: int = 2048, ksize: int = 11,
                                     vocab: int = 8404) -> "OrderedDict[str, tuple]":
     """funasr Paraformer (CifPredictorV2 + ParaformerSANMDecoder) state_dict layout [upstream-recall, SURVEY Appendix B.4]:
