@@ -241,6 +241,30 @@ int tdx_pfdec_decode(tdx_pfdec* h, const float* emb_dev, int emb_rows, const int
                      int T, int* ids_dev, float* score_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * N2t Paraformer's upsampling timestamp predictor — the second head of funasr's CifPredictorV3 (BiCifParaformer, the
+ *     "paraformer-large-vad-punc" bundle behind ASRProcessor.py:424; third-party), on the tdx_pfdec handle.  OPTIONAL AS A SET:
+ *     a blob with none of the head's 12 tensors (predictor.upsample_cnn.{weight,bias}, predictor.blstm.{weight_ih,weight_hh,
+ *     bias_ih,bias_hh}_l0 and the same four with _reverse, predictor.cif_output2.{weight,bias}) creates the decoder as before
+ *     (has_timestamps = 0); with some but not all of them tdx_pfdec_create fails with TDX_E_BLOB naming the first missing one.
+ *       timestamps: enc_dev [B,T,512] (the encoder output itself), counts_dev int32 [B] (tdx_pfdec_predict), U = 3T ->
+ *                   ConvTranspose1d(512,512,3,stride 3) -> BLSTM(512) -> a = relu(smooth_factor2 * sigmoid(Linear(1024,1)) -
+ *                   noise_threshold2) (0.25 / 0.01; tdx_pfdec_set_alpha2) -> us_alphas_dev [B,U] = a * counts / sum(a) (a clip
+ *                   whose sum is 0 stays unscaled) -> us_peaks_dev [B,U]: funasr's cif_wo_hidden with threshold 1 - 1e-4, the
+ *                   running integral at every frame, walked sequentially in fp32.  tap_blstm_dev: NULL or [B,U,1024], the BLSTM
+ *                   output.  On return the first B*U floats of the workspace hold the alphas before the re-normalisation.
+ *                   On a handle without the head: TDX_E_INVALID.  The workspace is 6146 floats per upsampled frame (24 KB:
+ *                   the projected LSTM input of both directions dominates).
+ *       set_cif_residual: the main predictor branch is relu(conv(x) + bias + x) in CifPredictorV2 and relu(conv(x) + bias) in
+ *                   V3 [upstream-recall]; create sets 1 without the head (as before) and 0 with it, this call overrides.
+ * ---------------------------------------------------------------------------------- */
+int tdx_pfdec_has_timestamps(const tdx_pfdec* h);
+int tdx_pfdec_set_cif_residual(tdx_pfdec* h, int on);
+int tdx_pfdec_set_alpha2(tdx_pfdec* h, float smooth_factor2, float noise_threshold2);
+size_t tdx_pfdec_timestamps_workspace_bytes(const tdx_pfdec* h, int B, int T);
+int tdx_pfdec_timestamps(tdx_pfdec* h, const float* enc_dev, int B, int T, const int* counts_dev, float* us_alphas_dev,
+                         float* us_peaks_dev, float* tap_blstm_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * a10 ERes2NetV2-w24s4ep4 speaker embedding — replaces
  *     `self.embedding[embedding_model](wav_file, output_emb=True)['embs']`  TargetASR.py:161
  *     (modelscope / 3D-Speaker ERes2NetV2: third-party).  blob: TDXW container with the

@@ -76,6 +76,11 @@ SIGNATURES = {
     "tdx_pfdec_predict": (_i, [_vp, _fp, _i, _i, _fp, _fp, _vp, _vp, _vp, _sz, _vp]),
     "tdx_pfdec_decode_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "tdx_pfdec_decode": (_i, [_vp, _fp, _i, _vp, _fp, _i, _i, _i, _vp, _fp, _vp, _sz, _vp]),
+    "tdx_pfdec_has_timestamps": (_i, [_vp]),
+    "tdx_pfdec_set_cif_residual": (_i, [_vp, _i]),
+    "tdx_pfdec_set_alpha2": (_i, [_vp, C.c_float, C.c_float]),
+    "tdx_pfdec_timestamps_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "tdx_pfdec_timestamps": (_i, [_vp, _fp, _i, _i, _vp, _fp, _fp, _fp, _vp, _sz, _vp]),
     "tdx_eres2net_create": (_i, [_vp, _sz, _i, C.POINTER(_vp)]),
     "tdx_eres2net_destroy": (_i, [_vp]),
     "tdx_eres2net_workspace_bytes": (_sz, [_vp, _i, _i]),

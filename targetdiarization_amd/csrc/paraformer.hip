@@ -20,6 +20,7 @@
 #include "weight_planes.hpp"
 #include "epilogues.hpp"
 #include "pf_sanm.hpp"
+#include "pf_timestamps.hpp"
 
 using namespace tdx;
 
@@ -726,6 +727,8 @@ struct tdx_pfdec {
     std::vector<PfDecLayer> layers; PfDecLayer d3;
     H3W hcif, hout;
     const float *cifb, *cifw, *cifob, *ang, *anb, *bout, *Wout;
+    PfTsHead ts;                    // the upsampling timestamp predictor (pf_timestamps.hpp), when the blob holds it
+    bool cif_residual = true;       // relu(conv(x) + bias + x) (CifPredictorV2) or relu(conv(x) + bias) (V3, the predictor that carries the head)
 };
 
 extern "C" {
@@ -770,6 +773,8 @@ int tdx_pfdec_create(int num_blocks, int vocab, const void* blob, size_t blob_by
         Wout = ld.push(ld.get("decoder.output_layer.weight", (size_t)vocab * D), (size_t)vocab * D, (size_t)vpad * D);     // rows vocab..vpad-1 zero
         bout = ld.push(ld.get("decoder.output_layer.bias", vocab), vocab, vpad);
     }
+    PfTsOff tsoff{};
+    const bool has_ts = ld.ok() && pfts_stage(ld, tsoff);       // optional as a set: none of its tensors = no head, some = the first missing one is the error
     std::unique_ptr<tdx_pfdec> h(new tdx_pfdec());
     h->device = device; h->L = num_blocks; h->vocab = vocab; h->vpad = vpad;
     TRY(ld.finish("tdx_pfdec_create", false, device, h->dev));
@@ -792,6 +797,7 @@ int tdx_pfdec_create(int num_blocks, int vocab, const void* blob, size_t blob_by
     bind_ff(offs[num_blocks], h->d3);
     h->cifb = dev + cifb; h->cifw = dev + cifw; h->cifob = dev + cifob; h->ang = dev + ang; h->anb = dev + anb; h->bout = dev + bout; h->Wout = dev + Wout;
     job(dev + cifW, D, 3 * D, h->hcif); job(dev + Wout, vpad, D, h->hout);
+    if (has_ts) { pfts_bind(dev, tsoff, h->ts, jobs); h->cif_residual = false; }
     TRY(tdx::split_weight_planes(jobs, device, h->dev_planes));
     *out = h.release();
     return TDX_OK;
@@ -800,6 +806,37 @@ int tdx_pfdec_create(int num_blocks, int vocab, const void* blob, size_t blob_by
 int tdx_pfdec_destroy(tdx_pfdec* h) {
     delete h;
     return TDX_OK;
+}
+
+int tdx_pfdec_set_cif_residual(tdx_pfdec* h, int on) {
+    if (!h) return tdx::fail(TDX_E_INVALID, "tdx_pfdec_set_cif_residual: null handle");
+    h->cif_residual = on != 0;
+    return TDX_OK;
+}
+
+int tdx_pfdec_has_timestamps(const tdx_pfdec* h) { return h && h->ts.present ? 1 : 0; }
+
+int tdx_pfdec_set_alpha2(tdx_pfdec* h, float smooth_factor2, float noise_threshold2) {
+    if (!h || !h->ts.present) return tdx::fail(TDX_E_INVALID, "tdx_pfdec_set_alpha2: the handle has no timestamp head");
+    h->ts.smooth = smooth_factor2; h->ts.noise = noise_threshold2;
+    return TDX_OK;
+}
+
+size_t tdx_pfdec_timestamps_workspace_bytes(const tdx_pfdec* h, int B, int T) {
+    if (!h || !h->ts.present || B < 1 || T < 1) return 0;
+    return pfts_work_floats(B, T) * sizeof(float);
+}
+
+// enc_dev [B,T,512], counts_dev int32 [B] (tdx_pfdec_predict) -> us_alphas_dev [B,3T], us_peaks_dev [B,3T]; tap_blstm_dev [B,3T,1024] or NULL
+int tdx_pfdec_timestamps(tdx_pfdec* h, const float* enc, int B, int T, const int* counts, float* us_alphas, float* us_peaks, float* tap_blstm,
+                         void* ws_, size_t ws_bytes, void* stream) {
+    if (!h || !enc || !counts || !us_alphas || !us_peaks || !ws_ || B < 1 || T < 1) return tdx::fail(TDX_E_INVALID, "tdx_pfdec_timestamps: bad argument");
+    if (!h->ts.present) return tdx::fail(TDX_E_INVALID, "tdx_pfdec_timestamps: the blob held no timestamp head (predictor.upsample_cnn / blstm / cif_output2)");
+    if ((long)B * T * 3 > 0x7fffffffL / 4096) return tdx::fail(TDX_E_INVALID, "tdx_pfdec_timestamps: B * 3T too large");
+    if (ws_bytes < tdx_pfdec_timestamps_workspace_bytes(h, B, T)) return tdx::fail(TDX_E_WORKSPACE, "tdx_pfdec_timestamps: workspace too small");
+    tdx::DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
+    return pfts_forward(h->ts, enc, B, T, counts, us_alphas, us_peaks, tap_blstm, (float*)ws_, (hipStream_t)stream);
 }
 
 size_t tdx_pfdec_predict_workspace_bytes(const tdx_pfdec* h, int B, int T) {
@@ -825,7 +862,8 @@ int tdx_pfdec_predict(tdx_pfdec* h, const float* enc, int B, int T, float* alpha
     const dim3 rows4((unsigned)((M + 3) / 4));
     hipLaunchKernelGGL(pf_im2col3_planes_kernel, rows4, dim3(256), 0, st, enc, hp, hs, M, T);
     LAUNCH_CHECK();
-    TRY(linear_h3(hp, hs, (int)M, h->hcif, D, 3 * D, EpiCifConv{h->cifb, enc, p1}, st));
+    if (h->cif_residual) TRY(linear_h3(hp, hs, (int)M, h->hcif, D, 3 * D, EpiCifConv{h->cifb, enc, p1}, st));
+    else TRY(linear_h3(hp, hs, (int)M, h->hcif, D, 3 * D, EpiBiasAct<ActRelu>{h->cifb, p1, D}, st));
     hipLaunchKernelGGL(pf_alpha_kernel, rows4, dim3(256), 0, st, p1, h->cifw, h->cifob, alphas, M, T);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(pf_cif_kernel, dim3(B), dim3(512), (size_t)(T + 1) * 12, st, enc, alphas, emb, counts, peaks, T);

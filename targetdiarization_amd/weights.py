@@ -283,6 +283,43 @@ def recipe_paraformer_decoder_state_dict(seed: int = 0, num_blocks: int = 16, vo
     return out
 
 
+def paraformer_timestamp_param_shapes(d: int = 512, hidden: int = 512) -> "OrderedDict[str, tuple]":
+    """the second head of funasr's CifPredictorV3 (BiCifParaformer) [upstream-recall]: ConvTranspose1d(d, d, 3, stride 3),
+    nn.LSTM(d, hidden, 1, bidirectional) and Linear(2 * hidden, 1) — 12 tensors"""
+    s = OrderedDict()
+    s["predictor.upsample_cnn.weight"] = (d, d, 3)
+    s["predictor.upsample_cnn.bias"] = (d,)
+    for sfx in ("", "_reverse"):
+        s["predictor.blstm.weight_ih_l0" + sfx] = (4 * hidden, d)
+        s["predictor.blstm.weight_hh_l0" + sfx] = (4 * hidden, hidden)
+        s["predictor.blstm.bias_ih_l0" + sfx] = (4 * hidden,)
+        s["predictor.blstm.bias_hh_l0" + sfx] = (4 * hidden,)
+    s["predictor.cif_output2.weight"] = (1, 2 * hidden)
+    s["predictor.cif_output2.bias"] = (1,)
+    return s
+
+
+def recipe_paraformer_timestamp_state_dict(seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Weights of unit gain (variance 1 / fan_in; the transposed convolution's fan-in is its 512 input channels: kernel = stride,
+    one tap per output frame), so that the LSTM's gate pre-activations have a spread of about 1 and do not saturate.  The output
+    bias puts 0.25 * sigmoid - 0.01 near 0.09: three upsampled frames then carry what one encoder frame of the main predictor
+    does (sigmoid(-1) = 0.27), and the sum of the upsampled alphas lands near the token count before it is re-normalised."""
+    out = OrderedDict()
+    for name, shape in paraformer_timestamp_param_shapes().items():
+        n = int(np.prod(shape))
+        u = torch.from_numpy(philox_uniform("pfts:" + name, n, seed)).reshape(shape)
+        leaf = name.rsplit(".", 1)[-1]
+        if name == "predictor.cif_output2.bias":
+            t = torch.full(shape, -0.4)
+        elif leaf.startswith("bias"):
+            t = 0.1 * u
+        else:
+            fan_in = shape[0] if name == "predictor.upsample_cnn.weight" else int(np.prod(shape[1:]))
+            t = u * float(np.sqrt(3.0 / fan_in))
+        out[name] = t.to(torch.float32).contiguous()
+    return out
+
+
 def eres2netv2_param_shapes(m: int = 64, feat_dim: int = 80, emb: int = 192, base_width: int = 24, scale: int = 4,
                             expansion: int = 4, num_blocks=(3, 4, 6, 3)) -> "OrderedDict[str, tuple]":
     """3D-Speaker ERes2NetV2 state_dict layout [upstream-recall, SURVEY Appendix B.3]."""
