@@ -25,6 +25,7 @@
 
 #include "../../include/tdx.h"
 #include "epilogues.hpp"
+#include "weight_pack.hpp"
 
 using namespace tdx;
 
@@ -207,7 +208,7 @@ struct EpiHeadOut {     // head.conv2: row (b, f, t) of [B, Hf, T], channel n ->
     }
 };
 
-struct ConvW { size_t w, b; int N, Npad, cinp, taps; };
+using ConvW = tdx::GemmW;
 struct LayerW { size_t s1, sh1; ConvW lin1; size_t wl, cw1, cb1, cw2, cb2; int cin; };
 struct TransW { size_t s, sh; ConvW lin; int cin; };
 
@@ -244,18 +245,12 @@ int tdx_campp_create(const void* blob, size_t blob_bytes, int device, tdx_campp*
     if (!blob || !out) return tdx::fail(TDX_E_INVALID, "tdx_campp_create: null argument");
     tdx::Loader ld;
     if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_campp_create: malformed TDXW blob");
-    struct BN { std::vector<double> s, sh; };
+    using tdx::BN;
     // eval BatchNorm `p` -> y = x*s + sh   (affine = false: running statistics only)
     auto bn = [&](const std::string& p, int N, bool affine = true) -> BN {
-        BN r; r.s.assign(N, 1.0); r.sh.assign(N, 0.0);
         const float *g = affine ? ld.get(p + "weight", N) : nullptr, *be = affine ? ld.get(p + "bias", N) : nullptr;
         const float *mu = ld.get(p + "running_mean", N), *var = ld.get(p + "running_var", N);
-        if (!ld.ok()) return r;
-        for (int n = 0; n < N; ++n) {
-            r.s[n] = (affine ? (double)g[n] : 1.0) / sqrt((double)var[n] + 1e-5);
-            r.sh[n] = (affine ? (double)be[n] : 0.0) - (double)mu[n] * r.s[n];
-        }
-        return r;
+        return tdx::bn_fold(g, be, mu, var, N);
     };
     auto put = [&](const std::vector<double>& v) -> size_t {
         const size_t o = ld.room(v.size());
@@ -264,31 +259,15 @@ int tdx_campp_create(const void* blob, size_t blob_bytes, int device, tdx_campp*
     };
     // bias-free conv [N,cin,taps] followed by eval BatchNorm `bnp` ("" = none) -> [Npad][taps][cinp] + bias[Npad]
     auto fold = [&](const std::string& wname, const std::string& bnp, int N, int cin, int taps, bool affine = true) -> ConvW {
-        ConvW cw; cw.N = N; cw.Npad = up(N, 128); cw.cinp = up(cin, 32); cw.taps = taps;
         const float* W = ld.get(wname, (size_t)N * cin * taps);
-        BN b; if (!bnp.empty()) b = bn(bnp, N, affine);
-        cw.w = ld.room((size_t)cw.Npad * taps * cw.cinp);
-        cw.b = ld.room(cw.Npad);
-        if (!ld.ok()) return cw;
-        for (int n = 0; n < N; ++n) {
-            const double sc = bnp.empty() ? 1.0 : b.s[n];
-            ld.host[cw.b + n] = bnp.empty() ? 0.f : (float)b.sh[n];
-            for (int c = 0; c < cin; ++c)
-                for (int t = 0; t < taps; ++t)
-                    ld.host[cw.w + ((size_t)n * taps + t) * cw.cinp + c] = (float)((double)W[((size_t)n * cin + c) * taps + t] * sc);
-        }
-        return cw;
+        if (bnp.empty()) return tdx::push_conv_gemm(ld, W, nullptr, (const double*)nullptr, N, cin, taps, up(N, 128), up(cin, 32));
+        const BN b = bn(bnp, N, affine);
+        return tdx::push_conv_gemm(ld, W, b.s.data(), b.sh.data(), N, cin, taps, up(N, 128), up(cin, 32));
     };
     std::unique_ptr<tdx_campp> h(new tdx_campp());
     {   // head.conv1 [32,1,3,3] + bn1 -> w9[9][32], bias[32]
         const float* W = ld.get("head.conv1.weight", HC * 9);
-        const BN b = bn("head.bn1.", HC);
-        h->stem_w = ld.room(9 * HC);
-        h->stem_b = ld.room(HC);
-        if (ld.ok()) for (int n = 0; n < HC; ++n) {
-            ld.host[h->stem_b + n] = (float)b.sh[n];
-            for (int t = 0; t < 9; ++t) ld.host[h->stem_w + t * HC + n] = (float)((double)W[n * 9 + t] * b.s[n]);
-        }
+        tdx::push_stem9(ld, W, bn("head.bn1.", HC), HC, h->stem_w, h->stem_b);
     }
     for (int i = 0; i < 4; ++i) {
         const std::string p = "head.layer" + std::to_string(i / 2 + 1) + "." + std::to_string(i % 2) + ".";

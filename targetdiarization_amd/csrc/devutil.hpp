@@ -59,6 +59,8 @@ __device__ __forceinline__ float sigmoidf_acc(float x) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
 }
 __device__ __forceinline__ float siluf_acc(float x) { return x * sigmoidf_acc(x); }
+// ... and with expf and a true divide, for the LSTM recurrences, whose error feeds back into every later step
+__device__ __forceinline__ float sigmoid_full(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float relu20(float v) { return fminf(fmaxf(v, 0.f), 20.f); }
 __device__ __forceinline__ float leaky(float v, float slope) { return v >= 0.f ? v : slope * v; }
 

@@ -19,6 +19,7 @@
 
 #include "../../include/tdx.h"
 #include "epilogues.hpp"
+#include "weight_pack.hpp"
 #include "weight_planes.hpp"
 
 using namespace tdx;
@@ -490,8 +491,7 @@ __global__ __launch_bounds__(256) void split_rows_static_s2_kernel(const float* 
     h3_store_chunk(planes + row * (long)K * 4 + ch * 32, v, s);
 }
 
-struct ConvW {
-    size_t w, b; int N, Npad, cin, cinp, taps;
+struct ConvW : tdx::GemmW {
     const unsigned char* hp = nullptr; const float* hs = nullptr;     // split-f16 planes [Npad][taps*cinp] + row scales (x3 core), if made
 };
 struct AffW { ConvW c0, c3; int C, inter, ipad; };
@@ -624,23 +624,17 @@ int tdx_eres2net_create(const void* blob, size_t blob_bytes, int device, tdx_ere
     if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_eres2net_create: malformed TDXW blob");
     // conv [N,Cin,kh,kw] (+bias) followed by eval BatchNorm `bn` ("" = none) -> [Npad][taps][cinp], bias[Npad]
     auto fold = [&](const std::string& wname, const std::string& bname, const std::string& bn, int N, int cin, int taps) -> ConvW {
-        ConvW cw; cw.N = N; cw.Npad = up(N, 128); cw.cin = cin; cw.cinp = up(cin, 32); cw.taps = taps;
         const float* W = ld.get(wname, (size_t)N * cin * taps);
         const float* cb = bname.empty() ? nullptr : ld.get(bname, N);
         const float *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
         if (!bn.empty()) { g = ld.get(bn + "weight", N); be = ld.get(bn + "bias", N); mu = ld.get(bn + "running_mean", N); var = ld.get(bn + "running_var", N); }
-        cw.w = ld.room((size_t)cw.Npad * taps * cw.cinp);
-        cw.b = ld.room(cw.Npad);
-        if (!ld.ok()) return cw;
-        for (int n = 0; n < N; ++n) {
-            const double sc = bn.empty() ? 1.0 : (double)g[n] / sqrt((double)var[n] + 1e-5);
+        const tdx::BN f = tdx::bn_fold(g, be, mu, var, N);
+        std::vector<double> bias(N, 0.0);
+        if (ld.ok()) for (int n = 0; n < N; ++n) {
             const double b0 = cb ? (double)cb[n] : 0.0;
-            ld.host[cw.b + n] = (float)(bn.empty() ? b0 : (b0 - (double)mu[n]) * sc + (double)be[n]);
-            for (int c = 0; c < cin; ++c)
-                for (int t = 0; t < taps; ++t)
-                    ld.host[cw.w + ((size_t)n * taps + t) * cw.cinp + c] = (float)((double)W[((size_t)n * cin + c) * taps + t] * sc);
+            bias[n] = bn.empty() ? b0 : (b0 - (double)mu[n]) * f.s[n] + (double)be[n];
         }
-        return cw;
+        return ConvW{tdx::push_conv_gemm(ld, W, f.s.data(), bias.data(), N, cin, taps, up(N, 128), up(cin, 32))};
     };
     auto fold_aff = [&](const std::string& p, int C) -> AffW {
         AffW a; a.C = C; a.inter = C / 4; a.ipad = up(a.inter, 32);
@@ -649,17 +643,10 @@ int tdx_eres2net_create(const void* blob, size_t blob_bytes, int device, tdx_ere
         return a;
     };
     std::unique_ptr<tdx_eres2net> h(new tdx_eres2net());
-    // stem: [64,1,3,3] + bn1 -> w9[9][64], bias[64]
-    {
+    {   // stem: [64,1,3,3] + bn1 -> w9[9][64], bias[64]
         const float* W = ld.get("conv1.weight", 64 * 9);
         const float *g = ld.get("bn1.weight", 64), *be = ld.get("bn1.bias", 64), *mu = ld.get("bn1.running_mean", 64), *var = ld.get("bn1.running_var", 64);
-        h->stem_w = ld.room(9 * 64);
-        h->stem_b = ld.room(64);
-        if (ld.ok()) for (int n = 0; n < 64; ++n) {
-            const double sc = (double)g[n] / sqrt((double)var[n] + 1e-5);
-            ld.host[h->stem_b + n] = (float)((double)be[n] - (double)mu[n] * sc);
-            for (int t = 0; t < 9; ++t) ld.host[h->stem_w + t * 64 + n] = (float)((double)W[n * 9 + t] * sc);
-        }
+        tdx::push_stem9(ld, W, tdx::bn_fold(g, be, mu, var, 64), 64, h->stem_w, h->stem_b);
     }
     int in_planes = 64;
     for (int s = 0; s < NSTAGE && ld.ok(); ++s) {

@@ -26,6 +26,7 @@
 
 #include "../../include/tdx.h"
 #include "epilogues.hpp"
+#include "weight_pack.hpp"
 
 using namespace tdx;
 
@@ -126,13 +127,13 @@ __global__ __launch_bounds__(256) void softmax_kernel(const float* __restrict__ 
     if (post && on) *reinterpret_cast<f32x4*>(post + (long)t * NCLS + lane * 4) = e * inv;
 }
 
-struct Lin { size_t w, b; int Np, Kp; bool bias; };
+struct Lin : tdx::GemmW { bool bias = true; };
 
 // v + b (optionally ReLU); every column of the padded width is stored (see the file comment)
 int dense(const float* A, const float* dev, const Lin& l, int M, float* out, bool relu, hipStream_t st) {
     const float* b = l.bias ? dev + l.b : nullptr;
-    if (relu) return linear_f32(A, l.Kp, dev + l.w, M, l.Np, l.Kp, EpiBiasAct<ActRelu>{b, out, l.Np}, st);
-    return linear_f32(A, l.Kp, dev + l.w, M, l.Np, l.Kp, EpiBiasAct<>{b, out, l.Np}, st);
+    if (relu) return linear_f32(A, l.Kp, dev + l.w, M, l.Npad, l.Kp, EpiBiasAct<ActRelu>{b, out, l.Npad}, st);
+    return linear_f32(A, l.Kp, dev + l.w, M, l.Npad, l.Kp, EpiBiasAct<>{b, out, l.Npad}, st);
 }
 
 }  // namespace
@@ -151,16 +152,6 @@ int tdx_fsmnvad_create(const void* blob, size_t blob_bytes, int device, tdx_fsmn
     if (!blob || !out) return tdx::fail(TDX_E_INVALID, "tdx_fsmnvad_create: null argument");
     tdx::Loader ld;
     if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_fsmnvad_create: malformed TDXW blob");
-    // W [N][K] (+ bias [N]) -> zero-padded [Np][Kp] + bias [Np]
-    auto put = [&](const std::vector<double>& W, const std::vector<double>* b, int N, int K, int Np, int Kp) -> Lin {
-        Lin l; l.Np = Np; l.Kp = Kp; l.bias = b != nullptr;
-        l.w = ld.room((size_t)Np * Kp); l.b = ld.room(Np);
-        for (int n = 0; n < N; ++n) {
-            for (int k = 0; k < K; ++k) ld.host[l.w + (size_t)n * Kp + k] = (float)W[(size_t)n * K + k];
-            if (b) ld.host[l.b + n] = (float)(*b)[n];
-        }
-        return l;
-    };
     // `b` . `a` : two linears with no activation between them, as one matrix; the product is taken in fp64
     auto folded = [&](const std::string& a, const std::string& b, int Nin, int Nmid, int Nout, int Np, int Kp) -> Lin {
         const float *Wa = ld.get(a + "weight", {(uint32_t)Nmid, (uint32_t)Nin}), *ba = ld.get(a + "bias", {(uint32_t)Nmid});
@@ -177,17 +168,12 @@ int tdx_fsmnvad_create(const void* blob, size_t blob_bytes, int device, tdx_fsmn
             }
             bias[n] = acc;
         }
-        return put(W, &bias, Nout, Nin, Np, Kp);
+        return Lin{tdx::push_linear(ld, W.data(), bias.data(), Nout, Nin, Np, Kp)};
     };
     auto plain = [&](const std::string& p, bool with_bias, int N, int K, int Np, int Kp) -> Lin {
         const float* Wp = ld.get(p + "weight", {(uint32_t)N, (uint32_t)K});
         const float* bp = with_bias ? ld.get(p + "bias", {(uint32_t)N}) : nullptr;
-        std::vector<double> W((size_t)N * K, 0.0), bias(N, 0.0);
-        if (ld.ok()) {
-            for (size_t i = 0; i < W.size(); ++i) W[i] = Wp[i];
-            if (with_bias) for (int n = 0; n < N; ++n) bias[n] = bp[n];
-        }
-        return put(W, with_bias ? &bias : nullptr, N, K, Np, Kp);
+        return Lin{tdx::push_linear(ld, Wp, bp, N, K, Np, Kp), with_bias};
     };
     std::unique_ptr<tdx_fsmnvad> h(new tdx_fsmnvad());
     h->shift = ld.push(ld.get("cmvn.shift", {(uint32_t)DIN}), DIN, DINP);

@@ -22,14 +22,13 @@
 
 #include "../../include/tdx.h"
 #include "epilogues.hpp"
+#include "weight_pack.hpp"
 
 using namespace tdx;
 
 namespace {
 
-
-
-struct GW { size_t w = 0, b = 0; int N = 0, Npad = 0, K = 0; };            // folded GEMM weights [Npad][K] + bias [Npad]
+using GW = tdx::GemmW;            // folded GEMM weights [Npad][Kp] + bias [Npad]
 struct TdfW { size_t w1 = 0, w2 = 0, b1 = 0, b2 = 0, s1 = 0, t1 = 0, s2 = 0, t2 = 0; int f = 0, fb = 0, fbp = 0; };
 struct BlockW { std::vector<GW> conv; TdfW tdf; int c = 0, f = 0; };
 
@@ -159,7 +158,7 @@ int run_tfc_tdf(const tdx_mdx* h, const BlockW& bw, int B, int T, int F, float**
     const long M = (long)B * T * F;
     for (size_t j = 0; j < bw.conv.size(); ++j) {
         const GW& cw = bw.conv[j];
-        GemmArgs g = make_args((int)M, cw.Npad, make_seg(*px, c, h->dev + cw.w, cw.K, c));
+        GemmArgs g = make_args((int)M, cw.Npad, make_seg(*px, c, h->dev + cw.w, cw.Kp, c));
         g.n_valid = up(c, 32);
         g.cv_Hin = T; g.cv_Win = F; g.cv_Hout = T; g.cv_Wout = F; g.cv_stride = 1; g.cv_ntaps = 9; g.cv_cin = c;
         if (launch_gemm<false, false, false, false, EpiBiasActN<ActRelu>, 0, true>(g, 1, EpiBiasActN<ActRelu>{h->dev + cw.b, *py, c, c}, st) != hipSuccess)
@@ -197,29 +196,23 @@ int tdx_mdx_create(const tdx_mdx_config* cfg, const void* blob, size_t blob_byte
         return tdx::fail(TDX_E_INVALID, "tdx_mdx_create: unsupported config (need odd num_blocks <= 15, k = 3, g % 32 == 0, dim_f / 2^n a multiple of 32 and of bn, dim_t / 2^n integral)");
     tdx::Loader ld;
     if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_mdx_create: malformed TDXW blob");
-    struct BN { std::vector<double> s, t; };
-    auto bnfold = [&](const std::string& p, int c) -> BN {       // y = x * s + t
-        BN r; r.s.assign(c, 1.0); r.t.assign(c, 0.0);
+    using tdx::BN;
+    auto bnfold = [&](const std::string& p, int c) -> BN {       // y = x * s + sh
         const float *w = ld.get(p + "weight", c), *b = ld.get(p + "bias", c), *mu = ld.get(p + "running_mean", c), *var = ld.get(p + "running_var", c);
-        if (ld.ok()) for (int i = 0; i < c; ++i) { r.s[i] = (double)w[i] / std::sqrt((double)var[i] + 1e-5); r.t[i] = (double)b[i] - (double)mu[i] * r.s[i]; }
+        return tdx::bn_fold(w, b, mu, var, c);
+    };
+    // conv bias + BN -> bias of the folded conv
+    auto fold_bias = [&](const float* cb, const BN& b, int N) {
+        std::vector<double> r(N, 0.0);
+        if (cb) for (int nn = 0; nn < N; ++nn) r[nn] = (double)cb[nn] * b.s[nn] + b.sh[nn];
         return r;
     };
     // Conv2d [N][cin][kh][kw] + bias + BN -> [Npad][taps][cin] (tap = kh * kw_count + kw), bias[Npad]
     auto fold_conv = [&](const std::string& p, const std::string& bnp, int N, int cin, int kh, int kw) -> GW {
-        GW w; w.N = N; w.Npad = up(N, 128); w.K = kh * kw * cin;
         const float* W = ld.get(p + "weight", (size_t)N * cin * kh * kw);
         const float* cb = ld.get(p + "bias", N);
         const BN b = bnfold(bnp, N);
-        w.w = ld.room((size_t)w.Npad * w.K);
-        w.b = ld.room(w.Npad);
-        if (!ld.ok()) return w;
-        for (int nn = 0; nn < N; ++nn) {
-            ld.host[w.b + nn] = (float)((double)cb[nn] * b.s[nn] + b.t[nn]);
-            for (int c = 0; c < cin; ++c)
-                for (int t = 0; t < kh * kw; ++t)
-                    ld.host[w.w + ((size_t)nn * kh * kw + t) * cin + c] = (float)((double)W[((size_t)nn * cin + c) * kh * kw + t] * b.s[nn]);
-        }
-        return w;
+        return tdx::push_conv_gemm(ld, W, b.s.data(), fold_bias(cb, b, N).data(), N, cin, kh * kw, up(N, 128), cin);
     };
     auto fold_block = [&](const std::string& p, int c, int f) -> BlockW {
         BlockW bw; bw.c = c; bw.f = f;
@@ -244,8 +237,8 @@ int tdx_mdx_create(const tdx_mdx_config* cfg, const void* blob, size_t blob_byte
         if (B1) memcpy(ld.host.data() + td.b1, B1, td.fb * sizeof(float));
         if (B2) memcpy(ld.host.data() + td.b2, B2, f * sizeof(float));
         for (int i = 0; i < c; ++i) {
-            ld.host[td.s1 + i] = (float)n1.s[i]; ld.host[td.t1 + i] = (float)n1.t[i];
-            ld.host[td.s2 + i] = (float)n2.s[i]; ld.host[td.t2 + i] = (float)n2.t[i];
+            ld.host[td.s1 + i] = (float)n1.s[i]; ld.host[td.t1 + i] = (float)n1.sh[i];
+            ld.host[td.s2 + i] = (float)n2.s[i]; ld.host[td.t2 + i] = (float)n2.sh[i];
         }
         return bw;
     };
@@ -255,12 +248,8 @@ int tdx_mdx_create(const tdx_mdx_config* cfg, const void* blob, size_t blob_byte
         const float* W = ld.get("first_conv.0.weight", (size_t)g * 4);
         const float* cb = ld.get("first_conv.0.bias", g);
         const BN b = bnfold("first_conv.1.", g);
-        h->first_w = ld.room((size_t)g * 4);
-        h->first_b = ld.room(g);
-        if (ld.ok()) for (int nn = 0; nn < g; ++nn) {
-            ld.host[h->first_b + nn] = (float)((double)cb[nn] * b.s[nn] + b.t[nn]);
-            for (int c = 0; c < 4; ++c) ld.host[h->first_w + nn * 4 + c] = (float)((double)W[nn * 4 + c] * b.s[nn]);
-        }
+        const GW w = tdx::push_conv_gemm(ld, W, b.s.data(), fold_bias(cb, b, g).data(), g, 4, 1, g, 4);
+        h->first_w = w.w; h->first_b = w.b;
     }
     int f = dim_f, c = g;
     for (int i = 0; i < n && ld.ok(); ++i) {
@@ -273,7 +262,7 @@ int tdx_mdx_create(const tdx_mdx_config* cfg, const void* blob, size_t blob_byte
         // ConvTranspose2d weight [cin = c][cout = c - g][2][2] + bias + BN -> rows r = tap * cg + n of [4 cg (pad 128)][c], bias repeated per tap
         const std::string p = "us." + std::to_string(i) + ".";
         const int cg = c - g;
-        GW w; w.N = 4 * cg; w.Npad = up(4 * cg, 128); w.K = c;
+        GW w; w.N = 4 * cg; w.Npad = up(4 * cg, 128); w.Kp = c;
         const float* W = ld.get(p + "0.weight", (size_t)c * cg * 4);
         const float* cb = ld.get(p + "0.bias", cg);
         const BN b = bnfold(p + "1.", cg);
@@ -281,7 +270,7 @@ int tdx_mdx_create(const tdx_mdx_config* cfg, const void* blob, size_t blob_byte
         w.b = ld.room(w.Npad);
         if (ld.ok()) for (int tap = 0; tap < 4; ++tap)
             for (int nn = 0; nn < cg; ++nn) {
-                ld.host[w.b + tap * cg + nn] = (float)((double)cb[nn] * b.s[nn] + b.t[nn]);
+                ld.host[w.b + tap * cg + nn] = (float)((double)cb[nn] * b.s[nn] + b.sh[nn]);
                 for (int ci = 0; ci < c; ++ci) ld.host[w.w + ((size_t)tap * cg + nn) * c + ci] = (float)((double)W[((size_t)ci * cg + nn) * 4 + tap] * b.s[nn]);
             }
         h->us.push_back(w);
@@ -349,7 +338,7 @@ int tdx_mdx_forward(tdx_mdx* h, const float* spec, int B, float* out, void* ws_,
         hipLaunchKernelGGL(mdx_s2d_kernel, dim3((unsigned)((Po * c + 255) / 256)), dim3(256), 0, st, x, s2d, Po, p.t[i + 1], p.f[i + 1], c);
         LAUNCH_CHECK();
         const GW& dw = h->ds[i];
-        TRY(linear_f32(s2d, 4L * c, h->dev + dw.w, (int)Po, dw.Npad, dw.K, EpiBiasActN<ActRelu>{h->dev + dw.b, y, dw.N, dw.N}, st, up(dw.N, 32)));
+        TRY(linear_f32(s2d, 4L * c, h->dev + dw.w, (int)Po, dw.Npad, dw.Kp, EpiBiasActN<ActRelu>{h->dev + dw.b, y, dw.N, dw.N}, st, up(dw.N, 32)));
         std::swap(x, y);
     }
     TRY(run_tfc_tdf(h, h->bott, B, p.t[h->n], p.f[h->n], &x, &y, tmid, st));

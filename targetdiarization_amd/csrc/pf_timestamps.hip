@@ -39,8 +39,6 @@ constexpr int D = 512, HID = 512, GATES = 4 * HID, XP = 2 * GATES, YW = 2 * HID,
 constexpr int PFTS_CT = 4, PFTS_THREADS = 2 * HID, PFTS_KH = HID / 2;
 constexpr float PFTS_THRESHOLD = 1.0f - 1e-4f;
 
-__device__ __forceinline__ float sigmoid_full(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // xp [B*U][4096]: column dir*2048 + u*4 + gate (i, f, g, o), biases included; whhT [2][512 (k)][2048 (u*4 + gate)];
 // y [B*U][1024] = [h_fwd | h_bwd].  grid = 2 * ceil(B / PFTS_CT) blocks: dir = block & 1, clip tile = block >> 1.
 __global__ __launch_bounds__(PFTS_THREADS) void pfts_lstm_rec_kernel(const float* __restrict__ xp, const float* __restrict__ whhT,
@@ -164,21 +162,16 @@ bool pfts_stage(Loader& ld, PfTsOff& o) {
         ld.host[o.Wup + ((size_t)j * D + co) * D + ci] = cw[((size_t)ci * D + co) * UPS + j];
     if (cb) for (int j = 0; j < UPS; ++j) for (int co = 0; co < D; ++co) ld.host[o.bup + (size_t)j * D + co] = cb[co];
     // both directions' W_ih as one [4096][512] matrix with rows dir*2048 + u*4 + gate, bias b_ih + b_hh; W_hh transposed
-    o.Wih = ld.room((size_t)XP * D);
-    o.bih = ld.room(XP);
+    o.ih.N = XP; o.ih.Npad = XP; o.ih.Kp = D;
+    o.ih.w = ld.room((size_t)XP * D);
+    o.ih.b = ld.room(XP);
     o.whhT = ld.room((size_t)2 * HID * GATES);
     for (int dir = 0; dir < 2; ++dir) {
         const float* wih = ld.get(PFTS_TENSORS[2 + 4 * dir], {g, d});
         const float* whh = ld.get(PFTS_TENSORS[3 + 4 * dir], {g, hd});
         const float* bi = ld.get(PFTS_TENSORS[4 + 4 * dir], {g});
         const float* bh = ld.get(PFTS_TENSORS[5 + 4 * dir], {g});
-        if (!wih || !whh || !bi || !bh) continue;
-        for (int gt = 0; gt < 4; ++gt) for (int u = 0; u < HID; ++u) {
-            const size_t src = (size_t)gt * HID + u, dst = (size_t)dir * GATES + (size_t)u * 4 + gt;
-            memcpy(&ld.host[o.Wih + dst * D], wih + src * D, D * sizeof(float));
-            ld.host[o.bih + dst] = bi[src] + bh[src];
-            for (int k = 0; k < HID; ++k) ld.host[o.whhT + ((size_t)dir * HID + k) * GATES + (size_t)u * 4 + gt] = whh[src * HID + k];
-        }
+        push_lstm_gates(ld, wih, whh, bi, bh, HID, D, o.ih, o.whhT, dir * GATES, true);
     }
     o.w2 = ld.push(ld.get(PFTS_TENSORS[10], {1u, (uint32_t)YW}), YW);
     o.b2 = ld.push(ld.get(PFTS_TENSORS[11], {1u}), 1);
@@ -187,7 +180,7 @@ bool pfts_stage(Loader& ld, PfTsOff& o) {
 
 void pfts_bind(const float* dev, const PfTsOff& o, PfTsHead& w, std::vector<PlaneJob>& jobs) {
     w.present = true;
-    w.Wup = dev + o.Wup; w.bup = dev + o.bup; w.Wih = dev + o.Wih; w.bih = dev + o.bih; w.whhT = dev + o.whhT; w.w2 = dev + o.w2; w.b2 = dev + o.b2;
+    w.Wup = dev + o.Wup; w.bup = dev + o.bup; w.Wih = dev + o.ih.w; w.bih = dev + o.ih.b; w.whhT = dev + o.whhT; w.w2 = dev + o.w2; w.b2 = dev + o.b2;
     jobs.push_back({w.Wup, UPS * D, D, &w.hup.p, &w.hup.s});
     jobs.push_back({w.Wih, XP, D, &w.hih.p, &w.hih.s});
 }

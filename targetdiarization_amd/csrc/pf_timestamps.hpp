@@ -10,9 +10,10 @@
 
 #include "epilogues.hpp"
 #include "tdx_common.hpp"
+#include "weight_pack.hpp"
 #include "weight_planes.hpp"
 
-struct PfTsOff { size_t Wup, bup, Wih, bih, whhT, w2, b2; };       // offsets into the Loader's image
+struct PfTsOff { size_t Wup, bup; tdx::GemmW ih; size_t whhT, w2, b2; };       // offsets into the Loader's image (ih: the LSTM input projection)
 struct PfTsHead {
     bool present = false;
     float smooth = 0.25f, noise = 0.01f;       // smooth_factor2, noise_threshold2

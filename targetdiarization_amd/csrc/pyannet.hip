@@ -38,6 +38,7 @@
 
 #include "../../include/tdx.h"
 #include "epilogues.hpp"
+#include "weight_pack.hpp"
 
 using namespace tdx;
 
@@ -242,8 +243,6 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* in, const 
 
 // (e) the LSTM recurrence of one layer (file comment).  xp [B*F][1024]: column dir*512 + u*4 + gate (i, f, g, o);
 // whh [2][512][128]: row u*4 + gate of each direction; y [B*F][256]: [h_fwd | h_bwd].
-__device__ __forceinline__ float sigmoid_full(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 __global__ __launch_bounds__(REC_THREADS) void lstm_rec_kernel(const float* __restrict__ xp, const float* __restrict__ whh,
                                                                 float* __restrict__ y, int B, int F) {
     __shared__ __attribute__((aligned(16))) float hs[2][REC_TILE][H_PITCH];
@@ -337,18 +336,18 @@ struct EpiConv {        // batch z = chunk: out[z][m][n] = v + b[n], n < 60
     }
 };
 
-struct Lin { size_t w, b; int Np, Kp, N; };
+using Lin = tdx::GemmW;
 
 // columns < l.N: out[m][n] = v + b[n], optionally leaky_relu
 int dense(const float* A, long lda, const float* dev, const Lin& l, int M, float* out, long ldo, bool act, hipStream_t st) {
-    if (act) return linear_f32(A, lda, dev + l.w, M, l.Np, l.Kp, EpiBiasActN<ActLeaky<1, 100>>{dev + l.b, out, ldo, l.N}, st, up(l.N, 32));
-    return linear_f32(A, lda, dev + l.w, M, l.Np, l.Kp, EpiBiasActN<>{dev + l.b, out, ldo, l.N}, st, up(l.N, 32));
+    if (act) return linear_f32(A, lda, dev + l.w, M, l.Npad, l.Kp, EpiBiasActN<ActLeaky<1, 100>>{dev + l.b, out, ldo, l.N}, st, up(l.N, 32));
+    return linear_f32(A, lda, dev + l.w, M, l.Npad, l.Kp, EpiBiasActN<>{dev + l.b, out, ldo, l.N}, st, up(l.N, 32));
 }
 
 // the k5 convolution of B chunks: in [B][rows_in][C] (normalised), out [B][rows_in - 4][60]
 int conv5(const float* in, int C, int rows_in, const float* dev, const Lin& l, int B, float* out, hipStream_t st) {
     const int M = rows_in - (KCONV - 1);
-    GemmArgs g = make_args(M, l.Np, make_seg(in, C, dev + l.w, l.Kp, l.Kp, (long)rows_in * C));
+    GemmArgs g = make_args(M, l.Npad, make_seg(in, C, dev + l.w, l.Kp, l.Kp, (long)rows_in * C));
     g.n_valid = up(l.N, 32);
     if (launch_gemm<false, false, false, false>(g, B, EpiConv{dev + l.b, out, (long)M}, st) != hipSuccess)
         return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
@@ -415,21 +414,14 @@ int tdx_pyannet_create(const void* blob, size_t blob_bytes, int device, tdx_pyan
         const std::string p = "sincnet.conv1d." + std::to_string(i + 1) + ".";
         const float* w = ld.get(p + "weight", {(uint32_t)C1, (uint32_t)cin, (uint32_t)KCONV});
         const float* b = ld.get(p + "bias", {(uint32_t)C1});
-        Lin& l = h->conv[i];
-        l.N = C1; l.Np = GEMM_BN; l.Kp = Kp;
-        l.w = ld.room((size_t)l.Np * Kp); l.b = ld.room(l.Np);
-        if (w && b) for (int n = 0; n < C1; ++n) {
-            for (int c = 0; c < cin; ++c)
-                for (int k = 0; k < KCONV; ++k) ld.host[l.w + (size_t)n * Kp + k * cin + c] = w[((size_t)n * cin + c) * KCONV + k];
-            ld.host[l.b + n] = b[n];
-        }
+        h->conv[i] = tdx::push_conv_gemm(ld, w, nullptr, b, C1, cin, KCONV, GEMM_BN, cin, Kp);
     }
     // LSTM: both directions' W_ih as one [1024][Kp] matrix with rows permuted to dir*512 + u*4 + gate, bias b_ih + b_hh
     // likewise; W_hh [2][512][128] in the same row order
     for (int l = 0; l < NLAYER; ++l) {
         const int in = l == 0 ? C1 : LSTM_OUT, Kp = l == 0 ? SIN : LSTM_OUT;
         Lin& pj = h->proj[l];
-        pj.N = XP; pj.Np = XP; pj.Kp = Kp;
+        pj.N = XP; pj.Npad = XP; pj.Kp = Kp;
         pj.w = ld.room((size_t)XP * Kp); pj.b = ld.room(XP);
         h->whh[l] = ld.room((size_t)NDIR * GATES * HID);
         for (int d = 0; d < NDIR; ++d) {
@@ -438,23 +430,13 @@ int tdx_pyannet_create(const void* blob, size_t blob_bytes, int device, tdx_pyan
             const float* whh = ld.get("lstm.weight_hh" + sfx, {(uint32_t)GATES, (uint32_t)HID});
             const float* bih = ld.get("lstm.bias_ih" + sfx, {(uint32_t)GATES});
             const float* bhh = ld.get("lstm.bias_hh" + sfx, {(uint32_t)GATES});
-            if (!(wih && whh && bih && bhh)) continue;
-            for (int g = 0; g < 4; ++g)
-                for (int u = 0; u < HID; ++u) {
-                    const size_t src = (size_t)g * HID + u, dst = (size_t)d * GATES + u * 4 + g;
-                    memcpy(ld.host.data() + pj.w + dst * Kp, wih + src * in, in * sizeof(float));
-                    memcpy(ld.host.data() + h->whh[l] + dst * HID, whh + src * HID, HID * sizeof(float));
-                    ld.host[pj.b + dst] = bih[src] + bhh[src];
-                }
+            tdx::push_lstm_gates(ld, wih, whh, bih, bhh, HID, in, pj, h->whh[l], d * GATES);
         }
     }
     auto linear = [&](const std::string& p, int N, int K) -> Lin {
-        Lin l; l.N = N; l.Np = GEMM_BN; l.Kp = K;
         const float* w = ld.get(p + "weight", {(uint32_t)N, (uint32_t)K});
         const float* b = ld.get(p + "bias", {(uint32_t)N});
-        l.w = ld.push(w, (size_t)N * K, (size_t)l.Np * K);
-        l.b = ld.push(b, N, l.Np);
-        return l;
+        return tdx::push_linear(ld, w, b, N, K, GEMM_BN, K);
     };
     h->lin[0] = linear("linear.0.", HID, LSTM_OUT);
     h->lin[1] = linear("linear.1.", HID, HID);

@@ -43,6 +43,7 @@
 
 #include "../../include/tdx.h"
 #include "epilogues.hpp"
+#include "weight_pack.hpp"
 
 using namespace tdx;
 
@@ -107,7 +108,6 @@ struct EpiFrames {
     }
 };
 
-__device__ __forceinline__ float sigmoid_full(float x) { return 1.0f / (1.0f + expf(-x)); }
 // lane L of the caller's quad to all four lanes (DPP quad_perm [L,L,L,L])
 template <int L>
 __device__ __forceinline__ float quad_bcast(float v) {
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ h, 
     if (lane == 0) prob[t] = sigmoid_full(v + bias[0]);
 }
 
-struct Conv { size_t w, b; int Np, Kp, N; };
+using Conv = tdx::GemmW;
 
 }  // namespace
 
@@ -212,20 +212,13 @@ int tdx_silero_create(const void* blob, size_t blob_bytes, int device, tdx_siler
             memcpy(ld.host.data() + h->basis + (size_t)NBINP * NFFT, b + (size_t)NBIN * NFFT, (size_t)NBIN * NFFT * sizeof(float));
         }
     }
-    // Conv1d weight [Cout][Cin][3] -> GEMM B [Np][Kp], column (k - k0) * pitch + c for taps k0 .. k0 + nk - 1 (channel-last
+    // Conv1d weight [Cout][Cin][3] -> GEMM B [Npad][Kp], column (k - k0) * pitch + c for taps k0 .. k0 + nk - 1 (channel-last
     // input rows of `pitch` floats); rows Cout.., columns past Cin of a tap zero
     auto conv = [&](int i, int cout, int cin, int pitch, int k0, int nk) -> Conv {
         const std::string p = "encoder." + std::to_string(i) + ".reparam_conv.";
         const float* w = ld.get(p + "weight", {(uint32_t)cout, (uint32_t)cin, 3u});
         const float* b = ld.get(p + "bias", {(uint32_t)cout});
-        Conv l; l.N = cout; l.Np = GEMM_BN; l.Kp = nk * pitch;
-        l.w = ld.room((size_t)l.Np * l.Kp); l.b = ld.room(l.Np);
-        if (w && b) for (int n = 0; n < cout; ++n) {
-            for (int c = 0; c < cin; ++c)
-                for (int k = 0; k < nk; ++k) ld.host[l.w + (size_t)n * l.Kp + k * pitch + c] = w[((size_t)n * cin + c) * 3 + k0 + k];
-            ld.host[l.b + n] = b[n];
-        }
-        return l;
+        return tdx::push_conv_gemm(ld, w, nullptr, b, cout, cin, 3, GEMM_BN, pitch, nk * pitch, k0, nk);
     };
     h->conv[0] = conv(0, C1, NBIN, P0, 0, 3);
     h->conv[1] = conv(1, C2, C1, C1, 0, 3);
@@ -237,17 +230,10 @@ int tdx_silero_create(const void* blob, size_t blob_bytes, int device, tdx_siler
         const float* bih = ld.get("decoder.rnn.bias_ih", {(uint32_t)GATES});
         const float* bhh = ld.get("decoder.rnn.bias_hh", {(uint32_t)GATES});
         Conv& pj = h->proj;
-        pj.N = GATES; pj.Np = GATES; pj.Kp = HID;
+        pj.N = GATES; pj.Npad = GATES; pj.Kp = HID;
         pj.w = ld.room((size_t)GATES * HID); pj.b = ld.room(GATES);
         h->whh = ld.room((size_t)GATES * HID);
-        if (wih && whh && bih && bhh)
-            for (int g = 0; g < 4; ++g)
-                for (int u = 0; u < HID; ++u) {
-                    const size_t src = (size_t)g * HID + u, dst = (size_t)u * 4 + g;
-                    memcpy(ld.host.data() + pj.w + dst * HID, wih + src * HID, HID * sizeof(float));
-                    memcpy(ld.host.data() + h->whh + dst * HID, whh + src * HID, HID * sizeof(float));
-                    ld.host[pj.b + dst] = bih[src] + bhh[src];
-                }
+        tdx::push_lstm_gates(ld, wih, whh, bih, bhh, HID, HID, pj, h->whh, 0);
     }
     h->head_w = ld.push(ld.get("decoder.decoder.2.weight", {1u, (uint32_t)HID, 1u}), HID);
     h->head_b = ld.push(ld.get("decoder.decoder.2.bias", {1u}), 1);
@@ -314,19 +300,19 @@ int tdx_silero_forward(tdx_silero* h, const float* wav, const int* starts, int n
     TRY((linear_f32<true>(win, HOP, dev + h->basis, WROWS * N - 1, NBINP, NFFT, EpiMag{x0}, st, 0, NBINP)));
     {
         const Conv& l = h->conv[0];
-        TRY(linear_f32(x0, P0, dev + l.w, PER * N - 2, l.Np, l.Kp, EpiFrames{dev + l.b, x1, PER, NFR, PER * C1, C1, C1, l.N}, st, up(l.N, 32)));
+        TRY(linear_f32(x0, P0, dev + l.w, PER * N - 2, l.Npad, l.Kp, EpiFrames{dev + l.b, x1, PER, NFR, PER * C1, C1, C1, l.N}, st, up(l.N, 32)));
     }
     {
         const Conv& l = h->conv[1];
-        TRY(linear_f32(x1, 2 * C1, dev + l.w, 3 * N - 1, l.Np, l.Kp, EpiFrames{dev + l.b, x2, 3, 2, 2 * C2, C2, 0, l.N}, st, up(l.N, 32)));
+        TRY(linear_f32(x1, 2 * C1, dev + l.w, 3 * N - 1, l.Npad, l.Kp, EpiFrames{dev + l.b, x2, 3, 2, 2 * C2, C2, 0, l.N}, st, up(l.N, 32)));
     }
     {
         const Conv& l = h->conv[2];
-        TRY(linear_f32(x2, 2 * C2, dev + l.w, N, l.Np, l.Kp, EpiBiasActN<ActRelu>{dev + l.b, x3, C3, l.N}, st, up(l.N, 32)));
+        TRY(linear_f32(x2, 2 * C2, dev + l.w, N, l.Npad, l.Kp, EpiBiasActN<ActRelu>{dev + l.b, x3, C3, l.N}, st, up(l.N, 32)));
     }
     {
         const Conv& l = h->conv[3];
-        TRY(linear_f32(x3, C3, dev + l.w, N, l.Np, l.Kp, EpiBiasAct<ActRelu>{dev + l.b, feat, C4}, st));
+        TRY(linear_f32(x3, C3, dev + l.w, N, l.Npad, l.Kp, EpiBiasAct<ActRelu>{dev + l.b, feat, C4}, st));
     }
     TRY(linear_f32(feat, C4, dev + h->proj.w, N, GATES, HID, EpiBiasAct<>{dev + h->proj.b, xp, GATES}, st));
     hipLaunchKernelGGL(silero_rec_kernel, dim3((unsigned)nclips), dim3(REC_THREADS), 0, st, (const float*)xp, dev + h->whh, starts, N, hh);

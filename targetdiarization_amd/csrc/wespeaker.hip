@@ -24,6 +24,7 @@
 
 #include "../../include/tdx.h"
 #include "epilogues.hpp"
+#include "weight_pack.hpp"
 
 using namespace tdx;
 
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(256) void seg1_kernel(const float* __restrict__ sta
     if (tid == 0) emb[(long)r * EMB + n] = (red[0] + red[1]) + (red[2] + red[3]) + bias[n];
 }
 
-struct ConvW { size_t w, b, wn; int N, Npad, cin, taps; };      // w: [Npad][taps][cin] (shared core); wn: [9][N][cin] (narrow) or 0
+struct ConvW : tdx::GemmW { size_t wn = 0; };      // w: [Npad][taps][cinp = cin] (shared core); wn: [9][N][cin] (narrow) or 0
 struct BlockW { ConvW c1, c2, sc; bool has_sc; int cin, cout, stride; };
 
 // a convolution as an implicit GEMM on the shared fp32 core (a third copy of the launcher of eres2net.hip / campplus.hip: those
@@ -273,9 +274,9 @@ struct BlockW { ConvW c1, c2, sc; bool has_sc; int cin, cout, stride; };
 template <class Epi>
 int conv_gemm(const float* A, const float* dev, const ConvW& cw, int B, int Hin, int Win, int Hout, int Wout, int stride, Epi e, hipStream_t st) {
     const long M = (long)B * Hout * Wout;
-    GemmArgs g = make_args((int)M, cw.Npad, make_seg(A, cw.cin, dev + cw.w, (long)cw.taps * cw.cin, cw.cin));
+    GemmArgs g = make_args((int)M, cw.Npad, make_seg(A, cw.cinp, dev + cw.w, (long)cw.taps * cw.cinp, cw.cinp));
     g.n_valid = up(cw.N, 32);
-    g.cv_Hin = Hin; g.cv_Win = Win; g.cv_Hout = Hout; g.cv_Wout = Wout; g.cv_stride = stride; g.cv_ntaps = cw.taps; g.cv_cin = cw.cin;
+    g.cv_Hin = Hin; g.cv_Win = Win; g.cv_Hout = Hout; g.cv_Wout = Wout; g.cv_stride = stride; g.cv_ntaps = cw.taps; g.cv_cin = cw.cinp;
     if (launch_gemm<false, false, false, false, Epi, 0, true>(g, 1, e, st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
     return TDX_OK;
 }
@@ -308,36 +309,21 @@ int tdx_wespk_create(const void* blob, size_t blob_bytes, int device, tdx_wespk*
     if (!blob || !out) return tdx::fail(TDX_E_INVALID, "tdx_wespk_create: null argument");
     tdx::Loader ld;
     if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_wespk_create: malformed TDXW blob");
-    struct BN { std::vector<double> s, sh; };
+    using tdx::BN;
     auto bn = [&](const std::string& p, int N) -> BN {      // eval BatchNorm `p` -> y = x*s + sh
-        BN r; r.s.assign(N, 1.0); r.sh.assign(N, 0.0);
         const float *g = ld.get(p + "weight", {(uint32_t)N}), *be = ld.get(p + "bias", {(uint32_t)N});
         const float *mu = ld.get(p + "running_mean", {(uint32_t)N}), *var = ld.get(p + "running_var", {(uint32_t)N});
-        if (!g || !be || !mu || !var) return r;
-        for (int n = 0; n < N; ++n) {
-            r.s[n] = (double)g[n] / sqrt((double)var[n] + 1e-5);
-            r.sh[n] = (double)be[n] - (double)mu[n] * r.s[n];
-        }
-        return r;
+        return tdx::bn_fold(g, be, mu, var, N);
     };
     // bias-free conv [N,cin,k,k] + eval BatchNorm -> [Npad][taps][cin] + bias[Npad]; with `narrow` also [taps][N][cin]
     auto fold = [&](const std::string& wname, const std::string& bnp, int N, int cin, int k, bool narrow) -> ConvW {
-        ConvW cw{}; cw.N = N; cw.Npad = up(N, 128); cw.cin = cin; cw.taps = k * k;
         const float* W = ld.get(wname, {(uint32_t)N, (uint32_t)cin, (uint32_t)k, (uint32_t)k});
         const BN b = bn(bnp, N);
-        cw.w = ld.room((size_t)cw.Npad * cw.taps * cin);
-        cw.b = ld.room(cw.Npad);
+        ConvW cw{tdx::push_conv_gemm(ld, W, b.s.data(), b.sh.data(), N, cin, k * k, up(N, 128), cin)};
         if (narrow) cw.wn = ld.room((size_t)cw.taps * N * cin);
-        if (!W || !ld.ok()) return cw;
-        for (int n = 0; n < N; ++n) {
-            ld.host[cw.b + n] = (float)b.sh[n];
-            for (int c = 0; c < cin; ++c)
-                for (int t = 0; t < cw.taps; ++t) {
-                    const float v = (float)((double)W[((size_t)n * cin + c) * cw.taps + t] * b.s[n]);
-                    ld.host[cw.w + ((size_t)n * cw.taps + t) * cin + c] = v;
-                    if (narrow) ld.host[cw.wn + ((size_t)t * N + n) * cin + c] = v;
-                }
-        }
+        if (narrow && W) for (int n = 0; n < N; ++n)
+            for (int t = 0; t < cw.taps; ++t)
+                memcpy(&ld.host[cw.wn + ((size_t)t * N + n) * cin], &ld.host[cw.w + ((size_t)n * cw.taps + t) * cin], cin * sizeof(float));
         return cw;
     };
     std::unique_ptr<tdx_wespk> h(new tdx_wespk());
@@ -348,13 +334,7 @@ int tdx_wespk_create(const void* blob, size_t blob_bytes, int device, tdx_wespk*
     }
     {   // resnet.conv1 [32,1,3,3] + bn1 -> w9[9][32], bias[32]
         const float* W = ld.get("resnet.conv1.weight", {(uint32_t)C0, 1, 3, 3});
-        const BN b = bn("resnet.bn1.", C0);
-        h->stem_w = ld.room(9 * C0);
-        h->stem_b = ld.room(C0);
-        if (W && ld.ok()) for (int n = 0; n < C0; ++n) {
-            ld.host[h->stem_b + n] = (float)b.sh[n];
-            for (int t = 0; t < 9; ++t) ld.host[h->stem_w + t * C0 + n] = (float)((double)W[n * 9 + t] * b.s[n]);
-        }
+        tdx::push_stem9(ld, W, bn("resnet.bn1.", C0), C0, h->stem_w, h->stem_b);
     }
     int cin = C0;
     for (int L = 0; L < NSTAGE; ++L) {

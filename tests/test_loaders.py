@@ -35,7 +35,19 @@ MODELS = {
                  lambda l, b, n, h: l.tdx_campp_create(b, n, 0, h), True, "xvector.block2.tdnnd17.cam_layer.linear2.bias", None),
     "fsmn_vad": (lambda: _fsmn_vad_tensors(),
                  lambda l, b, n, h: l.tdx_fsmnvad_create(b, n, 0, h), True, "encoder.fsmn.2.affine.linear.weight", "encoder.in_linear1.linear.weight"),
+    "pyannet": (lambda: W.recipe_pyannet_state_dict(),
+                lambda l, b, n, h: l.tdx_pyannet_create(b, n, 0, h), True, "lstm.bias_hh_l3_reverse", "lstm.weight_ih_l0"),
+    "silero": (lambda: W.recipe_silero_vad_state_dict(),
+               lambda l, b, n, h: l.tdx_silero_create(b, n, 0, h), True, "decoder.rnn.bias_hh", "decoder.rnn.weight_ih"),
+    "wespeaker": (lambda: W.recipe_wespeaker_state_dict(),
+                  lambda l, b, n, h: l.tdx_wespk_create(b, n, 0, h), True, "resnet.layer3.5.bn2.running_var", "resnet.seg_1.weight"),
+    "sensevoice": (lambda: W.recipe_sensevoice_state_dict(num_blocks=1, tp_blocks=0, vocab=64),
+                   lambda l, b, n, h: l.tdx_sv_create(1, 0, 64, b, n, 0, h), False, "encoder.tp_norm.bias", "ctc.ctc_lo.weight"),
+    "pfdec_ts": (lambda: _pfdec_ts_tensors(),
+                 lambda l, b, n, h: l.tdx_pfdec_create(2, 64, b, n, 0, h), False, "predictor.blstm.bias_hh_l0_reverse", "predictor.blstm.weight_ih_l0"),
 }
+# the models' own packers, where they have one
+PACK = {"pyannet": W.pack_pyannet_blob, "silero": W.pack_silero_vad_blob}
 STRICT = [m for m, v in MODELS.items() if v[2]]
 SHAPED = [m for m, v in MODELS.items() if v[4]]
 
@@ -44,6 +56,13 @@ def _fsmn_vad_tensors():
     """the recipe plus the CMVN vectors pack_fsmn_vad_blob adds to it: the tensors tdx_fsmnvad_create reads"""
     sd = dict(W.recipe_fsmn_vad_state_dict())
     sd["cmvn.shift"] = torch.zeros(400); sd["cmvn.scale"] = torch.ones(400)
+    return sd
+
+
+def _pfdec_ts_tensors():
+    """the Paraformer decoder with the timestamp head's 12 tensors present"""
+    sd = dict(W.recipe_paraformer_decoder_state_dict(num_blocks=2, vocab=64))
+    sd.update(W.recipe_paraformer_timestamp_state_dict())
     return sd
 
 
@@ -60,7 +79,7 @@ def _tensors(model):
 
 
 def _create(lib, model, sd):
-    blob = W.pack_blob(sd)
+    blob = PACK.get(model, W.pack_blob)(sd)
     buf = (C.c_char * len(blob)).from_buffer_copy(blob)
     h = C.c_void_p()
     rc = MODELS[model][1](lib, buf, len(blob), C.byref(h))
