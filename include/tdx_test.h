@@ -37,6 +37,17 @@ int tdx_linear_variant(const float* a_dev, const float* w_dev, int M, int N, int
 int tdx_linear_epi(const float* a_dev, const float* w_dev, const float* bias_or_null, const float* res_or_null, float* out_dev,
                    int M, int Npad, int nreal, int K, int act, void* stream);
 
+/* the gated attention launch of a FLASH layer exactly as tdx_mf2_forward issues it (csrc/mf2_attention.hpp attention_core_h3 with the
+ * planes-out gate): o = (att_u*v) * sigmoid(att_v*u) as row-major split-f16 planes oP [B*S][4E bytes] with one scale os and one sum of
+ * squares oss per (128-channel segment, token): [E/128][B*S] floats each.  Inputs as tdx_cal_attention (four fp32 heads [B][S][128],
+ * v, u [B][S][E], rotary freqs [16]); u is also the gate's fp32 u operand.  h3a: 1 = the half-height kernel (gemm_h3a.hpp), 0 = the
+ * wide one (what TDX_H3A selects in the model); swap: the order of the two K segments on the half-height kernel (TDX_H3A_SWAP).
+ * kvu_out [B][128][2E] gets the reduced lin_k^T [v|u].  E % 128 == 0. */
+size_t tdx_attn_gate_planes_workspace_bytes(int B, int S, int E);
+int tdx_attn_gate_planes(const float* quad_q, const float* lin_q, const float* quad_k, const float* lin_k, const float* v,
+                         const float* u, const float* freqs, int B, int S, int E, int h3a, int swap, void* oP_dev, float* os_dev,
+                         float* oss_dev, float* kvu_out_dev, void* workspace, size_t workspace_bytes, void* stream);
+
 /* per-CU operand fill rates (tools/fill_bench*.py) */
 int tdx_fill_bench(int mode, const void* src_dev, long bytes_per_block, int blocks, int iters, float* sink_dev, void* stream);
 int tdx_fill_bench2(int mode, const void* src_dev, int stride, int blocks, int iters, float* sink_dev, void* stream);

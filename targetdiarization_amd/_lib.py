@@ -166,6 +166,8 @@ DIAG_SIGNATURES = {
     "tdx_h3_gemm_variant": (_i, [_vp] * 6 + [_i] * 4 + [_vp]),
     "tdx_linear_variant": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "tdx_linear_epi": (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
+    "tdx_attn_gate_planes_workspace_bytes": (_sz, [_i, _i, _i]),
+    "tdx_attn_gate_planes": (_i, [_vp] * 7 + [_i] * 5 + [_vp] * 5 + [_sz, _vp]),
     "tdx_fill_bench": (_i, [_i, _vp, _l, _i, _i, _vp, _vp]),
     "tdx_fill_bench2": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
     "tdx_fill_bench3": (_i, [_vp, _l, _i, _l, _i, _i, _i, _vp, _vp]),

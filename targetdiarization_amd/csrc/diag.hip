@@ -1,6 +1,7 @@
 // diag.hip — libtdx_diag.so: test hooks and timing diagnostics of the GEMM cores (declared in include/tdx_test.h).
 // NOT part of the product library: libtdx.so exports only what include/tdx.h declares.  Used by tests/test_gpu_h3.py
-// (numerics of the split-f16 x3 core in all operand modes) and by tools/ (timing variants, operand fill rates).
+// (numerics of the split-f16 x3 core in all operand modes), tests/test_gpu_attention_gate.py (the gated attention launch exactly as
+// the model issues it) and by tools/ (timing variants, operand fill rates).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -8,6 +9,7 @@
 #include "../../include/tdx.h"
 #include "../../include/tdx_test.h"
 #include "epilogues.hpp"
+#include "mf2_attention.hpp"
 
 using namespace tdx;
 
@@ -108,6 +110,36 @@ int tdx_h3_gemm(const void* pa, const float* sa, const void* pb, const float* sb
     g.seg[0] = tdx::h3_seg(pa, sa, 4L * K, pb, sb, 4L * K, K);
     g.nseg = 1; g.M = M; g.N = N;
     hipError_t r = tdx::launch_gemm_h3<false>(g, 1, EpiBiasAct<>{bias, c, N}, (hipStream_t)stream);
+    return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
+}
+
+// the gated attention launch on the model's own path: tests/test_gpu_attention_gate.py.  Packs the inputs and prepares the operand
+// planes as tdx_cal_attention does, then calls attention_core_h3 the way tdx_mf2_forward does — oP / os / oss set (the planes-out gate
+// EpiAttnGatePlOut), u itself as the gate's fp32 u operand — with the kernel choice (h3a) and the segment order (swap) as arguments
+// instead of the process-wide TDX_H3A / TDX_H3A_SWAP.  kvu_out gets Kvu [B][128][2E] (the reduced split-K launch).
+size_t tdx_attn_gate_planes_workspace_bytes(int B, int S, int E) {
+    if (B < 1 || S < 1 || E < 128 || E % 128) return 0;
+    int sp, kc; size_t a, b, c, d, e, tot;
+    attn_plan(B, S, E, sp, kc, a, b, c, d, e, tot);
+    return tot * sizeof(float);
+}
+int tdx_attn_gate_planes(const float* quad_q, const float* lin_q, const float* quad_k, const float* lin_k, const float* v, const float* u,
+                         const float* freqs, int B, int S, int E, int h3a, int swap, void* oP, float* os, float* oss, float* kvu_out,
+                         void* ws_, size_t ws_bytes, void* stream) {
+    if (!quad_q || !lin_q || !quad_k || !lin_k || !v || !u || !freqs || !oP || !os || !oss || !kvu_out || !ws_)
+        return tdx::fail(TDX_E_INVALID, "tdx_attn_gate_planes: null argument");
+    if (B < 1 || S < 1 || E < 128 || E % 128) return tdx::fail(TDX_E_INVALID, "tdx_attn_gate_planes: need E % 128 == 0");
+    int splits, kchunk; size_t oq, ovu, oA, oslab, okvu, tot;
+    attn_plan(B, S, E, splits, kchunk, oq, ovu, oA, oslab, okvu, tot);
+    if (ws_bytes < tot * sizeof(float)) return tdx::fail(TDX_E_WORKSPACE, "tdx_attn_gate_planes: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)ws_;
+    TRY(attn_pack_inputs(quad_q, lin_q, quad_k, lin_k, v, u, freqs, B, S, E, ws, oq, ovu, st));
+    AttnPlanes P;
+    TRY(attn_prepare_planes(ws, oq, ovu, okvu, B, S, E, P, st));
+    TRY(attention_core_h3(P.qkP, P.qks, P.vuP, nullptr, P.stt, B, S, E, splits, kchunk, ws + oA, P.AbufP, P.Asc, ws + oslab, ws + okvu, P.KvuP, P.kvus,
+                          nullptr, nullptr, nullptr, st, h3a != 0, swap != 0, (unsigned char*)oP, os, oss, nullptr, nullptr, nullptr, u));
+    const hipError_t r = hipMemcpyAsync(kvu_out, ws + okvu, (size_t)B * QK * 2 * E * sizeof(float), hipMemcpyDeviceToDevice, st);
     return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
 }
 
