@@ -493,6 +493,54 @@ int tdx_sv_forward(tdx_sv* h, const float* feats_dev, int B, int T, const int* p
 int tdx_ctc_collapse(const int* frame_ids_dev, int B, int S, int blank, int* tok_ids_dev, int* tok_frames_dev, int* counts_dev,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * N10  Whisper — replaces `AutoModelForSpeechSeq2Seq.from_pretrained(dir)` + `generate(input_features, task="transcribe",
+ *      language="chinese", num_beams=1, prompt_ids=...)` (ASRProcessor.py:244-251, 489-514; Hugging Face transformers'
+ *      WhisperForConditionalGeneration, pinned by tests/test_whisper_host.py).  fp32 throughout (the reference runs .half()),
+ *      greedy decoding only, one prefix per call.
+ *      create enforces, each with its own message: d_model / heads == 64 (encoder and decoder), gelu != 0 (activation_function
+ *      "gelu", the exact erf form), n_mels 80 or 128, 1 <= n_audio_ctx, n_text_ctx <= 32768, vocab >= 2, layers >= 1, the FFN
+ *      widths positive multiples of 64.
+ *      blob: TDXW container with transformers' names (model.encoder.*, model.decoder.*; proj_out.weight optional and then equal
+ *      to model.decoder.embed_tokens.weight); strict both ways, by shape, before any device work.
+ *      1 <= B <= 32 in every call (workspace_bytes returns 0 outside); one workspace size serves the three entry points.
+ *
+ *      tdx_whisper_logmel: WhisperFeatureExtractor.  wav_dev [B,N] 16 kHz in [-1,1]; lens_dev NULL or int32 [B] on the DEVICE,
+ *      the valid samples of each row (clamped to [0,N]).  Each clip is cut or zero-padded to 320 * n_audio_ctx samples, reflect-
+ *      padded by 200, framed (periodic Hann 400, hop 160, the last frame dropped), power spectrum, Slaney mel bank, log10 of
+ *      max(., 1e-10), clamped at the clip's own maximum - 8, (x + 4) / 4.  feat_dev [B, n_mels, 2 * n_audio_ctx].
+ *      tdx_whisper_encode: feat_dev -> enc_dev (NULL or [B, n_audio_ctx, d_model], the encoder's final LayerNorm output) and
+ *      enc_state_dev (NULL or [dec_layers][2][B][n_audio_ctx][d_model]: the cross-attention K and V of every decoder layer).
+ *      tdx_whisper_decode: greedy decoding of B clips from enc_state_dev.  prefix_host: prefix_len >= 1 ids common to the clips,
+ *      fed one per step through the same kernels as generated tokens (no batched prefill).  Step p reads the token at position p;
+ *      step_ids_dev / step_scores_dev [B, n_text_ctx] receive at [b][p] the argmax over the unsuppressed vocabulary (ties: the
+ *      lowest id) and its log-softmax; positions no step reached are left untouched.  suppress_host ids are masked at every
+ *      step, begin_suppress_host ids at step prefix_len - 1 only.  min(max_new, n_text_ctx - prefix_len) tokens are generated
+ *      at most (positions prefix_len ...); counts_dev [B] = tokens generated per clip, a final `eos` included; with max_new = 0
+ *      the prefix is scored whole and nothing is generated.  A clip that emitted eos stops writing and does not disturb the
+ *      others; a clip's results do not depend on the other clips of its batch (the Linear is one kernel for B <= 8 and another from
+ *      9 rows on: across that line they agree to fp32 rounding).  The [B, vocab] logits are never stored.  Arguments
+ *      are validated before the device is touched.  The call enqueues 16 steps at a time and then waits for one pinned word,
+ *      the number of finished clips: it returns after the stream has drained and cannot be captured into a graph.
+ * ---------------------------------------------------------------------------------- */
+typedef struct tdx_whisper_config {
+    int32_t n_mels, n_audio_ctx, d_model, enc_heads, enc_layers, enc_ffn;
+    int32_t n_text_ctx, dec_heads, dec_layers, dec_ffn, vocab, gelu;
+    int32_t reserved[4];
+} tdx_whisper_config;
+typedef struct tdx_whisper tdx_whisper;
+int tdx_whisper_create(const tdx_whisper_config* cfg, const void* weights_blob, size_t blob_bytes, int device, tdx_whisper** out);
+int tdx_whisper_destroy(tdx_whisper* h);
+size_t tdx_whisper_workspace_bytes(const tdx_whisper* h, int B);
+double tdx_whisper_flops(const tdx_whisper* h, int B, int steps);
+int tdx_whisper_logmel(tdx_whisper* h, const float* wav_dev, const int* lens_dev, int B, long N, float* feat_dev, void* workspace_dev,
+                       size_t workspace_bytes, void* stream);
+int tdx_whisper_encode(tdx_whisper* h, const float* feat_dev, int B, float* enc_dev, float* enc_state_dev, void* workspace_dev,
+                       size_t workspace_bytes, void* stream);
+int tdx_whisper_decode(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int prefix_len, const int* suppress_host,
+                       int n_suppress, const int* begin_suppress_host, int n_begin, int eos, int max_new, int* step_ids_dev,
+                       float* step_scores_dev, int* counts_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

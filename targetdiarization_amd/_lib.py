@@ -23,6 +23,12 @@ class MdxConfig(C.Structure):
                 ("dim_f", C.c_int32), ("dim_t", C.c_int32), ("reserved", C.c_int32)]
 
 
+class WhisperConfig(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("n_audio_ctx", C.c_int32), ("d_model", C.c_int32), ("enc_heads", C.c_int32),
+                ("enc_layers", C.c_int32), ("enc_ffn", C.c_int32), ("n_text_ctx", C.c_int32), ("dec_heads", C.c_int32),
+                ("dec_layers", C.c_int32), ("dec_ffn", C.c_int32), ("vocab", C.c_int32), ("gelu", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 _lib = None
 
 # every symbol include/tdx.h declares: (restype, argtypes)
@@ -127,6 +133,13 @@ SIGNATURES = {
     "tdx_sv_flops": (C.c_double, [_vp, _i, _i]),
     "tdx_sv_forward": (_i, [_vp, _fp, _i, _i, C.POINTER(C.c_int), _fp, _vp, _fp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tdx_ctc_collapse": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "tdx_whisper_create": (_i, [C.POINTER(WhisperConfig), _vp, _sz, _i, C.POINTER(_vp)]),
+    "tdx_whisper_destroy": (_i, [_vp]),
+    "tdx_whisper_workspace_bytes": (_sz, [_vp, _i]),
+    "tdx_whisper_flops": (C.c_double, [_vp, _i, _i]),
+    "tdx_whisper_logmel": (_i, [_vp, _fp, _vp, _i, C.c_long, _fp, _vp, _sz, _vp]),
+    "tdx_whisper_encode": (_i, [_vp, _fp, _i, _fp, _fp, _vp, _sz, _vp]),
+    "tdx_whisper_decode": (_i, [_vp, _fp, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, _i, _i, _vp, _fp, _vp, _vp, _sz, _vp]),
 }
 
 

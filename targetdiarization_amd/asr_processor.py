@@ -20,7 +20,8 @@ class ASRProcessor:
                  is_asr_api: bool = False, api_config_path: str = "", verbose_log: bool = True, cuda_device: int = 0, ap=None,
                  *, asr_state_dict=None, decoder: Optional[Callable] = None, punctuation: Optional[Callable] = None, token_list=None,
                  punc_state_dict=None, punc_vocab=None, vad_state_dict=None, vad_cmvn=None,
-                 sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None):
+                 sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None,
+                 whisper_state_dict=None, whisper_config=None, whisper_token_list=None, whisper_tokenizer=None, whisper_generation_config=None):
         self.is_asr = is_asr
         self.verbose_log = verbose_log
         self.ap = ap
@@ -65,6 +66,20 @@ class ASRProcessor:
                 self.is_asr = True
             except Exception as e:
                 print(f"Load ASR model failed: {e}")
+        # ASRProcessor.py:244-251: the Whisper engine, from weights or from a directory whose name says "whisper" and "finetune"
+        import os
+        wdir = asr_model_dir if isinstance(asr_model_dir, str) and "whisper" in asr_model_dir.lower() and "finetune" in asr_model_dir.lower() \
+            and os.path.isdir(asr_model_dir) else None
+        if is_asr and (whisper_state_dict is not None or wdir is not None):
+            try:
+                from .whisper import build_whisper
+                m = build_whisper(whisper_state_dict, whisper_config, wdir, whisper_token_list, whisper_tokenizer, whisper_generation_config, cuda_device)
+                if m is None:
+                    raise FileNotFoundError(f"{wdir!r} holds no config.json with model.safetensors or pytorch_model.bin")
+                self.asr["whisper_finetune"] = m
+                self.is_asr = True
+            except Exception as e:
+                print(f"Failed to load Whisper finetune model: {e}")
 
     def _nar_decode(self, enc_out):
         """encoder output [T',512] -> {"text", "timestamp"} through the device CIF predictor + NAR decoder"""
@@ -184,6 +199,20 @@ class ASRProcessor:
             for clip in res:
                 lang, emo, text = parse_tagged_text(clip["text"], no_punc)
                 result_list.append({"key": clip["key"], "language": lang, "text": text, "emotion": emo})
+            return join_text_only(result_list) if output_text_only else result_list
+        if asr_engine == "whisper_finetune":             # :489-526
+            from .sensevoice import join_text_only
+            m = self.asr["whisper_finetune"]
+            prompt_ids = None
+            if m.tokenizer is not None:                  # :505 encodes the prompt whatever it is, the empty one included
+                prompt_ids = m.tokenizer.get_prompt_ids(prompt)
+            elif prompt:
+                print("Whisper: no tokenizer loaded, the prompt is ignored.")
+            clips = [np.asarray(w, dtype=np.float32).reshape(-1)[:480000] for w in wavs]     # the feature extractor keeps 30 s
+            res = m.generate(clips, language="chinese", task="transcribe", prompt_ids=prompt_ids, keys=[str(k) for k in range(len(clips))])
+            if output_raw_result:
+                return res
+            result_list = [{"key": r["key"], "language": self.detect_language(r["text"]), "text": r["text"].strip()} for r in res]
             return join_text_only(result_list) if output_text_only else result_list
         enc = self.asr["paraformer"]
         for k, w in enumerate(wavs):

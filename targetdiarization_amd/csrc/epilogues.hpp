@@ -36,6 +36,7 @@ struct ActNone { __device__ static float f(float v) { return v; } };
 struct ActRelu { __device__ static float f(float v) { return fmaxf(v, 0.f); } };
 struct ActRelu20 { __device__ static float f(float v) { return relu20(v); } };
 struct ActSilu { __device__ static float f(float v) { return siluf_acc(v); } };
+struct ActGelu { __device__ static float f(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); } };      // exact (erf) GELU, nn.GELU()
 template <int NUM = 1, int DEN = 100>      // slope NUM / DEN as a compile-time constant (a float cannot be a template argument)
 struct ActLeaky { __device__ static float f(float v) { return leaky(v, (float)NUM / (float)DEN); } };
 

@@ -1,0 +1,1026 @@
+// whisper.hip — Whisper on MI355X (include/tdx.h N10): the reference's third local recogniser,
+// `AutoModelForSpeechSeq2Seq.from_pretrained(...)` + `generate(task="transcribe", language="chinese", num_beams=1, prompt_ids=...)`
+// (ASRProcessor.py:244-251, 489-514).  Hugging Face transformers' WhisperForConditionalGeneration is the upstream;
+// tests/whisper_oracle.py restates it and tests/test_whisper_host.py pins the restatement to it.  Everything fp32.
+//
+//   log-mel   reflect-padded clips as overlapping rows (pitch 160) x [window * DFT basis] on the fp32 MFMA core (re, im pairs ->
+//             power), x Slaney mel bank -> log10, transposed store; per-clip max, clamp at max - 8, (x + 4) / 4
+//   encoder   conv1 / conv2 as GEMMs over channel-last rows with a zero frame on either side (taps contiguous, conv2 at row pitch
+//             2 d), GELU, + positions; L pre-LN layers: LayerNorm rows, q / k / v / out / fc1 / fc2 through linear_f32, attention
+//             as one streaming-softmax kernel (no score map is ever stored); final LayerNorm; the cross K / V of every decoder layer
+//   decode    one token per clip per step, B <= 32, state on the device (cur_tok, pos, done): embed; per layer a skinny Linear
+//             launch for q | k | v (k, v land in the cache row `pos`), single-query attention in key chunks of 256 + a combine,
+//             out_proj + residual, the same for the cross attention over the precomputed K / V, fc1 + GELU, fc2 + residual; the
+//             vocabulary head in 64-column slices (max, argmax, sum exp per row and slice, suppression mask applied, logits never
+//             stored) and one combine launch that writes the per-position outputs, the next token, pos + 1 and the done flags.
+//             The host enqueues 16 steps at a time and then reads one pinned word (the number of finished clips).
+//
+// Skinny Linear (wh_skinny_kernel): a workgroup owns 4 output columns; its 4 waves split K in interleaved 256-float chunks, a
+// lane keeps B x 4 accumulators (plain fp32 FMA; every weight element is loaded once for all B rows), the 64 lanes meet in a
+// transposing butterfly (126 exchanges for 128 sums), the 4 waves in LDS.  The summation order of an output element is the same
+// whatever B is and whichever rows share the launch, so a clip decoded alone gives the bits it gives in a batch.  From 9 rows on
+// the Linear runs on MFMA tiles instead (wh_skinny_mfma_kernel + wh_sk_finish_kernel, further down), with the same property.
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+
+#include "epilogues.hpp"
+
+using namespace tdx;
+
+namespace {
+
+constexpr int DK = 64;                                   // head width of every Whisper size
+constexpr int NFFT = 400, HOP = 160, NBIN = 201;
+constexpr int NBINP = 256;                               // bins padded to the paired GEMM's 64-column tiles
+constexpr int KFR = 416;                                 // frame length padded to a multiple of 32 (basis columns 400.. are zero)
+constexpr int PWP = 224;                                 // pitch of the power rows (columns 201.. are exact zeros)
+constexpr int MELP = 128;                                // mel rows of the filter bank image (rows n_mels.. are zero)
+constexpr int WH_MAXB = 32, WH_CHUNK = 16;               // clips per decode call; steps enqueued between two host reads
+constexpr int WH_SLICE = 64;                             // vocabulary columns per head workgroup
+constexpr int WH_KEYS = 256;                             // keys per single-query attention workgroup
+constexpr int WH_MAXCTX = 1 << 15;
+constexpr float LN_EPS = 1e-5f;
+
+__device__ __forceinline__ float gelu_erf(float v) { return ActGelu::f(v); }
+
+// ------------------------------------------------------------------------------------------------ log-mel
+// the clip cut / zero-padded to P samples, reflect-padded by 200 on either side, then zeros up to the row pitch
+__global__ __launch_bounds__(256) void wh_pad_kernel(const float* __restrict__ wav, const int* __restrict__ lens, long N, int P, int pitch,
+                                                      float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (i >= pitch) return;
+    long n = lens ? (long)lens[b] : N;
+    n = n < 0 ? 0 : (n > N ? N : n);
+    float v = 0.f;
+    if (i < P + NFFT) {
+        int j = i - NFFT / 2;
+        if (j < 0) j = -j;
+        if (j >= P) j = 2 * (P - 1) - j;
+        if (j < n) v = wav[(long)b * N + j];
+    }
+    out[(long)b * pitch + i] = v;
+}
+struct EpiPow {
+    float* pw;
+    __device__ EpiNone col(int, int) const { return EpiNone{}; }
+    __device__ EpiNone row(int, int) const { return EpiNone{}; }
+    __device__ void store2(int, int m, int c, float re, float im, EpiNone, EpiNone) const {
+        if (c < PWP) pw[(long)m * PWP + c] = re * re + im * im;
+    }
+};
+// row m = rp * b + f is frame f of clip b when f < T; feat [B][n_mels][T]
+struct EpiLogMelT {
+    float* feat; int rp, T, n_mels;
+    __device__ EpiNone col(int, int) const { return EpiNone{}; }
+    __device__ EpiNone row(int, int) const { return EpiNone{}; }
+    __device__ void store(int, int m, int n, float v, EpiNone, EpiNone) const {
+        const int b = m / rp, f = m - b * rp;
+        if (f < T && n < n_mels) feat[((long)b * n_mels + n) * T + f] = v > 1e-10f ? log10f(v) : -10.0f;      // the floor is exact: log10f(1e-10f) is not
+    }
+};
+// per clip: the maximum of the whole map, then max(x, max - 8) -> (x + 4) / 4
+__global__ __launch_bounds__(1024) void wh_clamp_kernel(float* __restrict__ feat, long n) {
+    __shared__ float red[16];
+    float* x = feat + (long)blockIdx.x * n;
+    const int tid = threadIdx.x;
+    float mx = -INFINITY;
+    for (long i = tid; i < n; i += 1024) mx = fmaxf(mx, x[i]);
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) red[tid >> 6] = mx;
+    __syncthreads();
+    mx = red[0];
+    for (int w = 1; w < 16; ++w) mx = fmaxf(mx, red[w]);
+    const float lo = mx - 8.0f;
+    for (long i = tid; i < n; i += 1024) x[i] = (fmaxf(x[i], lo) + 4.0f) / 4.0f;
+}
+
+// ------------------------------------------------------------------------------------------------ encoder
+// feat [B][n_mels][T] -> channel-last rows [B][T + 2][MP] with a zero frame on either side and zero channels n_mels..MP-1
+__global__ void wh_chlast_kernel(const float* __restrict__ feat, int n_mels, int T, int MP, float* __restrict__ xc) {
+    const int r = blockIdx.x, b = blockIdx.y, c = threadIdx.x;
+    float v = 0.f;
+    if (r >= 1 && r <= T && c < n_mels) v = feat[((long)b * n_mels + c) * T + r - 1];
+    xc[((long)b * (T + 2) + r) * MP + c] = v;
+}
+// rows 0 and T + 1 of every clip of c1 [B][T + 2][d]
+__global__ void wh_zero_edge_kernel(float* __restrict__ c1, int T, int d) {
+    float* p = c1 + ((long)blockIdx.y * (T + 2) + (blockIdx.x ? T + 1 : 0)) * d;
+    for (int i = threadIdx.x; i < d; i += blockDim.x) p[i] = 0.f;
+}
+// conv1: GEMM row m = (T + 2) b + t -> c1 row (T + 2) b + t + 1
+struct EpiConv1 {
+    const float* b; float* out; int T, d;
+    __device__ float col(int, int n) const { return n < d ? b[n] : 0.f; }
+    __device__ EpiNone row(int, int) const { return EpiNone{}; }
+    __device__ void store(int, int m, int n, float v, EpiNone, float c) const {
+        const int bi = m / (T + 2), t = m - bi * (T + 2);
+        if (t < T && n < d) out[((long)bi * (T + 2) + t + 1) * d + n] = gelu_erf(v + c);
+    }
+};
+// conv2: GEMM row m = (S + 1) b + t -> x row S b + t, + the position row t
+struct EpiConv2 {
+    const float* b; const float* pos; float* out; int S, d;
+    __device__ float col(int, int n) const { return n < d ? b[n] : 0.f; }
+    __device__ EpiNone row(int, int) const { return EpiNone{}; }
+    __device__ void store(int, int m, int n, float v, EpiNone, float c) const {
+        const int bi = m / (S + 1), t = m - bi * (S + 1);
+        if (t < S && n < d) out[((long)bi * S + t) * d + n] = gelu_erf(v + c) + pos[(long)t * d + n];
+    }
+};
+// LayerNorm of rows of d floats (d % 4 == 0), one wave per row, two passes (mean, then the centred squares)
+__global__ __launch_bounds__(256) void wh_ln_rows_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ be,
+                                                          float* __restrict__ y, long M, int d) {
+    const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (m >= M) return;
+    const float* xr = x + m * d;
+    float s = 0.f;
+    for (int k = 4 * lane; k < d; k += 256) { const f32x4 v = ldg4(xr + k); s += (v[0] + v[1]) + (v[2] + v[3]); }
+    const float mean = wave_sum(s) / (float)d;
+    float q = 0.f;
+    for (int k = 4 * lane; k < d; k += 256) {
+        const f32x4 v = ldg4(xr + k);
+        const float a0 = v[0] - mean, a1 = v[1] - mean, a2 = v[2] - mean, a3 = v[3] - mean;
+        q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + LN_EPS);
+    for (int k = 4 * lane; k < d; k += 256) {
+        const f32x4 v = ldg4(xr + k), gv = ldg4(g + k), bv = ldg4(be + k);
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = fmaf((v[j] - mean) * rstd, gv[j], bv[j]);
+        *reinterpret_cast<f32x4*>(y + m * d + k) = o;
+    }
+}
+// Full softmax attention over S keys, head width 64, q scaled by 1/8 on load.  Workgroup (qt, h, b): 64 queries; thread
+// (query t >> 2, part t & 3) owns 16 of the 64 dimensions of its query and of its output; a 64-key tile of K and V sits in LDS
+// (every lane of a quad reads the same key row: broadcasts); the four parts of a score meet in two DPP quad exchanges; the
+// softmax streams in chunks of 8 keys with a running maximum, so no score leaves the registers.
+__global__ __launch_bounds__(256) void wh_enc_attn_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                           float* __restrict__ out, int S, int d) {
+    __shared__ __attribute__((aligned(16))) float Ks[64 * DK];
+    __shared__ __attribute__((aligned(16))) float Vs[64 * DK];
+    const int tid = threadIdx.x, qi = tid >> 2, p = tid & 3;
+    const int h = blockIdx.y, b = blockIdx.z;
+    const int qg = blockIdx.x * 64 + qi;
+    const long base = (long)b * S * d + (long)h * DK;
+    float qv[16], acc[16];
+    {
+        const float* qr = q + base + (long)min(qg, S - 1) * d + 16 * p;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f32x4 t = ldg4(qr + 4 * i);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { qv[4 * i + j] = t[j] * 0.125f; acc[4 * i + j] = 0.f; }
+        }
+    }
+    float mrun = -INFINITY, lrun = 0.f;
+    for (int k0 = 0; k0 < S; k0 += 64) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i, r = e >> 4, c = (e & 15) * 4;
+            const long off = base + (long)min(k0 + r, S - 1) * d + c;
+            *reinterpret_cast<f32x4*>(Ks + r * DK + c) = ldg4(k + off);
+            *reinterpret_cast<f32x4*>(Vs + r * DK + c) = ldg4(v + off);
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int j0 = 0; j0 < 64 && k0 + j0 < S; j0 += 8) {
+            float s[8];
+            float cm = -INFINITY;
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+                const float* kr = Ks + (j0 + jj) * DK + 16 * p;
+                float a = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const f32x4 t = *reinterpret_cast<const f32x4*>(kr + 4 * i);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) a = fmaf(qv[4 * i + j], t[j], a);
+                }
+                a += h3_dpp(a, 0);
+                a += h3_dpp(a, 1);
+                s[jj] = (k0 + j0 + jj < S) ? a : -INFINITY;
+                cm = fmaxf(cm, s[jj]);
+            }
+            if (cm > mrun) {
+                const float sc = expf(mrun - cm);
+                lrun *= sc;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] *= sc;
+                mrun = cm;
+            }
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+                const float pj = expf(s[jj] - mrun);
+                lrun += pj;
+                const float* vr = Vs + (j0 + jj) * DK + 16 * p;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const f32x4 t = *reinterpret_cast<const f32x4*>(vr + 4 * i);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[4 * i + j] = fmaf(pj, t[j], acc[4 * i + j]);
+                }
+            }
+        }
+    }
+    if (qg < S) {
+        float* o = out + base + (long)qg * d + 16 * p;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            f32x4 t;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = acc[4 * i + j] / lrun;
+            *reinterpret_cast<f32x4*>(o + 4 * i) = t;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ decode step
+__global__ __launch_bounds__(256) void wh_embed_kernel(const float* __restrict__ tok, const float* __restrict__ pe, const int* __restrict__ cur,
+                                                        const int* __restrict__ pos, float* __restrict__ x, int d) {
+    const int b = blockIdx.x;
+    const float* t = tok + (long)cur[b] * d;
+    const float* p = pe + (long)pos[b] * d;
+    for (int i = threadIdx.x; i < d; i += 256) x[(long)b * d + i] = t[i] + p[i];
+}
+
+// one output of a skinny launch: y[row(b)][n] = act((x . W[n]) + bias[n]) + res[b][n]; row(b) = b, or brow * b + pos[b]
+// (the cache row of the token being decoded) when brow > 0
+struct SkJob { const float* W; const float* bias; const float* res; float* y; long ld; int brow; int gelu; };
+struct SkArgs { const float* x; const float* lng; const float* lnb; const int* pos; int B, N, K; SkJob job[3]; };
+
+// LayerNorm statistics of the B rows into LDS (mean, 1 / std): wave w takes the rows w, w + 4, ... and walks them together, so
+// that the loads of its (up to 8) rows are in flight at once; per row the sums run over k in ascending order
+__device__ __forceinline__ void sk_stats(const SkArgs& a, float* stat, int wave, int lane) {
+    constexpr int R = WH_MAXB / 4;
+    float s[R], mean[R], q[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) { s[i] = 0.f; q[i] = 0.f; }
+    for (int k = 4 * lane; k < a.K; k += 256)
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (wave + 4 * i < a.B) { const f32x4 v = ldg4(a.x + (long)(wave + 4 * i) * a.K + k); s[i] += (v[0] + v[1]) + (v[2] + v[3]); }
+#pragma unroll
+    for (int i = 0; i < R; ++i) mean[i] = wave_sum(s[i]) / (float)a.K;
+    for (int k = 4 * lane; k < a.K; k += 256)
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (wave + 4 * i < a.B) {
+                const f32x4 v = ldg4(a.x + (long)(wave + 4 * i) * a.K + k);
+                const float a0 = v[0] - mean[i], a1 = v[1] - mean[i], a2 = v[2] - mean[i], a3 = v[3] - mean[i];
+                q[i] += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+            }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const float rstd = 1.0f / sqrtf(wave_sum(q[i]) / (float)a.K + LN_EPS);
+        if (lane == 0 && wave + 4 * i < a.B) { stat[2 * (wave + 4 * i)] = mean[i]; stat[2 * (wave + 4 * i) + 1] = rstd; }
+    }
+}
+// acc[4 b + c] += sum over this wave's k of LN?(x)[b][k] * W[n0 + c][k]; wave w owns the 256-float chunks w, w + 4, ...
+template <int BT>
+__device__ __forceinline__ void sk_accumulate(const SkArgs& a, const float* __restrict__ W, int n0, const float* stat, int wave, int lane, float (&acc)[4 * BT]) {
+    const float* Wr[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) Wr[c] = W + (long)min(n0 + c, a.N - 1) * a.K;
+    const bool ln = a.lng != nullptr;
+    for (int k = (wave * 64 + lane) * 4; k < a.K; k += 1024) {
+        f32x4 wv[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) wv[c] = ldg4(Wr[c] + k);
+        f32x4 g{1.f, 1.f, 1.f, 1.f}, be{0.f, 0.f, 0.f, 0.f};
+        if (ln) { g = ldg4(a.lng + k); be = ldg4(a.lnb + k); }
+#pragma unroll
+        for (int b = 0; b < BT; ++b) {
+            f32x4 xv = ldg4(a.x + (long)min(b, a.B - 1) * a.K + k);
+            if (ln) {
+                const float mean = stat[2 * min(b, a.B - 1)], rstd = stat[2 * min(b, a.B - 1) + 1];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) xv[j] = fmaf((xv[j] - mean) * rstd, g[j], be[j]);
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[4 * b + c] = fmaf(xv[j], wv[c][j], acc[4 * b + c]);
+        }
+    }
+}
+// Sums NV values per lane over the 64 lanes.  While more than one value is left a step halves them: a lane keeps the half its
+// bit M selects and receives the partner's sums for it; the remaining steps are plain exchanges.  A sum is the same tree over
+// the lanes (masks 32, 16, ... 1) wherever in the array it sits.  Lanes whose `writer` stays set hold values idx .. idx + N - 1.
+template <int N, int M>
+__device__ __forceinline__ void sk_butterfly(float* v, int lane, int& idx, bool& writer, int& nleft) {
+    if constexpr (M == 0) { nleft = N; }
+    else {
+        const bool up = (lane & M) != 0;
+        if constexpr (N > 1) {
+            constexpr int H = N / 2;
+#pragma unroll
+            for (int i = 0; i < H; ++i) {
+                const float send = up ? v[i] : v[i + H], keep = up ? v[i + H] : v[i];
+                v[i] = keep + __shfl_xor(send, M, 64);
+            }
+            if (up) idx += H;
+            sk_butterfly<H, M / 2>(v, lane, idx, writer, nleft);
+        } else {
+            v[0] += __shfl_xor(v[0], M, 64);
+            if (up) writer = false;
+            sk_butterfly<1, M / 2>(v, lane, idx, writer, nleft);
+        }
+    }
+}
+template <int BT>
+__device__ __forceinline__ void sk_reduce_to_lds(float (&acc)[4 * BT], int lane, float* out) {
+    int idx = 0, nleft = 0;
+    bool writer = true;
+    sk_butterfly<4 * BT, 32>(acc, lane, idx, writer, nleft);
+    if (writer) {
+        if constexpr (4 * BT >= 128) { out[idx] = acc[0]; out[idx + 1] = acc[1]; }
+        else out[idx] = acc[0];
+    }
+}
+
+// grid (ceil(N / 4), jobs)
+template <int BT>
+__global__ __launch_bounds__(256) void wh_skinny_kernel(SkArgs a) {
+    __shared__ float stat[2 * WH_MAXB];
+    __shared__ float red[4][4 * BT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const SkJob& jb = a.job[blockIdx.y];
+    const int n0 = blockIdx.x * 4;
+    if (a.lng) { sk_stats(a, stat, wave, lane); __syncthreads(); }
+    float acc[4 * BT];
+#pragma unroll
+    for (int i = 0; i < 4 * BT; ++i) acc[i] = 0.f;
+    sk_accumulate<BT>(a, jb.W, n0, stat, wave, lane, acc);
+    sk_reduce_to_lds<BT>(acc, lane, red[wave]);
+    __syncthreads();
+    for (int e = tid; e < 4 * BT; e += 256) {
+        const int b = e >> 2, n = n0 + (e & 3);
+        if (b >= a.B || n >= a.N) continue;
+        float v = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+        v += jb.bias ? jb.bias[n] : 0.f;
+        if (jb.gelu) v = gelu_erf(v);
+        if (jb.res) v += jb.res[(long)b * a.N + n];
+        const long row = jb.brow > 0 ? (long)jb.brow * b + a.pos[b] : b;
+        jb.y[row * jb.ld + n] = v;
+    }
+}
+
+// Skinny Linear for 9..32 rows.  At that many rows an fp32-FMA lane would need 128 accumulators and 32 loads of x per weight
+// load; here the rows are one operand of v_mfma_f32_32x32x2_f32 (exact fp32 products; operand map of gemm.hpp / sensevoice.hip:
+// lane l supplies x[row l&31][k] and W[col l&31][k] for the four k = 8 kc + 4 (l>>5) + j of one 16-byte load), so a wave keeps 16
+// accumulators and reads as many bytes of x (from L2) as of W.  Workgroup (column tile of 32, K split s, job): its 4 waves take
+// the 8-float k blocks kc = 4 s + w, + 4 KS, ...; the waves meet in LDS and one partial [32][32] goes to the workspace.
+// wh_sk_finish_kernel adds the KS partials in order and applies bias / GELU / residual / the cache row.  KS depends on N and K
+// only, x is LayerNorm'ed once by wh_ln_rows_kernel: a row's bits do not depend on the other rows of the launch.
+constexpr int SKM_PITCH = 33;
+__global__ __launch_bounds__(256) void wh_skinny_mfma_kernel(SkArgs a, int KS, float* __restrict__ partial) {
+    __shared__ float red[4][32 * SKM_PITCH];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
+    const int n0 = blockIdx.x * 32, s = blockIdx.y, job = blockIdx.z;
+    const float* __restrict__ W = a.job[job].W;
+    const float* const xr = a.x + (long)min(l31, a.B - 1) * a.K + 4 * hh;
+    const float* const wr = W + (long)min(n0 + l31, a.N - 1) * a.K + 4 * hh;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const int nkc = a.K >> 3;
+#pragma unroll 4
+    for (int kc = 4 * s + wave; kc < nkc; kc += 4 * KS) {
+        const f32x4 av = ldg4(xr + 8 * kc), bv = ldg4(wr + 8 * kc);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
+    }
+    // D: col = l31, row = (r&3) + 8*(r>>2) + 4*hh
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[wave][((r & 3) + 8 * (r >> 2) + 4 * hh) * SKM_PITCH + l31] = acc[r];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = tid + 256 * i, row = e >> 5, col = e & 31, o = row * SKM_PITCH + col;
+        if (row < a.B && n0 + col < a.N)
+            partial[(((long)job * KS + s) * WH_MAXB + row) * a.N + n0 + col] = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
+    }
+}
+// grid (ceil(B N / 256), jobs)
+__global__ __launch_bounds__(256) void wh_sk_finish_kernel(SkArgs a, int KS, const float* __restrict__ partial) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)a.B * a.N) return;
+    const int b = (int)(e / a.N), n = (int)(e - (long)b * a.N), job = blockIdx.y;
+    const SkJob& jb = a.job[job];
+    float v = 0.f;
+    for (int s = 0; s < KS; ++s) v += partial[(((long)job * KS + s) * WH_MAXB + b) * a.N + n];
+    v += jb.bias ? jb.bias[n] : 0.f;
+    if (jb.gelu) v = gelu_erf(v);
+    if (jb.res) v += jb.res[(long)b * a.N + n];
+    const long row = jb.brow > 0 ? (long)jb.brow * b + a.pos[b] : b;
+    jb.y[row * jb.ld + n] = v;
+}
+constexpr int SKM_MAXKS = 8;
+inline int skm_splits(int N, int K) {          // enough workgroups to pull on every CU; at least one k block per wave
+    const int tiles = (N + 31) / 32;
+    return std::max(1, std::min(std::min(SKM_MAXKS, (256 + tiles - 1) / tiles), K / 32));
+}
+
+// (max, argmax, sum of exp(v - max)) of a set of logits; the empty set is (-inf, INT_MAX, 0).  Ties: the lowest id, like torch.argmax.
+struct WhTop { float m; int i; float s; };
+__device__ __forceinline__ void wh_merge(WhTop& a, const WhTop& b) {
+    if (b.i == INT_MAX) return;
+    if (a.i == INT_MAX) { a = b; return; }
+    const float mx = fmaxf(a.m, b.m);
+    a.s = a.s * expf(a.m - mx) + b.s * expf(b.m - mx);
+    if (b.m > a.m || (b.m == a.m && b.i < a.i)) a.i = b.i;
+    a.m = mx;
+}
+// Vocabulary head: workgroup s sweeps columns [64 s, 64 s + 64) four at a time through the skinny Linear's loop (W = the token
+// embedding, no bias); thread (b, c) keeps the running triple of row b over its columns; one triple per (row, slice) goes out.
+// mask[n] bit 0: suppressed at every step, bit 1: suppressed when `begin`.
+template <int BT>
+__global__ __launch_bounds__(256) void wh_head_kernel(SkArgs a, const unsigned char* __restrict__ mask, int begin, float* __restrict__ pm,
+                                                       int* __restrict__ pi, float* __restrict__ ps, int nsl) {
+    __shared__ float stat[2 * WH_MAXB];
+    __shared__ float red[4][4 * BT];
+    __shared__ float tm[4 * BT], tsum[4 * BT];
+    __shared__ int ti[4 * BT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (a.lng) { sk_stats(a, stat, wave, lane); __syncthreads(); }
+    const int deny = begin ? 3 : 1;
+    WhTop top{-INFINITY, INT_MAX, 0.f};
+    for (int g = 0; g < WH_SLICE / 4; ++g) {
+        const int n0 = blockIdx.x * WH_SLICE + 4 * g;
+        if (n0 >= a.N) break;                                       // (uniform over the workgroup)
+        float acc[4 * BT];
+#pragma unroll
+        for (int i = 0; i < 4 * BT; ++i) acc[i] = 0.f;
+        sk_accumulate<BT>(a, a.job[0].W, n0, stat, wave, lane, acc);
+        sk_reduce_to_lds<BT>(acc, lane, red[wave]);
+        __syncthreads();
+        if (tid < 4 * BT) {
+            const int n = n0 + (tid & 3);
+            if (n < a.N && !(mask[n] & deny)) {
+                const float v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+                if (top.i == INT_MAX) top = WhTop{v, n, 1.f};
+                else if (v > top.m) { top.s = top.s * expf(top.m - v) + 1.f; top.m = v; top.i = n; }
+                else top.s += expf(v - top.m);
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < 4 * BT) { tm[tid] = top.m; ti[tid] = top.i; tsum[tid] = top.s; }
+    __syncthreads();
+    if (tid < BT && tid < a.B) {
+        WhTop t{-INFINITY, INT_MAX, 0.f};
+        for (int c = 0; c < 4; ++c) wh_merge(t, WhTop{tm[4 * tid + c], ti[4 * tid + c], tsum[4 * tid + c]});
+        const long o = (long)tid * nsl + blockIdx.x;
+        pm[o] = t.m; pi[o] = t.i; ps[o] = t.s;
+    }
+}
+
+// decode state on the device
+struct WhState { int* cur; int* pos; int* done; int* ndone; const int* prefix; };
+
+__global__ void wh_init_kernel(WhState s, int B, int* __restrict__ counts) {
+    const int b = threadIdx.x;
+    if (b < B) { s.cur[b] = s.prefix[0]; s.pos[b] = 0; s.done[b] = 0; counts[b] = 0; }
+    if (b == 0) *s.ndone = 0;
+}
+// The slices of a row -> (argmax, its log-softmax); then the step: the per-position outputs, the next token (forced while the
+// prefix lasts), pos + 1, the done flag, the count of finished clips.  32 lanes per clip, block = 32 B threads.
+__global__ __launch_bounds__(1024) void wh_next_kernel(const float* __restrict__ pm, const int* __restrict__ pi, const float* __restrict__ ps, int nsl,
+                                                        WhState s, int B, int T, int prefix_len, int gen_to, int eos, int* __restrict__ ids,
+                                                        float* __restrict__ score, int* __restrict__ counts) {
+    __shared__ int fin[WH_MAXB];
+    const int b = threadIdx.x >> 5, l = threadIdx.x & 31;
+    WhTop t{-INFINITY, INT_MAX, 0.f};
+    for (int j = l; j < nsl; j += 32) wh_merge(t, WhTop{pm[(long)b * nsl + j], pi[(long)b * nsl + j], ps[(long)b * nsl + j]});
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) {
+        WhTop u{__shfl_xor(t.m, o, 64), __shfl_xor(t.i, o, 64), __shfl_xor(t.s, o, 64)};
+        // both partners must end with the same triple: merge (lower lane's, upper lane's) in that order on both
+        WhTop lo = (l & o) ? u : t, hi = (l & o) ? t : u;
+        wh_merge(lo, hi);
+        t = lo;
+    }
+    if (l == 0) {
+        int d = s.done[b];
+        if (!d) {
+            const int p = s.pos[b];
+            const int am = t.i == INT_MAX ? eos : t.i;
+            ids[(long)b * T + p] = am;
+            score[(long)b * T + p] = -logf(t.s);
+            int nxt;
+            if (p + 1 < prefix_len) nxt = s.prefix[p + 1];
+            else {
+                nxt = am;
+                if (p < gen_to) { counts[b] += 1; if (nxt == eos) d = 1; }
+            }
+            s.cur[b] = nxt;
+            if (d) s.done[b] = 1;
+            else s.pos[b] = min(p + 1, T - 1);
+        }
+        fin[b] = d;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0;
+        for (int i = 0; i < B; ++i) n += fin[i];
+        *s.ndone = n;
+    }
+}
+
+// Single-query attention, one workgroup per (key chunk of 256, head, clip): scores of the chunk's keys (q scaled by 1/8),
+// their maximum, exponentials and sum, then the 64 outputs as 4 groups of 64 keys x 64 lanes (a V row is one
+// coalesced 256-byte read).  The chunk's (max, sum, unnormalised output) goes to the workspace; wh_attn_comb_kernel joins the
+// chunks.  The number of keys is pos[b] + 1 (self attention over the cache) or nfix (cross attention).
+__global__ __launch_bounds__(256) void wh_attn_part_kernel(const float* __restrict__ q, const float* __restrict__ Kc, const float* __restrict__ Vc,
+                                                            long clip_stride, int d, const int* __restrict__ pos, int nfix, float* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) float qs[DK];
+    __shared__ float sc[WH_KEYS];
+    __shared__ float red[4];
+    __shared__ float ored[4][DK];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z, nch = gridDim.x, H = gridDim.y;
+    const int n = pos ? pos[b] + 1 : nfix;
+    float* po = part + (((long)b * H + h) * nch + c) * (DK + 2);
+    const int j0 = c * WH_KEYS;
+    if (j0 >= n) {                                                  // (uniform over the workgroup)
+        if (tid < DK) po[2 + tid] = 0.f;
+        if (tid == 0) { po[0] = -INFINITY; po[1] = 0.f; }
+        return;
+    }
+    if (tid < DK) qs[tid] = q[(long)b * d + h * DK + tid] * 0.125f;
+    __syncthreads();
+    const float* Kb = Kc + (long)b * clip_stride + h * DK;
+    const float* Vb = Vc + (long)b * clip_stride + h * DK;
+    // scores: 16 lanes per key (a K row is one coalesced 256-byte read, 4 keys per wave instruction), 16 keys per pass
+    {
+        const int sub = tid & 15, kg = tid >> 4;
+        const f32x4 u = *reinterpret_cast<const f32x4*>(qs + 4 * sub);
+#pragma unroll 8
+        for (int ps = 0; ps < WH_KEYS / 16; ++ps) {
+            const int jk = j0 + 16 * ps + kg;
+            const f32x4 t = ldg4(Kb + (long)min(jk, n - 1) * d + 4 * sub);
+            const float dot = h3_row16_sum(fmaf(u[3], t[3], fmaf(u[2], t[2], fmaf(u[1], t[1], u[0] * t[0]))));
+            if (sub == 0) sc[16 * ps + kg] = jk < n ? dot : -INFINITY;
+        }
+    }
+    __syncthreads();
+    const int j = j0 + tid;
+    const float s = sc[tid];
+    float mx = wave_max(s);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const float pj = j < n ? expf(s - mx) : 0.f;
+    const float ls = wave_sum(pj);
+    __syncthreads();                                                // red and sc have been read by all
+    sc[tid] = pj;
+    if (lane == 0) red[wave] = ls;
+    __syncthreads();
+    float a = 0.f;
+    const int jend = min(64, n - j0 - 64 * wave);
+#pragma unroll 8
+    for (int jj = 0; jj < jend; ++jj) a = fmaf(sc[64 * wave + jj], Vb[(long)(j0 + 64 * wave + jj) * d + lane], a);
+    ored[wave][lane] = a;
+    __syncthreads();
+    if (tid < DK) po[2 + tid] = ((ored[0][tid] + ored[1][tid]) + ored[2][tid]) + ored[3][tid];
+    if (tid == 0) { po[0] = mx; po[1] = ((red[0] + red[1]) + red[2]) + red[3]; }
+}
+// grid (H, B), 64 threads
+__global__ __launch_bounds__(64) void wh_attn_comb_kernel(const float* __restrict__ part, int nch, float* __restrict__ out, int d) {
+    const int h = blockIdx.x, b = blockIdx.y, H = gridDim.x, i = threadIdx.x;
+    const float* p = part + ((long)b * H + h) * nch * (DK + 2);
+    float mx = -INFINITY;
+    for (int c = 0; c < nch; ++c) mx = fmaxf(mx, p[c * (DK + 2)]);
+    float l = 0.f, o = 0.f;
+    for (int c = 0; c < nch; ++c) {
+        const float w = expf(p[c * (DK + 2)] - mx);
+        l = fmaf(p[c * (DK + 2) + 1], w, l);
+        o = fmaf(p[c * (DK + 2) + 2 + i], w, o);
+    }
+    out[(long)b * d + h * DK + i] = o / l;
+}
+
+struct AttnW { const float *ln_g, *ln_b, *Wq, *bq, *Wk, *Wv, *bv, *Wo, *bo; };
+struct EncLayer { AttnW sa; const float *ln2_g, *ln2_b, *W1, *b1, *W2, *b2; };
+struct DecLayer { AttnW sa, ca; const float *ln3_g, *ln3_b, *W1, *b1, *W2, *b2; };
+struct AttnOff { size_t ln_g, ln_b, Wq, bq, Wk, Wv, bv, Wo, bo; };
+struct LayerOff { AttnOff sa, ca; size_t g, b, W1, b1, W2, b2; };
+
+size_t push_linear(Loader& ld, const std::string& name, int N, int K) {       // rows padded to the GEMM's 128-column tiles
+    return ld.push(ld.get(name, {(uint32_t)N, (uint32_t)K}), (size_t)N * K, (size_t)up(N, 128) * K);
+}
+void stage_attn(Loader& ld, const std::string& pre, const std::string& ln, int d, AttnOff& o) {
+    o.ln_g = ld.push(ld.get(ln + ".weight", d), d); o.ln_b = ld.push(ld.get(ln + ".bias", d), d);
+    o.Wq = push_linear(ld, pre + ".q_proj.weight", d, d); o.bq = ld.push(ld.get(pre + ".q_proj.bias", d), d);
+    o.Wk = push_linear(ld, pre + ".k_proj.weight", d, d);
+    o.Wv = push_linear(ld, pre + ".v_proj.weight", d, d); o.bv = ld.push(ld.get(pre + ".v_proj.bias", d), d);
+    o.Wo = push_linear(ld, pre + ".out_proj.weight", d, d); o.bo = ld.push(ld.get(pre + ".out_proj.bias", d), d);
+}
+void stage_ffn(Loader& ld, const std::string& pre, int d, int ffn, LayerOff& o) {
+    o.g = ld.push(ld.get(pre + "final_layer_norm.weight", d), d); o.b = ld.push(ld.get(pre + "final_layer_norm.bias", d), d);
+    o.W1 = push_linear(ld, pre + "fc1.weight", ffn, d); o.b1 = ld.push(ld.get(pre + "fc1.bias", ffn), ffn);
+    o.W2 = push_linear(ld, pre + "fc2.weight", d, ffn); o.b2 = ld.push(ld.get(pre + "fc2.bias", d), d);
+}
+AttnW bind_attn(const float* dev, const AttnOff& o) {
+    return AttnW{dev + o.ln_g, dev + o.ln_b, dev + o.Wq, dev + o.bq, dev + o.Wk, dev + o.Wv, dev + o.bv, dev + o.Wo, dev + o.bo};
+}
+
+double hz_to_mel(double f) { return f < 1000.0 ? 3.0 * f / 200.0 : 15.0 + std::log(f / 1000.0) * (27.0 / std::log(6.4)); }
+double mel_to_hz(double m) { return m < 15.0 ? 200.0 * m / 3.0 : 1000.0 * std::exp(std::log(6.4) / 27.0 * (m - 15.0)); }
+
+template <int BT>
+int launch_skinny_t(const SkArgs& a, int njobs, hipStream_t st) {
+    hipLaunchKernelGGL(wh_skinny_kernel<BT>, dim3((a.N + 3) / 4, njobs), dim3(256), 0, st, a);
+    LAUNCH_CHECK();
+    return TDX_OK;
+}
+// B <= 8: the fp32-FMA kernel, LayerNorm inside.  B > 8: LayerNorm rows into `xn` once, the MFMA kernel, the finish kernel.
+int launch_skinny(SkArgs a, int njobs, float* xn, float* partial, hipStream_t st) {
+    if (a.B <= 1) return launch_skinny_t<1>(a, njobs, st);
+    if (a.B <= 2) return launch_skinny_t<2>(a, njobs, st);
+    if (a.B <= 4) return launch_skinny_t<4>(a, njobs, st);
+    if (a.B <= 8) return launch_skinny_t<8>(a, njobs, st);
+    if (a.lng) {
+        hipLaunchKernelGGL(wh_ln_rows_kernel, dim3((a.B + 3) / 4), dim3(256), 0, st, a.x, a.lng, a.lnb, xn, (long)a.B, a.K);
+        LAUNCH_CHECK();
+        a.x = xn; a.lng = nullptr; a.lnb = nullptr;
+    }
+    const int KS = skm_splits(a.N, a.K);
+    hipLaunchKernelGGL(wh_skinny_mfma_kernel, dim3((a.N + 31) / 32, KS, njobs), dim3(256), 0, st, a, KS, partial);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(wh_sk_finish_kernel, dim3((unsigned)(((long)a.B * a.N + 255) / 256), njobs), dim3(256), 0, st, a, KS, (const float*)partial);
+    LAUNCH_CHECK();
+    return TDX_OK;
+}
+template <int BT>
+int launch_head_t(const SkArgs& a, const unsigned char* mask, int begin, float* pm, int* pi, float* ps, int nsl, hipStream_t st) {
+    hipLaunchKernelGGL(wh_head_kernel<BT>, dim3(nsl), dim3(256), 0, st, a, mask, begin, pm, pi, ps, nsl);
+    LAUNCH_CHECK();
+    return TDX_OK;
+}
+int launch_head(const SkArgs& a, const unsigned char* mask, int begin, float* pm, int* pi, float* ps, int nsl, hipStream_t st) {
+    if (a.B <= 1) return launch_head_t<1>(a, mask, begin, pm, pi, ps, nsl, st);
+    if (a.B <= 2) return launch_head_t<2>(a, mask, begin, pm, pi, ps, nsl, st);
+    if (a.B <= 4) return launch_head_t<4>(a, mask, begin, pm, pi, ps, nsl, st);
+    if (a.B <= 8) return launch_head_t<8>(a, mask, begin, pm, pi, ps, nsl, st);
+    if (a.B <= 16) return launch_head_t<16>(a, mask, begin, pm, pi, ps, nsl, st);
+    return launch_head_t<32>(a, mask, begin, pm, pi, ps, nsl, st);
+}
+SkJob sk_job(const float* W, const float* bias, const float* res, float* y, long ld, int brow = 0, int gelu = 0) {
+    return SkJob{W, bias, res, y, ld, brow, gelu};
+}
+
+}  // namespace
+
+struct tdx_whisper {
+    int device = 0;
+    tdx_whisper_config c{};
+    int MP = 0;                       // mel channels of the conv1 rows (multiple of 32)
+    tdx::DevBuf dev;
+    int* pinned = nullptr;            // the host word the decode loop reads
+    const float *dft, *melw, *c1w, *c1b, *c2w, *c2b, *epos, *eln_g, *eln_b, *tok, *dpos, *dln_g, *dln_b;
+    std::vector<EncLayer> enc;
+    std::vector<DecLayer> dec;
+    ~tdx_whisper() { if (pinned) (void)hipHostFree(pinned); }
+};
+
+namespace {
+
+// workspace layouts (floats)
+struct LogmelWs { size_t pw, total; };
+LogmelWs logmel_ws(const tdx_whisper* h, int B) {
+    const size_t rp = 2 * (size_t)h->c.n_audio_ctx + 3;
+    LogmelWs w;
+    w.pw = al(B * rp * HOP); w.total = w.pw + al(B * rp * PWP);
+    return w;
+}
+struct EncWs { size_t xc, c1, x, xn, q, k, v, ao, hb, total; };
+EncWs enc_ws(const tdx_whisper* h, int B) {
+    const size_t S = h->c.n_audio_ctx, T = 2 * S, d = h->c.d_model, M = B * S;
+    EncWs w; size_t o = 0;
+    w.xc = o; o += al(B * (T + 2) * h->MP);
+    w.c1 = o; o += al(B * (T + 2) * d);
+    w.x = o; o += al(M * d); w.xn = o; o += al(M * d); w.q = o; o += al(M * d); w.k = o; o += al(M * d); w.v = o; o += al(M * d); w.ao = o; o += al(M * d);
+    w.hb = o; o += al(M * (size_t)h->c.enc_ffn);
+    w.total = o;
+    return w;
+}
+struct DecWs { size_t x, xn, skp, q, ao, hb, part, pm, pi, ps, state, prefix, mask, cache, total; int nsl, nch_self, nch_cross; };
+DecWs dec_ws(const tdx_whisper* h, int B) {
+    const size_t d = h->c.d_model, T = h->c.n_text_ctx, H = h->c.dec_heads;
+    DecWs w; size_t o = 0;
+    w.nsl = (h->c.vocab + WH_SLICE - 1) / WH_SLICE;
+    w.nch_self = (h->c.n_text_ctx + WH_KEYS - 1) / WH_KEYS;
+    w.nch_cross = (h->c.n_audio_ctx + WH_KEYS - 1) / WH_KEYS;
+    w.x = o; o += al(B * d); w.xn = o; o += al(B * d);
+    w.skp = o; o += B > 8 ? al((size_t)3 * SKM_MAXKS * WH_MAXB * std::max<size_t>(d, h->c.dec_ffn)) : 0;
+    w.q = o; o += al(B * d); w.ao = o; o += al(B * d); w.hb = o; o += al(B * (size_t)h->c.dec_ffn);
+    w.part = o; o += al(B * H * (size_t)std::max(w.nch_self, w.nch_cross) * (DK + 2));
+    w.pm = o; o += al((size_t)B * w.nsl); w.pi = o; o += al((size_t)B * w.nsl); w.ps = o; o += al((size_t)B * w.nsl);
+    w.state = o; o += al(4 * WH_MAXB);
+    w.prefix = o; o += al(T);
+    w.mask = o; o += al(((size_t)h->c.vocab + 3) / 4);
+    w.cache = o; o += al((size_t)h->c.dec_layers * 2 * B * T * d);
+    w.total = o;
+    return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tdx_whisper_create(const tdx_whisper_config* cfg, const void* blob, size_t blob_bytes, int device, tdx_whisper** out) {
+    if (!cfg || !blob || !out) return tdx::fail(TDX_E_INVALID, "tdx_whisper_create: bad argument");
+    const tdx_whisper_config c = *cfg;
+    if (c.d_model < DK || c.enc_heads < 1 || c.dec_heads < 1 || c.d_model != DK * c.enc_heads || c.d_model != DK * c.dec_heads)
+        return tdx::fail(TDX_E_INVALID, "tdx_whisper_create: d_model / heads must be 64 in the encoder and the decoder");
+    if (!c.gelu) return tdx::fail(TDX_E_INVALID, "tdx_whisper_create: activation_function must be \"gelu\" (exact erf)");
+    if (c.n_mels != 80 && c.n_mels != 128) return tdx::fail(TDX_E_INVALID, "tdx_whisper_create: n_mels must be 80 or 128");
+    if (c.n_audio_ctx < 1 || c.n_audio_ctx > WH_MAXCTX) return tdx::fail(TDX_E_INVALID, "tdx_whisper_create: n_audio_ctx must be in [1, 32768]");
+    if (c.n_text_ctx < 1 || c.n_text_ctx > WH_MAXCTX) return tdx::fail(TDX_E_INVALID, "tdx_whisper_create: n_text_ctx must be in [1, 32768]");
+    if (c.vocab < 2) return tdx::fail(TDX_E_INVALID, "tdx_whisper_create: vocab must be at least 2");
+    if (c.enc_layers < 1 || c.dec_layers < 1) return tdx::fail(TDX_E_INVALID, "tdx_whisper_create: enc_layers and dec_layers must be at least 1");
+    if (c.enc_ffn < 64 || c.enc_ffn % 64 || c.dec_ffn < 64 || c.dec_ffn % 64)
+        return tdx::fail(TDX_E_INVALID, "tdx_whisper_create: enc_ffn and dec_ffn must be positive multiples of 64");
+    tdx::Loader ld;
+    if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_whisper_create: malformed TDXW blob");
+    const int d = c.d_model, MP = up(c.n_mels, 32), dP = up(d, 128);
+    std::unique_ptr<tdx_whisper> h(new tdx_whisper());
+    h->device = device; h->c = c; h->MP = MP;
+
+    // window x DFT basis, rows c (re) and NBINP + c (im); the Slaney mel bank [MELP][PWP]
+    size_t o_dft = ld.room((size_t)2 * NBINP * KFR), o_mel = ld.room((size_t)MELP * PWP);
+    {
+        const double PI = 3.14159265358979323846;
+        for (int b = 0; b < NBIN; ++b)
+            for (int k = 0; k < NFFT; ++k) {
+                const double w = 0.5 - 0.5 * std::cos(2.0 * PI * k / NFFT), a = 2.0 * PI * (double)((long)b * k % NFFT) / NFFT;
+                ld.host[o_dft + (size_t)b * KFR + k] = (float)(w * std::cos(a));
+                ld.host[o_dft + (size_t)(NBINP + b) * KFR + k] = (float)(-w * std::sin(a));
+            }
+        const int nm = c.n_mels;
+        std::vector<double> ff(nm + 2);
+        const double m0 = hz_to_mel(0.0), m1 = hz_to_mel(8000.0);
+        for (int i = 0; i < nm + 2; ++i) ff[i] = mel_to_hz(m0 + (m1 - m0) * i / (nm + 1));
+        for (int j = 0; j < nm; ++j)
+            for (int b = 0; b < NBIN; ++b) {
+                const double f = 8000.0 * b / (NBIN - 1);
+                const double down = (f - ff[j]) / (ff[j + 1] - ff[j]), upw = (ff[j + 2] - f) / (ff[j + 2] - ff[j + 1]);
+                const double v = std::max(0.0, std::min(down, upw)) * (2.0 / (ff[j + 2] - ff[j]));
+                ld.host[o_mel + (size_t)j * PWP + b] = (float)v;
+            }
+    }
+    // conv weights [d][cin][3] -> [dP][3][cin padded]
+    size_t o_c1w = ld.room((size_t)dP * 3 * MP), o_c2w = ld.room((size_t)dP * 3 * d);
+    if (const float* w = ld.get("model.encoder.conv1.weight", {(uint32_t)d, (uint32_t)c.n_mels, 3u}))
+        for (int n = 0; n < d; ++n) for (int ci = 0; ci < c.n_mels; ++ci) for (int t = 0; t < 3; ++t)
+            ld.host[o_c1w + ((size_t)n * 3 + t) * MP + ci] = w[((size_t)n * c.n_mels + ci) * 3 + t];
+    if (const float* w = ld.get("model.encoder.conv2.weight", {(uint32_t)d, (uint32_t)d, 3u}))
+        for (int n = 0; n < d; ++n) for (int ci = 0; ci < d; ++ci) for (int t = 0; t < 3; ++t)
+            ld.host[o_c2w + ((size_t)n * 3 + t) * d + ci] = w[((size_t)n * d + ci) * 3 + t];
+    const size_t o_c1b = ld.push(ld.get("model.encoder.conv1.bias", d), d), o_c2b = ld.push(ld.get("model.encoder.conv2.bias", d), d);
+    const size_t o_epos = ld.push(ld.get("model.encoder.embed_positions.weight", {(uint32_t)c.n_audio_ctx, (uint32_t)d}), (size_t)c.n_audio_ctx * d);
+    std::vector<LayerOff> eo(c.enc_layers), dofs(c.dec_layers);
+    for (int l = 0; l < c.enc_layers; ++l) {
+        const std::string p = "model.encoder.layers." + std::to_string(l) + ".";
+        stage_attn(ld, p + "self_attn", p + "self_attn_layer_norm", d, eo[l].sa);
+        stage_ffn(ld, p, d, c.enc_ffn, eo[l]);
+    }
+    const size_t o_elg = ld.push(ld.get("model.encoder.layer_norm.weight", d), d), o_elb = ld.push(ld.get("model.encoder.layer_norm.bias", d), d);
+    const float* tokp = ld.get("model.decoder.embed_tokens.weight", {(uint32_t)c.vocab, (uint32_t)d});
+    const size_t o_tok = ld.push(tokp, (size_t)c.vocab * d);
+    const size_t o_dpos = ld.push(ld.get("model.decoder.embed_positions.weight", {(uint32_t)c.n_text_ctx, (uint32_t)d}), (size_t)c.n_text_ctx * d);
+    for (int l = 0; l < c.dec_layers; ++l) {
+        const std::string p = "model.decoder.layers." + std::to_string(l) + ".";
+        stage_attn(ld, p + "self_attn", p + "self_attn_layer_norm", d, dofs[l].sa);
+        stage_attn(ld, p + "encoder_attn", p + "encoder_attn_layer_norm", d, dofs[l].ca);
+        stage_ffn(ld, p, d, c.dec_ffn, dofs[l]);
+    }
+    const size_t o_dlg = ld.push(ld.get("model.decoder.layer_norm.weight", d), d), o_dlb = ld.push(ld.get("model.decoder.layer_norm.bias", d), d);
+    if (const float* po = ld.get_optional("proj_out.weight", (size_t)c.vocab * d))
+        if (tokp && memcmp(po, tokp, (size_t)c.vocab * d * sizeof(float)) != 0)
+            return tdx::fail(TDX_E_BLOB, "tdx_whisper_create: proj_out.weight differs from model.decoder.embed_tokens.weight (the head is tied)");
+    TRY(ld.finish("tdx_whisper_create", true, device, h->dev));
+    const float* dev = h->dev;
+    h->dft = dev + o_dft; h->melw = dev + o_mel; h->c1w = dev + o_c1w; h->c2w = dev + o_c2w; h->c1b = dev + o_c1b; h->c2b = dev + o_c2b;
+    h->epos = dev + o_epos; h->eln_g = dev + o_elg; h->eln_b = dev + o_elb; h->tok = dev + o_tok; h->dpos = dev + o_dpos;
+    h->dln_g = dev + o_dlg; h->dln_b = dev + o_dlb;
+    h->enc.resize(c.enc_layers); h->dec.resize(c.dec_layers);
+    for (int l = 0; l < c.enc_layers; ++l)
+        h->enc[l] = EncLayer{bind_attn(dev, eo[l].sa), dev + eo[l].g, dev + eo[l].b, dev + eo[l].W1, dev + eo[l].b1, dev + eo[l].W2, dev + eo[l].b2};
+    for (int l = 0; l < c.dec_layers; ++l)
+        h->dec[l] = DecLayer{bind_attn(dev, dofs[l].sa), bind_attn(dev, dofs[l].ca), dev + dofs[l].g, dev + dofs[l].b, dev + dofs[l].W1, dev + dofs[l].b1,
+                             dev + dofs[l].W2, dev + dofs[l].b2};
+    {
+        tdx::DeviceGuard guard(device);
+        if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
+        const hipError_t rc = hipHostMalloc((void**)&h->pinned, 64, hipHostMallocDefault);
+        if (rc != hipSuccess) { h->pinned = nullptr; return tdx::fail_hip(rc, __FILE__, __LINE__); }
+    }
+    *out = h.release();
+    return TDX_OK;
+}
+
+int tdx_whisper_destroy(tdx_whisper* h) {
+    delete h;
+    return TDX_OK;
+}
+
+size_t tdx_whisper_workspace_bytes(const tdx_whisper* h, int B) {
+    if (!h || B < 1 || B > WH_MAXB) return 0;
+    return std::max(std::max(logmel_ws(h, B).total, enc_ws(h, B).total), dec_ws(h, B).total) * sizeof(float);
+}
+
+double tdx_whisper_flops(const tdx_whisper* h, int B, int steps) {
+    if (!h || B < 1 || steps < 0) return 0.0;
+    const double d = h->c.d_model, S = h->c.n_audio_ctx, M = B * S;
+    const double enc = 2.0 * B * 2.0 * S * 3.0 * h->c.n_mels * d + 2.0 * M * 3.0 * d * d
+                     + h->c.enc_layers * (2.0 * M * (4.0 * d * d + 2.0 * d * h->c.enc_ffn) + 4.0 * B * S * S * d)
+                     + h->c.dec_layers * 2.0 * M * 2.0 * d * d;
+    const double step = h->c.dec_layers * (2.0 * B * (8.0 * d * d + 2.0 * d * h->c.dec_ffn) + 4.0 * B * S * d) + 2.0 * B * d * (double)h->c.vocab;
+    return enc + steps * step;
+}
+
+int tdx_whisper_logmel(tdx_whisper* h, const float* wav_dev, const int* lens_dev, int B, long N, float* feat_dev, void* ws_, size_t ws_bytes, void* stream) {
+    if (!h || !wav_dev || !feat_dev || !ws_ || B < 1 || B > WH_MAXB || N < 1) return tdx::fail(TDX_E_INVALID, "tdx_whisper_logmel: bad argument (1 <= B <= 32, N >= 1)");
+    if (ws_bytes < tdx_whisper_workspace_bytes(h, B)) return tdx::fail(TDX_E_WORKSPACE, "tdx_whisper_logmel: workspace too small");
+    tdx::DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
+    hipStream_t st = (hipStream_t)stream;
+    const int T = 2 * h->c.n_audio_ctx, rp = T + 3, pitch = rp * HOP, P = T * HOP;
+    const LogmelWs w = logmel_ws(h, B);
+    float* pad = (float*)ws_; float* pw = (float*)ws_ + w.pw;
+    hipLaunchKernelGGL(wh_pad_kernel, dim3((pitch + 255) / 256, B), dim3(256), 0, st, wav_dev, lens_dev, N, P, pitch, pad);
+    LAUNCH_CHECK();
+    // the last row computed is B rp - 3: it ends 64 floats before the end of `pad`; the last frame kept is B rp - 4
+    const int M = B * rp - 2;
+    TRY((linear_f32<true>(pad, HOP, h->dft, M, NBINP, KFR, EpiPow{pw}, st, 0, NBINP)));
+    TRY(linear_f32(pw, PWP, h->melw, M, MELP, PWP, EpiLogMelT{feat_dev, rp, T, h->c.n_mels}, st));
+    hipLaunchKernelGGL(wh_clamp_kernel, dim3(B), dim3(1024), 0, st, feat_dev, (long)h->c.n_mels * T);
+    LAUNCH_CHECK();
+    return TDX_OK;
+}
+
+int tdx_whisper_encode(tdx_whisper* h, const float* feat_dev, int B, float* enc_dev, float* enc_state_dev, void* ws_, size_t ws_bytes, void* stream) {
+    if (!h || !feat_dev || !ws_ || (!enc_dev && !enc_state_dev) || B < 1 || B > WH_MAXB) return tdx::fail(TDX_E_INVALID, "tdx_whisper_encode: bad argument (1 <= B <= 32)");
+    if (ws_bytes < tdx_whisper_workspace_bytes(h, B)) return tdx::fail(TDX_E_WORKSPACE, "tdx_whisper_encode: workspace too small");
+    tdx::DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
+    hipStream_t st = (hipStream_t)stream;
+    const tdx_whisper_config& c = h->c;
+    const int S = c.n_audio_ctx, T = 2 * S, d = c.d_model, dP = up(d, 128), MP = h->MP, H = c.enc_heads, ffn = c.enc_ffn;
+    const long M = (long)B * S;
+    const EncWs w = enc_ws(h, B);
+    float* f = (float*)ws_;
+    float *xc = f + w.xc, *c1 = f + w.c1, *x = f + w.x, *xn = f + w.xn, *q = f + w.q, *k = f + w.k, *v = f + w.v, *ao = f + w.ao, *hb = f + w.hb;
+    hipLaunchKernelGGL(wh_chlast_kernel, dim3(T + 2, B), dim3(MP), 0, st, feat_dev, c.n_mels, T, MP, xc);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(wh_zero_edge_kernel, dim3(2, B), dim3(256), 0, st, c1, T, d);
+    LAUNCH_CHECK();
+    // overlapping rows: the last row computed is the last one kept, nothing is read past a buffer's end
+    TRY(linear_f32(xc, MP, h->c1w, B * (T + 2) - 2, dP, 3 * MP, EpiConv1{h->c1b, c1, T, d}, st));
+    TRY(linear_f32(c1, 2L * d, h->c2w, B * (S + 1) - 1, dP, 3 * d, EpiConv2{h->c2b, h->epos, x, S, d}, st));
+    const dim3 lng((unsigned)((M + 3) / 4));
+    for (int l = 0; l < c.enc_layers; ++l) {
+        const EncLayer& L = h->enc[l];
+        hipLaunchKernelGGL(wh_ln_rows_kernel, lng, dim3(256), 0, st, x, L.sa.ln_g, L.sa.ln_b, xn, M, d);
+        LAUNCH_CHECK();
+        TRY(linear_f32(xn, d, L.sa.Wq, (int)M, dP, d, EpiBiasActN<>{L.sa.bq, q, d, d}, st));
+        TRY(linear_f32(xn, d, L.sa.Wk, (int)M, dP, d, EpiBiasActN<>{nullptr, k, d, d}, st));
+        TRY(linear_f32(xn, d, L.sa.Wv, (int)M, dP, d, EpiBiasActN<>{L.sa.bv, v, d, d}, st));
+        hipLaunchKernelGGL(wh_enc_attn_kernel, dim3((S + 63) / 64, H, B), dim3(256), 0, st, q, k, v, ao, S, d);
+        LAUNCH_CHECK();
+        TRY(linear_f32(ao, d, L.sa.Wo, (int)M, dP, d, EpiBiasResN<>{L.sa.bo, x, x, d, d}, st));
+        hipLaunchKernelGGL(wh_ln_rows_kernel, lng, dim3(256), 0, st, x, L.ln2_g, L.ln2_b, xn, M, d);
+        LAUNCH_CHECK();
+        TRY(linear_f32(xn, d, L.W1, (int)M, up(ffn, 128), d, EpiBiasActN<ActGelu>{L.b1, hb, ffn, ffn}, st));
+        TRY(linear_f32(hb, ffn, L.W2, (int)M, dP, ffn, EpiBiasResN<>{L.b2, x, x, d, d}, st));
+    }
+    float* e = enc_dev ? enc_dev : xn;
+    hipLaunchKernelGGL(wh_ln_rows_kernel, lng, dim3(256), 0, st, x, h->eln_g, h->eln_b, e, M, d);
+    LAUNCH_CHECK();
+    if (enc_state_dev)
+        for (int l = 0; l < c.dec_layers; ++l) {
+            const AttnW& A = h->dec[l].ca;
+            float* Kc = enc_state_dev + (size_t)(2 * l) * M * d;
+            float* Vc = enc_state_dev + (size_t)(2 * l + 1) * M * d;
+            TRY(linear_f32(e, d, A.Wk, (int)M, dP, d, EpiBiasActN<>{nullptr, Kc, d, d}, st));
+            TRY(linear_f32(e, d, A.Wv, (int)M, dP, d, EpiBiasActN<>{A.bv, Vc, d, d}, st));
+        }
+    return TDX_OK;
+}
+
+int tdx_whisper_decode(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int prefix_len, const int* suppress_host, int n_suppress,
+                       const int* begin_suppress_host, int n_begin, int eos, int max_new, int* step_ids_dev, float* step_scores_dev, int* counts_dev,
+                       void* ws_, size_t ws_bytes, void* stream) {
+    if (!h || !enc_state_dev || !prefix_host || !step_ids_dev || !step_scores_dev || !counts_dev || !ws_ || B < 1 || B > WH_MAXB || prefix_len < 1 ||
+        n_suppress < 0 || n_begin < 0 || (n_suppress > 0 && !suppress_host) || (n_begin > 0 && !begin_suppress_host) || max_new < 0)
+        return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: bad argument (1 <= B <= 32, prefix_len >= 1, max_new >= 0)");
+    const tdx_whisper_config& c = h->c;
+    const int V = c.vocab, T = c.n_text_ctx, d = c.d_model, H = c.dec_heads, S = c.n_audio_ctx, ffn = c.dec_ffn, Ld = c.dec_layers;
+    if (prefix_len > T) return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: the prefix is longer than n_text_ctx");
+    if (eos < 0 || eos >= V) return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: eos outside the vocabulary");
+    for (int i = 0; i < prefix_len; ++i)
+        if (prefix_host[i] < 0 || prefix_host[i] >= V) return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: prefix id outside the vocabulary");
+    std::vector<unsigned char> mask(((size_t)V + 3) / 4 * 4, 0);
+    for (int i = 0; i < n_suppress; ++i) {
+        if (suppress_host[i] < 0 || suppress_host[i] >= V) return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: suppressed id outside the vocabulary");
+        mask[suppress_host[i]] |= 1;
+    }
+    for (int i = 0; i < n_begin; ++i) {
+        if (begin_suppress_host[i] < 0 || begin_suppress_host[i] >= V) return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: begin-suppressed id outside the vocabulary");
+        mask[begin_suppress_host[i]] |= 2;
+    }
+    if (ws_bytes < tdx_whisper_workspace_bytes(h, B)) return tdx::fail(TDX_E_WORKSPACE, "tdx_whisper_decode: workspace too small");
+    tdx::DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
+    hipStream_t st = (hipStream_t)stream;
+    // steps p = 0 .. p_end - 1 read the token at position p and write cache row p (< T); the tokens at positions prefix_len ..
+    // gen_to are generated by the steps prefix_len - 1 .. gen_to - 1.  With nothing to generate the prefix is still scored whole.
+    const int new_eff = std::min(max_new, T - prefix_len);
+    const int gen_to = prefix_len - 1 + new_eff;
+    const int p_end = std::max(prefix_len, gen_to);
+    const DecWs w = dec_ws(h, B);
+    float* f = (float*)ws_;
+    float *x = f + w.x, *xn = f + w.xn, *skp = f + w.skp, *q = f + w.q, *ao = f + w.ao, *hb = f + w.hb, *part = f + w.part, *pm = f + w.pm, *ps = f + w.ps, *cache = f + w.cache;
+    int* pi = (int*)(f + w.pi);
+    int* sti = (int*)(f + w.state);
+    int* prefix_dev = (int*)(f + w.prefix);
+    unsigned char* mask_dev = (unsigned char*)(f + w.mask);
+    const WhState s{sti, sti + WH_MAXB, sti + 2 * WH_MAXB, sti + 3 * WH_MAXB, prefix_dev};
+    hipError_t rc = hipMemcpyAsync(prefix_dev, prefix_host, sizeof(int) * prefix_len, hipMemcpyHostToDevice, st);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(mask_dev, mask.data(), mask.size(), hipMemcpyHostToDevice, st);
+    if (rc != hipSuccess) return tdx::fail_hip(rc, __FILE__, __LINE__);
+    hipLaunchKernelGGL(wh_init_kernel, dim3(1), dim3(64), 0, st, s, B, counts_dev);
+    LAUNCH_CHECK();
+    const size_t lay = (size_t)B * T * d;                       // one layer's K (or V) cache
+    const size_t clay = (size_t)B * S * d;                      // one layer's cross K (or V)
+    auto sk = [&](const float* xin, const float* g, const float* be, int N, int K) {
+        SkArgs a{};
+        a.x = xin; a.lng = g; a.lnb = be; a.pos = s.pos; a.B = B; a.N = N; a.K = K;
+        return a;
+    };
+    int status = TDX_OK;
+    auto step = [&](int p) -> int {
+        hipLaunchKernelGGL(wh_embed_kernel, dim3(B), dim3(256), 0, st, h->tok, h->dpos, s.cur, s.pos, x, d);
+        LAUNCH_CHECK();
+        for (int l = 0; l < Ld; ++l) {
+            const DecLayer& L = h->dec[l];
+            float* Kc = cache + (size_t)(2 * l) * lay;
+            float* Vc = cache + (size_t)(2 * l + 1) * lay;
+            SkArgs a = sk(x, L.sa.ln_g, L.sa.ln_b, d, d);
+            a.job[0] = sk_job(L.sa.Wq, L.sa.bq, nullptr, q, d);
+            a.job[1] = sk_job(L.sa.Wk, nullptr, nullptr, Kc, d, T);
+            a.job[2] = sk_job(L.sa.Wv, L.sa.bv, nullptr, Vc, d, T);
+            TRY(launch_skinny(a, 3, xn, skp, st));
+            hipLaunchKernelGGL(wh_attn_part_kernel, dim3(w.nch_self, H, B), dim3(256), 0, st, q, Kc, Vc, (long)T * d, d, s.pos, 0, part);
+            LAUNCH_CHECK();
+            hipLaunchKernelGGL(wh_attn_comb_kernel, dim3(H, B), dim3(64), 0, st, part, w.nch_self, ao, d);
+            LAUNCH_CHECK();
+            a = sk(ao, nullptr, nullptr, d, d);
+            a.job[0] = sk_job(L.sa.Wo, L.sa.bo, x, x, d);
+            TRY(launch_skinny(a, 1, xn, skp, st));
+            a = sk(x, L.ca.ln_g, L.ca.ln_b, d, d);
+            a.job[0] = sk_job(L.ca.Wq, L.ca.bq, nullptr, q, d);
+            TRY(launch_skinny(a, 1, xn, skp, st));
+            hipLaunchKernelGGL(wh_attn_part_kernel, dim3(w.nch_cross, H, B), dim3(256), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay,
+                               enc_state_dev + (size_t)(2 * l + 1) * clay, (long)S * d, d, (const int*)nullptr, S, part);
+            LAUNCH_CHECK();
+            hipLaunchKernelGGL(wh_attn_comb_kernel, dim3(H, B), dim3(64), 0, st, part, w.nch_cross, ao, d);
+            LAUNCH_CHECK();
+            a = sk(ao, nullptr, nullptr, d, d);
+            a.job[0] = sk_job(L.ca.Wo, L.ca.bo, x, x, d);
+            TRY(launch_skinny(a, 1, xn, skp, st));
+            a = sk(x, L.ln3_g, L.ln3_b, ffn, d);
+            a.job[0] = sk_job(L.W1, L.b1, nullptr, hb, ffn, 0, 1);
+            TRY(launch_skinny(a, 1, xn, skp, st));
+            a = sk(hb, nullptr, nullptr, d, ffn);
+            a.job[0] = sk_job(L.W2, L.b2, x, x, d);
+            TRY(launch_skinny(a, 1, xn, skp, st));
+        }
+        SkArgs a = sk(x, h->dln_g, h->dln_b, V, d);
+        a.job[0] = sk_job(h->tok, nullptr, nullptr, nullptr, 0);
+        TRY(launch_head(a, mask_dev, p == prefix_len - 1, pm, pi, ps, w.nsl, st));
+        hipLaunchKernelGGL(wh_next_kernel, dim3(1), dim3(32 * B), 0, st, pm, pi, ps, w.nsl, s, B, T, prefix_len, gen_to, eos, step_ids_dev, step_scores_dev,
+                           counts_dev);
+        LAUNCH_CHECK();
+        return TDX_OK;
+    };
+    for (int p = 0; p < p_end && status == TDX_OK;) {
+        const int n = std::min(WH_CHUNK, p_end - p);
+        for (int i = 0; i < n && status == TDX_OK; ++i) status = step(p + i);
+        p += n;
+        // one host read per chunk: the number of finished clips (also what keeps `mask` alive until its copy has run)
+        rc = hipMemcpyAsync(h->pinned, s.ndone, sizeof(int), hipMemcpyDeviceToHost, st);
+        if (rc == hipSuccess) rc = hipStreamSynchronize(st);
+        if (rc != hipSuccess) return tdx::fail_hip(rc, __FILE__, __LINE__);
+        if (*h->pinned >= B) break;
+    }
+    return status;
+}
+
+}  // extern "C"

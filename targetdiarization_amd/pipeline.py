@@ -64,7 +64,8 @@ class HotPath:
                  asr_rows_per_launch: int = 32768, mdx_model=None, mdx_weights_file: str = "mdx/weights/UVR-MDX-NET-Inst_HQ_3.onnx",
                  mdx_state_dict=None, mdx_args=None, restorer_state_dict=None, restorer_weights_folder: str | None = None,
                  sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None, sensevoice_model_dir=None,
-                 sensevoice_token_file=None):
+                 sensevoice_token_file=None, whisper_state_dict=None, whisper_config=None, whisper_model_dir=None, whisper_token_list=None,
+                 whisper_tokenizer=None, whisper_generation_config=None):
         from .audio_processor import AudioProcessor
         self.device = torch.device(f"cuda:{cuda_device}")
         self.ap = AudioProcessor(is_separate_audio=True, separater_state_dict=sep_state_dict, cuda_device=cuda_device, verbose_log=False,
@@ -90,6 +91,10 @@ class HotPath:
         # SenseVoiceSmall (sensevoice.py, tdx_sv_*): the recogniser of asr_engine="sensevoice"; None without weights
         from .sensevoice import build_sensevoice
         self.sv = build_sensevoice(sensevoice_state_dict, sensevoice_token_list, sensevoice_cmvn, sensevoice_model_dir, sensevoice_token_file, cuda_device)
+        # Whisper (whisper.py, tdx_whisper_*): the recogniser of asr_engine="whisper_finetune"; None without weights
+        from .whisper import build_whisper
+        self.whisper = build_whisper(whisper_state_dict, whisper_config, whisper_model_dir, whisper_token_list, whisper_tokenizer,
+                                     whisper_generation_config, cuda_device)
         self.asr_segment = asr_segment
         self.windows_per_launch = windows_per_launch
         self.asr_rows_per_launch = asr_rows_per_launch
@@ -208,6 +213,24 @@ class HotPath:
         self.sv.rows_per_launch = self.asr_rows_per_launch
         res = [[] for _ in streams]
         for si, r in zip(owner, self.sv.generate(segs, language=language, use_itn=use_itn) if segs else []):
+            res[si].append(r)
+        return res
+
+    def recognise_whisper(self, streams, language: str = "chinese", prompt_ids=None):
+        """H3 with Whisper: the streams cut into the same <= 30 s segments, 32 segments per launch sequence -> per stream the list of
+        its segments' {"text", "token_ids", "scores"}"""
+        if self.whisper is None:
+            from ._lib import TdxError
+            raise TdxError("recognise_whisper needs the Whisper weights (whisper_state_dict / whisper_model_dir)")
+        streams = [self._dev(s) for s in streams]
+        segs, owner = [], []
+        for si, s in enumerate(streams):
+            for a in range(0, int(s.shape[0]), self.asr_segment):
+                seg = s[a:a + self.asr_segment]
+                if seg.shape[0] >= 400:
+                    segs.append(seg); owner.append(si)
+        res = [[] for _ in streams]
+        for si, r in zip(owner, self.whisper.generate(segs, language=language, prompt_ids=prompt_ids) if segs else []):
             res[si].append(r)
         return res
 

@@ -19,6 +19,8 @@ order of its steps, with two differences that are the point of the rewrite:
       punctuation(text)  -> text                                          (CT-Transformer, ASRProcessor.py:880-897)
     `asr_engine="sensevoice"` with `sensevoice_state_dict` (+ `sensevoice_token_list`, `sensevoice_cmvn`) or a `sensevoice_model_dir` holding
     funasr's model.pt and am.mvn (+ `sensevoice_token_file`) runs H3 through the device SenseVoiceSmall (sensevoice.py, csrc/sensevoice.hip).
+    `asr_engine="whisper_finetune"` with `whisper_state_dict` + `whisper_config` (+ `whisper_token_list`, `whisper_tokenizer`,
+    `whisper_generation_config`) or a transformers `whisper_model_dir` runs H3 through the device Whisper (whisper.py, csrc/whisper.hip).
     `sd_state_dict` (CAM++ weights, 3D-Speaker names) or a `diarization_pipeline_dir` holding campplus_cn_common.bin puts the
     device diarizer (diarization.CamppDiarizer, csrc/campplus.hip) behind sd_pipeline.
     Defaults: one segment per utterance / no overlap detector / whole clip is speech / the device decoder / text unchanged.
@@ -59,7 +61,8 @@ class TargetDiarization:
                  punc_state_dict=None, punc_vocab=None, restorer_state_dict=None, sd_state_dict=None, vad_state_dict=None, vad_cmvn=None,
                  od_state_dict=None, od_embed: Optional[Callable] = None, od_embed_state_dict=None, od_embed_model_dir=None,
                  sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None, sensevoice_model_dir=None,
-                 sensevoice_token_file=None, **kwargs):
+                 sensevoice_token_file=None, whisper_state_dict=None, whisper_config=None, whisper_model_dir=None, whisper_token_list=None,
+                 whisper_tokenizer=None, whisper_generation_config=None, **kwargs):
         self.target_similarity_threshold = target_similarity_threshold
         self.asr_engine = asr_engine
         self.cuda_device = cuda_device
@@ -91,7 +94,9 @@ class TargetDiarization:
                           mdx_weights_file=mdx_weights_file, mdx_state_dict=mdx_state_dict, mdx_args=mdx_args,
                           restorer_state_dict=restorer_state_dict, restorer_weights_folder=restorer_weights_folder,
                           sensevoice_state_dict=sensevoice_state_dict, sensevoice_token_list=sensevoice_token_list, sensevoice_cmvn=sensevoice_cmvn,
-                          sensevoice_model_dir=sensevoice_model_dir, sensevoice_token_file=sensevoice_token_file)
+                          sensevoice_model_dir=sensevoice_model_dir, sensevoice_token_file=sensevoice_token_file,
+                          whisper_state_dict=whisper_state_dict, whisper_config=whisper_config, whisper_model_dir=whisper_model_dir,
+                          whisper_token_list=whisper_token_list, whisper_tokenizer=whisper_tokenizer, whisper_generation_config=whisper_generation_config)
         if od_pipeline is None:               # pyannote's overlap-aware diarization on the device (overlap.py, tdx_pyannet_*); neither source: none
             from .overlap import build_od_pipeline
             embed = od_embed if od_embed is not None else (self.hp.spk.get_speaker_embeddings if self.hp.spk is not None else None)
@@ -302,9 +307,11 @@ class TargetDiarization:
         encs, dres = [], None
         # asr_engine="sensevoice" with its weights loaded: H3 is SenseVoiceSmall (sensevoice.py); without them the engine falls back to
         # the loaded one, like asr_detection (ASRProcessor.py:390-391)
-        svres = None
+        svres = whres = None
         if str(self.asr_engine).lower() == "sensevoice" and getattr(self.hp, "sv", None) is not None:
             svres = self.hp.recognise_sensevoice(lines) if lines else []
+        elif str(self.asr_engine).lower() == "whisper_finetune" and getattr(self.hp, "whisper", None) is not None:
+            whres = self.hp.recognise_whisper(lines) if lines else []
         elif self.hp.asr is not None and lines:
             if self.decoder is None and self.hp.dec is not None:       # the device CIF + NAR decoder (N2)
                 encs, dres = self.hp.encode_device(lines, decode=True)
@@ -325,6 +332,12 @@ class TargetDiarization:
                 parsed = [parse_tagged_text(seg["text"]) for seg in svres[k]]
                 k += 1
                 text, extra = "".join(t for _, _, t in parsed), {"language": next((l for l, _, _ in parsed if l), "")}
+            elif whres is not None:
+                # Whisper without timestamps: one item per speaker too (:787-797); the segments' texts joined, the language detected
+                # from the text as asr_detection does (:509-513)
+                text = "".join(seg["text"] for seg in whres[k]).strip()
+                k += 1
+                extra = {"language": ASRProcessor.detect_language(text)}
             else:
                 recognised = self.hp.asr is not None and (dres is not None or self.decoder is not None)
                 if not recognised:                       # no recogniser loaded (asr_detection prints and returns nothing): the chunks keep empty texts

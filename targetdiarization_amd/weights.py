@@ -916,3 +916,112 @@ def recipe_wespeaker_state_dict(seed: int = 0) -> "OrderedDict[str, torch.Tensor
             t = u * float(np.sqrt(3.0 / fan_in))
         out[name] = t.to(torch.float32).contiguous()
     return out
+
+
+WHISPER_CONFIG_KEYS = ("n_mels", "n_audio_ctx", "d_model", "enc_heads", "enc_layers", "enc_ffn", "n_text_ctx", "dec_heads", "dec_layers",
+                       "dec_ffn", "vocab", "activation")
+
+
+def whisper_config(cfg=None, **kw) -> dict:
+    """The Whisper sizes as one dict (WHISPER_CONFIG_KEYS).  Accepts that dict, keyword arguments, transformers' config.json
+    dict or a WhisperConfig object (num_mel_bins, max_source_positions, encoder_attention_heads, ...); the FFN widths default
+    to 4 d_model, the context sizes to 1500 / 448, the activation to "gelu"."""
+    if cfg is not None and not isinstance(cfg, dict):
+        cfg = cfg.to_dict()
+    c = dict(cfg or {})
+    c.update(kw)
+    if "num_mel_bins" in c or "vocab_size" in c:
+        c = {"n_mels": c.get("num_mel_bins", 80), "n_audio_ctx": c.get("max_source_positions", 1500), "d_model": c["d_model"],
+             "enc_heads": c["encoder_attention_heads"], "enc_layers": c["encoder_layers"], "enc_ffn": c.get("encoder_ffn_dim", 4 * c["d_model"]),
+             "n_text_ctx": c.get("max_target_positions", 448), "dec_heads": c["decoder_attention_heads"], "dec_layers": c["decoder_layers"],
+             "dec_ffn": c.get("decoder_ffn_dim", 4 * c["d_model"]), "vocab": c["vocab_size"], "activation": c.get("activation_function", "gelu")}
+    d = int(c["d_model"])
+    heads = int(c.get("enc_heads", c.get("heads", d // 64)))
+    out = {"n_mels": int(c.get("n_mels", 80)), "n_audio_ctx": int(c.get("n_audio_ctx", 1500)), "d_model": d, "enc_heads": heads,
+           "enc_layers": int(c["enc_layers"]), "enc_ffn": int(c.get("enc_ffn", 4 * d)), "n_text_ctx": int(c.get("n_text_ctx", 448)),
+           "dec_heads": int(c.get("dec_heads", heads)), "dec_layers": int(c["dec_layers"]), "dec_ffn": int(c.get("dec_ffn", 4 * d)),
+           "vocab": int(c["vocab"]), "activation": str(c.get("activation", "gelu"))}
+    return out
+
+
+def whisper_param_shapes(cfg) -> "OrderedDict[str, tuple]":
+    """transformers' WhisperForConditionalGeneration.state_dict() layout (tests/test_whisper_host.py compares it with upstream):
+    k_proj has no bias; proj_out.weight is tied to model.decoder.embed_tokens.weight."""
+    c = whisper_config(cfg)
+    d = c["d_model"]
+    s = OrderedDict()
+
+    def attn(p):
+        s[p + ".k_proj.weight"] = (d, d)
+        s[p + ".v_proj.weight"] = (d, d)
+        s[p + ".v_proj.bias"] = (d,)
+        s[p + ".q_proj.weight"] = (d, d)
+        s[p + ".q_proj.bias"] = (d,)
+        s[p + ".out_proj.weight"] = (d, d)
+        s[p + ".out_proj.bias"] = (d,)
+
+    def norm(p):
+        s[p + ".weight"] = (d,)
+        s[p + ".bias"] = (d,)
+
+    def ffn(p, f):
+        s[p + "fc1.weight"] = (f, d)
+        s[p + "fc1.bias"] = (f,)
+        s[p + "fc2.weight"] = (d, f)
+        s[p + "fc2.bias"] = (d,)
+        norm(p + "final_layer_norm")
+
+    s["model.encoder.conv1.weight"] = (d, c["n_mels"], 3)
+    s["model.encoder.conv1.bias"] = (d,)
+    s["model.encoder.conv2.weight"] = (d, d, 3)
+    s["model.encoder.conv2.bias"] = (d,)
+    s["model.encoder.embed_positions.weight"] = (c["n_audio_ctx"], d)
+    for l in range(c["enc_layers"]):
+        p = f"model.encoder.layers.{l}."
+        attn(p + "self_attn")
+        norm(p + "self_attn_layer_norm")
+        ffn(p, c["enc_ffn"])
+    norm("model.encoder.layer_norm")
+    s["model.decoder.embed_tokens.weight"] = (c["vocab"], d)
+    s["model.decoder.embed_positions.weight"] = (c["n_text_ctx"], d)
+    for l in range(c["dec_layers"]):
+        p = f"model.decoder.layers.{l}."
+        attn(p + "self_attn")
+        norm(p + "self_attn_layer_norm")
+        attn(p + "encoder_attn")
+        norm(p + "encoder_attn_layer_norm")
+        ffn(p, c["dec_ffn"])
+    norm("model.decoder.layer_norm")
+    s["proj_out.weight"] = (c["vocab"], d)
+    return s
+
+
+def recipe_whisper_state_dict(seed: int, cfg) -> "OrderedDict[str, torch.Tensor]":
+    """Deterministic fp32 weights in the Whisper layout.  Matrices and convolution kernels are N(0, 0.02) as transformers
+    initialises them, times 4 (without the factor a random model repeats one token and its top two logits nearly tie: no
+    test of a decoder); biases N(0, 0.1); LayerNorm gains 1 + N(0, 0.1); decoder positions N(0, 0.5); encoder positions the
+    sinusoids transformers stores.  Every tensor has its own generator, keyed by (seed, crc32(name))."""
+    c = whisper_config(cfg)
+    out = OrderedDict()
+    for name, shape in whisper_param_shapes(c).items():
+        if name == "proj_out.weight":
+            out[name] = out["model.decoder.embed_tokens.weight"]
+            continue
+        g = torch.Generator()
+        g.manual_seed(((int(seed) & 0x7FFFFFFF) << 32) | zlib.crc32(name.encode()))
+        n = torch.randn(shape, generator=g, dtype=torch.float32)
+        if name == "model.encoder.embed_positions.weight":
+            length, ch = shape
+            inc = np.log(10000.0) / (ch // 2 - 1)
+            t = torch.arange(length).float()[:, None] * torch.exp(-inc * torch.arange(ch // 2).float())[None, :]
+            v = torch.cat([t.sin(), t.cos()], dim=1)
+        elif name == "model.decoder.embed_positions.weight":
+            v = 0.5 * n
+        elif name.endswith("layer_norm.weight"):
+            v = 1.0 + 0.1 * n
+        elif name.endswith(".bias"):
+            v = 0.1 * n
+        else:
+            v = 0.08 * n
+        out[name] = v.to(torch.float32).contiguous()
+    return out
