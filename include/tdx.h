@@ -522,6 +522,26 @@ int tdx_ctc_collapse(const int* frame_ids_dev, int B, int S, int blank, int* tok
  *      9 rows on: across that line they agree to fp32 rounding).  The [B, vocab] logits are never stored.  Arguments
  *      are validated before the device is touched.  The call enqueues 16 steps at a time and then waits for one pinned word,
  *      the number of finished clips: it returns after the stream has drained and cannot be captured into a graph.
+ *      tdx_whisper_decode_xattn: tdx_whisper_decode plus the cross-attention of the alignment heads (word timestamps).
+ *      heads_host int32 [nh][2]: (decoder layer, head) pairs, 1 <= nh <= 64; xattn_dev float [B][nh][max_rows][n_audio_ctx].
+ *      When step p feeds the token at position p and first_row <= p < first_row + max_rows, row p - first_row of every listed
+ *      head receives that step's softmax probabilities over the n_audio_ctx encoder positions (a full softmax in one workgroup,
+ *      recomputed from q and the layer's cross K: the decode's own attention kernels are not involved).  A clip that has finished
+ *      receives no more rows; rows no step reached are left untouched.  step_ids_dev, step_scores_dev and counts_dev are
+ *      bit-identical to tdx_whisper_decode's on the same inputs.  Rejected before any device call, each with its own message: nh
+ *      outside [1, 64], max_rows < 1, first_row < 0, a NULL heads_host / xattn_dev, a (layer, head) pair outside the decoder.
+ *
+ *      tdx_token_align: token times from those rows, as transformers' _extract_token_timestamps (no model handle; the current
+ *      device).  xattn_dev [B][nh][max_rows][n_audio_ctx]; per clip on the DEVICE nrows_dev[b] (0 .. max_rows, clamped) and
+ *      nframes_dev[b] (1 .. n_audio_ctx, clamped).  Over W[h][i][j], i < nrows, j < nframes: mean and population standard deviation
+ *      over i for each (h, j) (two passes, fp64 sums), z = (W - mean) / std, the median of median_width (odd, 1 .. 31; the product
+ *      passes 7) along j with reflect padding (skipped when nframes <= median_width / 2), the mean over the heads -> M[i][j]
+ *      (matrix_dev, NULL or [B][max_rows][n_audio_ctx]), then dynamic time warping on -M exactly as _dynamic_time_warping: fp32
+ *      cost, cost[i][j] = -M[i-1][j-1] + min as one fp32 addition, strict comparisons with ties going left, upstream's borders,
+ *      the backtrace from the last cell.  frames_dev int32 [B][max_rows]: at [b][i] the frame at which the path first enters
+ *      token row i (upstream's time_indices[jumps]); entries i >= nrows are left untouched.  nrows 0: nothing is written;
+ *      nrows 1: frame 0 (matrix_dev untouched); a column whose std is 0 contributes 0 (upstream: NaN).  1 <= max_rows <= 2048,
+ *      1 <= nh <= 64, 1 <= B <= 65535; every violation has its own message.  One workgroup per clip walks the anti-diagonals.
  * ---------------------------------------------------------------------------------- */
 typedef struct tdx_whisper_config {
     int32_t n_mels, n_audio_ctx, d_model, enc_heads, enc_layers, enc_ffn;
@@ -540,6 +560,13 @@ int tdx_whisper_encode(tdx_whisper* h, const float* feat_dev, int B, float* enc_
 int tdx_whisper_decode(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int prefix_len, const int* suppress_host,
                        int n_suppress, const int* begin_suppress_host, int n_begin, int eos, int max_new, int* step_ids_dev,
                        float* step_scores_dev, int* counts_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int tdx_whisper_decode_xattn(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int prefix_len, const int* suppress_host,
+                             int n_suppress, const int* begin_suppress_host, int n_begin, int eos, int max_new, const int* heads_host, int nh,
+                             int first_row, int max_rows, float* xattn_dev, int* step_ids_dev, float* step_scores_dev, int* counts_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
+size_t tdx_token_align_workspace_bytes(int B, int nh, int max_rows, int n_audio_ctx);
+int tdx_token_align(const float* xattn_dev, int B, int nh, int max_rows, int n_audio_ctx, const int* nrows_dev, const int* nframes_dev,
+                    int median_width, int* frames_dev, float* matrix_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

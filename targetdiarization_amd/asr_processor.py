@@ -21,7 +21,8 @@ class ASRProcessor:
                  *, asr_state_dict=None, decoder: Optional[Callable] = None, punctuation: Optional[Callable] = None, token_list=None,
                  punc_state_dict=None, punc_vocab=None, vad_state_dict=None, vad_cmvn=None,
                  sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None,
-                 whisper_state_dict=None, whisper_config=None, whisper_token_list=None, whisper_tokenizer=None, whisper_generation_config=None):
+                 whisper_state_dict=None, whisper_config=None, whisper_token_list=None, whisper_tokenizer=None, whisper_generation_config=None,
+                 whisper_engine: str = "whisper_finetune", whisper_alignment_heads=None):
         self.is_asr = is_asr
         self.verbose_log = verbose_log
         self.ap = ap
@@ -70,16 +71,27 @@ class ASRProcessor:
         import os
         wdir = asr_model_dir if isinstance(asr_model_dir, str) and "whisper" in asr_model_dir.lower() and "finetune" in asr_model_dir.lower() \
             and os.path.isdir(asr_model_dir) else None
-        if is_asr and (whisper_state_dict is not None or wdir is not None):
+        # ASRProcessor.py:232-243: the engines with word timestamps, from one OpenAI-format file whose name says "whisper" and "v2" / "v3"
+        # (a vocab.json next to it is read when present), or from weights with whisper_engine="whisper_v2" | "whisper_v3"
+        wfile, engine = None, str(whisper_engine).lower()
+        if isinstance(asr_model_dir, str) and "whisper" in asr_model_dir.lower() and os.path.isfile(asr_model_dir):
+            for tag in ("v2", "v3"):
+                if wfile is None and tag in asr_model_dir.lower():
+                    wfile, engine = asr_model_dir, "whisper_" + tag
+        if engine not in ("whisper_finetune", "whisper_v2", "whisper_v3"):
+            print(f"Failed to load Whisper model: whisper_engine {whisper_engine!r} is none of whisper_finetune, whisper_v2, whisper_v3")
+        elif is_asr and (whisper_state_dict is not None or wdir is not None or wfile is not None):
+            label = {"whisper_finetune": "finetune", "whisper_v2": "V2", "whisper_v3": "V3"}[engine]
             try:
                 from .whisper import build_whisper
-                m = build_whisper(whisper_state_dict, whisper_config, wdir, whisper_token_list, whisper_tokenizer, whisper_generation_config, cuda_device)
+                m = build_whisper(whisper_state_dict, whisper_config, wfile if wfile is not None else wdir, whisper_token_list, whisper_tokenizer,
+                                  whisper_generation_config, cuda_device, alignment_heads=whisper_alignment_heads)
                 if m is None:
                     raise FileNotFoundError(f"{wdir!r} holds no config.json with model.safetensors or pytorch_model.bin")
-                self.asr["whisper_finetune"] = m
+                self.asr[engine] = m
                 self.is_asr = True
             except Exception as e:
-                print(f"Failed to load Whisper finetune model: {e}")
+                print(f"Failed to load Whisper {label} model: {e}")
 
     def _nar_decode(self, enc_out):
         """encoder output [T',512] -> {"text", "timestamp"} through the device CIF predictor + NAR decoder"""
@@ -213,6 +225,25 @@ class ASRProcessor:
             if output_raw_result:
                 return res
             result_list = [{"key": r["key"], "language": self.detect_language(r["text"]), "text": r["text"].strip()} for r in res]
+            return join_text_only(result_list) if output_text_only else result_list
+        if asr_engine in ("whisper_v2", "whisper_v3"):   # :443-488
+            from .sensevoice import join_text_only
+            m = self.asr[asr_engine]
+            prompt_ids = None
+            if m.tokenizer is not None:                  # the prompt goes through the tokenizer as for whisper_finetune
+                prompt_ids = m.tokenizer.get_prompt_ids(prompt)
+            elif prompt:
+                print("Whisper: no tokenizer loaded, the prompt is ignored.")
+            clips = [np.asarray(w, dtype=np.float32).reshape(-1)[:480000] for w in wavs]     # one 30 s segment per clip (no long-form loop)
+            auto = language is None or str(language).lower() == "auto"
+            res = m.generate(clips, language=None if auto else str(language).lower(), task="transcribe", prompt_ids=prompt_ids,
+                             keys=[str(k) for k in range(len(clips))], return_timestamps=True)
+            if output_raw_result:
+                return res
+            from .whisper import language_code
+            for r in res:
+                result_list.append({"key": r["key"], "language": r["language"] if auto else language_code(language), "text": r["text"],
+                                    "timestamp": [(str(w), [float(a), float(b)]) for w, (a, b) in r["words"]]})
             return join_text_only(result_list) if output_text_only else result_list
         enc = self.asr["paraformer"]
         for k, w in enumerate(wavs):

@@ -14,6 +14,10 @@
 //             vocabulary head in 64-column slices (max, argmax, sum exp per row and slice, suppression mask applied, logits never
 //             stored) and one combine launch that writes the per-position outputs, the next token, pos + 1 and the done flags.
 //             The host enqueues 16 steps at a time and then reads one pinned word (the number of finished clips).
+//   times     word timestamps: tdx_whisper_decode_xattn is the same loop plus, per layer with a listed alignment head,
+//             one launch that writes the head's softmax row over the encoder positions; tdx_token_align normalises those rows over
+//             the tokens, median-filters along the frames, averages the heads and runs the dynamic time warping of a clip in one
+//             workgroup along the anti-diagonals (transformers' _extract_token_timestamps).
 //
 // Skinny Linear (wh_skinny_kernel): a workgroup owns 4 output columns; its 4 waves split K in interleaved 256-float chunks, a
 // lane keeps B x 4 accumulators (plain fp32 FMA; every weight element is loaded once for all B rows), the 64 lanes meet in a
@@ -40,6 +44,9 @@ constexpr int WH_MAXB = 32, WH_CHUNK = 16;               // clips per decode cal
 constexpr int WH_SLICE = 64;                             // vocabulary columns per head workgroup
 constexpr int WH_KEYS = 256;                             // keys per single-query attention workgroup
 constexpr int WH_MAXCTX = 1 << 15;
+constexpr int WH_XROW_LDS = 4096;                         // scores of that many encoder positions stay in LDS
+constexpr int WH_XROW_NT = 1024;                          // threads of the alignment heads' softmax workgroup
+constexpr int WH_MAXHEADS = 64;                           // alignment heads of a capturing decode
 constexpr float LN_EPS = 1e-5f;
 
 __device__ __forceinline__ float gelu_erf(float v) { return ActGelu::f(v); }
@@ -604,6 +611,182 @@ __global__ __launch_bounds__(64) void wh_attn_comb_kernel(const float* __restric
     out[(long)b * d + h * DK + i] = o / l;
 }
 
+// Cross-attention probabilities of the alignment heads (tdx_whisper_decode_xattn), launched after a listed layer's cross q
+// projection: workgroup (listed head, clip) recomputes the head's S scores from q and the layer's cross K (16 lanes per key, as
+// above), then a full softmax over S: raw scores, the maximum, exponentials and their sum, the quotient; the intermediate values live
+// in LDS up to 4096 positions and in the output row itself beyond.  1024 threads and four key rounds in flight: one workgroup per (head, clip) is a chain of dependent loads, and with 256
+// threads and one round at a time it cost 55 us a launch.  The row is pos[b] - first_row; a finished clip, a head of another layer or a row outside the buffer: nothing is
+// written.  The attention kernels above are not touched, so the decode's own results keep their bits.
+__global__ __launch_bounds__(WH_XROW_NT) void wh_xattn_row_kernel(const float* __restrict__ q, const float* __restrict__ Kc, long clip_stride, int S, int d,
+                                                            int layer, const int* __restrict__ heads, const int* __restrict__ pos,
+                                                            const int* __restrict__ done, int first_row, int max_rows, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float qs[DK];
+    __shared__ float red[WH_XROW_NT / 64];
+    __shared__ float slds[WH_XROW_LDS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int hi = blockIdx.x, b = blockIdx.y, nh = gridDim.x;
+    if (heads[2 * hi] != layer || done[b]) return;                  // (uniform over the workgroup, like the two returns below)
+    const int row = pos[b] - first_row;
+    if (row < 0 || row >= max_rows) return;
+    const int h = heads[2 * hi + 1];
+    float* o = out + (((size_t)b * nh + hi) * max_rows + row) * (size_t)S;
+    float* sc = S <= WH_XROW_LDS ? slds : o;                        // scores and exponentials: LDS when they fit, else the row itself
+    if (tid < DK) qs[tid] = q[(long)b * d + h * DK + tid] * 0.125f;
+    __syncthreads();
+    const float* Kb = Kc + (long)b * clip_stride + h * DK;
+    const int sub = tid & 15, kg = tid >> 4;
+    const f32x4 u = *reinterpret_cast<const f32x4*>(qs + 4 * sub);
+    float mx = -INFINITY;
+    constexpr int KPR = WH_XROW_NT / 16;                            // keys per round
+    for (int j0 = 0; j0 < S; j0 += 4 * KPR) {
+        f32x4 t[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) t[r] = ldg4(Kb + (long)min(j0 + r * KPR + kg, S - 1) * d + 4 * sub);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int jk = j0 + r * KPR + kg;
+            const float dot = h3_row16_sum(fmaf(u[3], t[r][3], fmaf(u[2], t[r][2], fmaf(u[1], t[r][1], u[0] * t[r][0]))));
+            if (sub == 0 && jk < S) { sc[jk] = dot; mx = fmaxf(mx, dot); }
+        }
+    }
+    mx = wave_max(mx);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();                                                // the scores are visible to the workgroup
+    mx = red[0];
+#pragma unroll
+    for (int w = 1; w < WH_XROW_NT / 64; ++w) mx = fmaxf(mx, red[w]);
+    float ls = 0.f;
+    for (int j = tid; j < S; j += WH_XROW_NT) { const float e = expf(sc[j] - mx); sc[j] = e; ls += e; }
+    ls = wave_sum(ls);
+    __syncthreads();                                                // red has been read by all
+    if (lane == 0) red[wave] = ls;
+    __syncthreads();
+    float l = red[0];
+#pragma unroll
+    for (int w = 1; w < WH_XROW_NT / 64; ++w) l += red[w];
+    for (int j = tid; j < S; j += WH_XROW_NT) o[j] = sc[j] / l;            // a thread's own exponentials
+}
+
+// ------------------------------------------------------------------------------------------------ token alignment
+// tdx_token_align (transformers' _extract_token_timestamps on the device).  W [B][nh][max_rows][S]; clip b uses rows < n, frames < m.
+constexpr int AL_MAXROWS = 2048, AL_MAXW = 31, AL_NT = 512;
+__device__ __forceinline__ int al_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// mean and population standard deviation over the token axis of every (clip, head, frame): two passes (mean, then the centred
+// squares), the sums in fp64 (full rate here) so that the mean is the rounded exact one.  grid (ceil(S / 256), nh, B)
+__global__ __launch_bounds__(256) void al_stats_kernel(const float* __restrict__ W, int max_rows, int S, const int* __restrict__ nrows,
+                                                        const int* __restrict__ nframes, float* __restrict__ mean, float* __restrict__ sd) {
+    const int j = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y, b = blockIdx.z, nh = gridDim.y;
+    const int n = al_clamp(nrows[b], 0, max_rows), m = al_clamp(nframes[b], 1, S);
+    if (n < 2 || j >= m) return;
+    const float* w = W + ((size_t)b * nh + h) * max_rows * (size_t)S + j;
+    double s = 0.0;
+    for (int i = 0; i < n; ++i) s += (double)w[(size_t)i * S];
+    const float mu = (float)(s / n);
+    double q = 0.0;
+    for (int i = 0; i < n; ++i) { const float c = w[(size_t)i * S] - mu; q += (double)c * (double)c; }
+    mean[((size_t)b * nh + h) * S + j] = mu;
+    sd[((size_t)b * nh + h) * S + j] = sqrtf((float)(q / n));
+}
+// z = (W - mean) / std (0 where std is 0), the median of `width` along the frames with reflect padding (none when m <= width / 2,
+// as upstream), the mean over the heads.  Thread (frame j, row i = blockIdx.y, clip).  CW: the width at compile time (the window
+// stays in registers) or 0 for any odd width up to AL_MAXW.
+template <int CW>
+__global__ __launch_bounds__(256) void al_filter_kernel(const float* __restrict__ W, int nh, int max_rows, int S, const int* __restrict__ nrows,
+                                                         const int* __restrict__ nframes, int width, const float* __restrict__ mean,
+                                                         const float* __restrict__ sd, float* __restrict__ M) {
+    const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y, b = blockIdx.z;
+    const int n = al_clamp(nrows[b], 0, max_rows), m = al_clamp(nframes[b], 1, S);
+    if (n < 2 || i >= n || j >= m) return;
+    const int w = CW ? CW : width, pad = w / 2;
+    const bool plain = m <= pad || w == 1;
+    float acc = 0.f;
+    for (int h = 0; h < nh; ++h) {
+        const float* wr = W + (((size_t)b * nh + h) * max_rows + i) * (size_t)S;
+        const float* mu = mean + ((size_t)b * nh + h) * S;
+        const float* sg = sd + ((size_t)b * nh + h) * S;
+        if (plain) { acc += sg[j] > 0.f ? (wr[j] - mu[j]) / sg[j] : 0.f; continue; }
+        float v[CW ? CW : AL_MAXW];
+        for (int t = 0; t < w; ++t) {
+            int jj = j + t - pad;
+            if (jj < 0) jj = -jj;
+            if (jj >= m) jj = 2 * (m - 1) - jj;
+            v[t] = sg[jj] > 0.f ? (wr[jj] - mu[jj]) / sg[jj] : 0.f;
+        }
+        for (int a = 0; a <= pad; ++a)                              // selection up to the middle element
+            for (int c = a + 1; c < w; ++c)
+                if (v[c] < v[a]) { const float t = v[a]; v[a] = v[c]; v[c] = t; }
+        acc += v[pad];
+    }
+    M[((size_t)b * max_rows + i) * (size_t)S + j] = acc / (float)nh;
+}
+// Dynamic time warping on -M, one workgroup per clip, as transformers' _dynamic_time_warping: cost[i][j] = -M[i-1][j-1] +
+// min(cost[i-1][j-1], cost[i-1][j], cost[i][j-1]) in fp32, strict comparisons, a tie goes left.  The workgroup walks the
+// anti-diagonals k = i + j; thread t owns the rows t + 1, t + 513, ... (R of them); the last two diagonals live in LDS indexed by
+// i (index 0 and index k are the borders: inf, and 0 at the origin), three buffers in rotation, so one barrier per diagonal
+// separates the writes of diagonal k from the reads of k + 1 and from the writes of k + 1 into the buffer k - 2 was read from.
+// The value of M a thread needs next is loaded a diagonal ahead.  The trace goes out as bytes; thread 0 walks it back from the
+// last cell: the frame of row i is the column at which the path leaves the row going back (upstream's time_indices[jumps]).
+template <int R>
+__global__ __launch_bounds__(AL_NT) void al_dtw_kernel(const float* __restrict__ M, int max_rows, int S, const int* __restrict__ nrows,
+                                                        const int* __restrict__ nframes, unsigned char* __restrict__ trace, int* __restrict__ frames) {
+    __shared__ float dg[3][R * AL_NT + 1];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int n = al_clamp(nrows[b], 0, min(max_rows, R * AL_NT)), m = al_clamp(nframes[b], 1, S);
+    if (n == 0) return;                                             // (uniform)
+    if (n == 1) { if (tid == 0) frames[(size_t)b * max_rows] = 0; return; }
+    const float* Mb = M + (size_t)b * max_rows * (size_t)S;
+    unsigned char* tb = trace + (size_t)b * max_rows * (size_t)S;
+    if (tid == 0) { dg[0][0] = 0.f; dg[1][0] = INFINITY; dg[1][1] = INFINITY; }
+    float nxt[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) nxt[r] = (tid + r * AL_NT == 0) ? Mb[0] : 0.f;      // diagonal 2 is the cell (1, 1)
+    __syncthreads();
+    for (int k = 2; k <= n + m; ++k) {
+        float* cur = dg[k % 3];
+        const float* p1 = dg[(k + 2) % 3];
+        const float* p2 = dg[(k + 1) % 3];
+        const int ilo = max(1, k - m), ihi = min(n, k - 1);
+        const int nlo = max(1, k + 1 - m), nhi = min(n, k);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int i = tid + 1 + r * AL_NT;
+            const float mv = nxt[r];
+            if (i >= nlo && i <= nhi) nxt[r] = Mb[(size_t)(i - 1) * S + (k - i)];       // the cell (i, k + 1 - i)
+            if (i >= ilo && i <= ihi) {
+                const float c0 = p2[i - 1], c1 = p1[i - 1], c2 = p1[i];
+                float c; unsigned char t;
+                if (c0 < c1 && c0 < c2) { c = c0; t = 0; }
+                else if (c1 < c0 && c1 < c2) { c = c1; t = 1; }
+                else { c = c2; t = 2; }
+                cur[i] = -mv + c;
+                tb[(size_t)(i - 1) * S + (k - i - 1)] = t;
+            }
+        }
+        if (tid == 0) { cur[0] = INFINITY; if (k <= n) cur[k] = INFINITY; }
+        __syncthreads();
+    }
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) {
+        int i = n, j = m;
+        while (i > 0) {
+            const int t = j > 0 ? tb[(size_t)(i - 1) * S + (j - 1)] : 1;
+            if (t != 2) frames[(size_t)b * max_rows + i - 1] = max(j - 1, 0);
+            if (t == 0) { --i; --j; } else if (t == 1) --i; else --j;
+        }
+    }
+}
+struct AlignWs { size_t mean, sd, M, trace, total; };
+AlignWs align_ws(size_t B, size_t nh, size_t max_rows, size_t S) {
+    AlignWs w; size_t o = 0;
+    w.mean = o; o += al(B * nh * S); w.sd = o; o += al(B * nh * S);
+    w.M = o; o += al(B * max_rows * S);
+    w.trace = o; o += al((B * max_rows * S + 3) / 4);
+    w.total = o;
+    return w;
+}
+
 struct AttnW { const float *ln_g, *ln_b, *Wq, *bq, *Wk, *Wv, *bv, *Wo, *bo; };
 struct EncLayer { AttnW sa; const float *ln2_g, *ln2_b, *W1, *b1, *W2, *b2; };
 struct DecLayer { AttnW sa, ca; const float *ln3_g, *ln3_b, *W1, *b1, *W2, *b2; };
@@ -709,7 +892,7 @@ EncWs enc_ws(const tdx_whisper* h, int B) {
     w.total = o;
     return w;
 }
-struct DecWs { size_t x, xn, skp, q, ao, hb, part, pm, pi, ps, state, prefix, mask, cache, total; int nsl, nch_self, nch_cross; };
+struct DecWs { size_t x, xn, skp, q, ao, hb, part, pm, pi, ps, state, prefix, mask, heads, cache, total; int nsl, nch_self, nch_cross; };
 DecWs dec_ws(const tdx_whisper* h, int B) {
     const size_t d = h->c.d_model, T = h->c.n_text_ctx, H = h->c.dec_heads;
     DecWs w; size_t o = 0;
@@ -724,6 +907,7 @@ DecWs dec_ws(const tdx_whisper* h, int B) {
     w.state = o; o += al(4 * WH_MAXB);
     w.prefix = o; o += al(T);
     w.mask = o; o += al(((size_t)h->c.vocab + 3) / 4);
+    w.heads = o; o += al(2 * WH_MAXHEADS);
     w.cache = o; o += al((size_t)h->c.dec_layers * 2 * B * T * d);
     w.total = o;
     return w;
@@ -914,28 +1098,45 @@ int tdx_whisper_encode(tdx_whisper* h, const float* feat_dev, int B, float* enc_
     return TDX_OK;
 }
 
-int tdx_whisper_decode(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int prefix_len, const int* suppress_host, int n_suppress,
-                       const int* begin_suppress_host, int n_begin, int eos, int max_new, int* step_ids_dev, float* step_scores_dev, int* counts_dev,
-                       void* ws_, size_t ws_bytes, void* stream) {
+// the capture of tdx_whisper_decode_xattn: (layer, head) pairs, the first position and the rows of the buffer
+struct WhCapture { const int* heads_host; int nh, first_row, max_rows; float* xattn_dev; };
+
+static int whisper_decode_impl(const std::string& fn, const WhCapture* cap, tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host,
+                               int prefix_len, const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int eos, int max_new,
+                               int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_, size_t ws_bytes, void* stream) {
+    if (cap) {
+        if (cap->nh < 1 || cap->nh > WH_MAXHEADS) return tdx::fail(TDX_E_INVALID, fn + ": nh must be in [1, 64]");
+        if (cap->max_rows < 1) return tdx::fail(TDX_E_INVALID, fn + ": max_rows must be at least 1");
+        if (cap->first_row < 0) return tdx::fail(TDX_E_INVALID, fn + ": first_row must not be negative");
+        if (!cap->heads_host || !cap->xattn_dev) return tdx::fail(TDX_E_INVALID, fn + ": heads_host and xattn_dev must not be NULL");
+    }
     if (!h || !enc_state_dev || !prefix_host || !step_ids_dev || !step_scores_dev || !counts_dev || !ws_ || B < 1 || B > WH_MAXB || prefix_len < 1 ||
         n_suppress < 0 || n_begin < 0 || (n_suppress > 0 && !suppress_host) || (n_begin > 0 && !begin_suppress_host) || max_new < 0)
-        return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: bad argument (1 <= B <= 32, prefix_len >= 1, max_new >= 0)");
+        return tdx::fail(TDX_E_INVALID, fn + ": bad argument (1 <= B <= 32, prefix_len >= 1, max_new >= 0)");
     const tdx_whisper_config& c = h->c;
     const int V = c.vocab, T = c.n_text_ctx, d = c.d_model, H = c.dec_heads, S = c.n_audio_ctx, ffn = c.dec_ffn, Ld = c.dec_layers;
-    if (prefix_len > T) return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: the prefix is longer than n_text_ctx");
-    if (eos < 0 || eos >= V) return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: eos outside the vocabulary");
+    if (prefix_len > T) return tdx::fail(TDX_E_INVALID, fn + ": the prefix is longer than n_text_ctx");
+    std::vector<char> listed(Ld, 0);
+    if (cap)
+        for (int i = 0; i < cap->nh; ++i) {
+            const int l = cap->heads_host[2 * i], hd = cap->heads_host[2 * i + 1];
+            if (l < 0 || l >= Ld || hd < 0 || hd >= H)
+                return tdx::fail(TDX_E_INVALID, fn + ": alignment head (" + std::to_string(l) + ", " + std::to_string(hd) + ") outside the decoder's layers / heads");
+            listed[l] = 1;
+        }
+    if (eos < 0 || eos >= V) return tdx::fail(TDX_E_INVALID, fn + ": eos outside the vocabulary");
     for (int i = 0; i < prefix_len; ++i)
-        if (prefix_host[i] < 0 || prefix_host[i] >= V) return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: prefix id outside the vocabulary");
+        if (prefix_host[i] < 0 || prefix_host[i] >= V) return tdx::fail(TDX_E_INVALID, fn + ": prefix id outside the vocabulary");
     std::vector<unsigned char> mask(((size_t)V + 3) / 4 * 4, 0);
     for (int i = 0; i < n_suppress; ++i) {
-        if (suppress_host[i] < 0 || suppress_host[i] >= V) return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: suppressed id outside the vocabulary");
+        if (suppress_host[i] < 0 || suppress_host[i] >= V) return tdx::fail(TDX_E_INVALID, fn + ": suppressed id outside the vocabulary");
         mask[suppress_host[i]] |= 1;
     }
     for (int i = 0; i < n_begin; ++i) {
-        if (begin_suppress_host[i] < 0 || begin_suppress_host[i] >= V) return tdx::fail(TDX_E_INVALID, "tdx_whisper_decode: begin-suppressed id outside the vocabulary");
+        if (begin_suppress_host[i] < 0 || begin_suppress_host[i] >= V) return tdx::fail(TDX_E_INVALID, fn + ": begin-suppressed id outside the vocabulary");
         mask[begin_suppress_host[i]] |= 2;
     }
-    if (ws_bytes < tdx_whisper_workspace_bytes(h, B)) return tdx::fail(TDX_E_WORKSPACE, "tdx_whisper_decode: workspace too small");
+    if (ws_bytes < tdx_whisper_workspace_bytes(h, B)) return tdx::fail(TDX_E_WORKSPACE, fn + ": workspace too small");
     tdx::DeviceGuard guard(h->device);
     if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
     hipStream_t st = (hipStream_t)stream;
@@ -954,6 +1155,8 @@ int tdx_whisper_decode(tdx_whisper* h, const float* enc_state_dev, int B, const 
     const WhState s{sti, sti + WH_MAXB, sti + 2 * WH_MAXB, sti + 3 * WH_MAXB, prefix_dev};
     hipError_t rc = hipMemcpyAsync(prefix_dev, prefix_host, sizeof(int) * prefix_len, hipMemcpyHostToDevice, st);
     if (rc == hipSuccess) rc = hipMemcpyAsync(mask_dev, mask.data(), mask.size(), hipMemcpyHostToDevice, st);
+    int* heads_dev = (int*)(f + w.heads);
+    if (rc == hipSuccess && cap) rc = hipMemcpyAsync(heads_dev, cap->heads_host, sizeof(int) * 2 * cap->nh, hipMemcpyHostToDevice, st);
     if (rc != hipSuccess) return tdx::fail_hip(rc, __FILE__, __LINE__);
     hipLaunchKernelGGL(wh_init_kernel, dim3(1), dim3(64), 0, st, s, B, counts_dev);
     LAUNCH_CHECK();
@@ -987,6 +1190,11 @@ int tdx_whisper_decode(tdx_whisper* h, const float* enc_state_dev, int B, const 
             a = sk(x, L.ca.ln_g, L.ca.ln_b, d, d);
             a.job[0] = sk_job(L.ca.Wq, L.ca.bq, nullptr, q, d);
             TRY(launch_skinny(a, 1, xn, skp, st));
+            if (cap && listed[l]) {
+                hipLaunchKernelGGL(wh_xattn_row_kernel, dim3(cap->nh, B), dim3(WH_XROW_NT), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay, (long)S * d, S, d, l,
+                                   (const int*)heads_dev, (const int*)s.pos, (const int*)s.done, cap->first_row, cap->max_rows, cap->xattn_dev);
+                LAUNCH_CHECK();
+            }
             hipLaunchKernelGGL(wh_attn_part_kernel, dim3(w.nch_cross, H, B), dim3(256), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay,
                                enc_state_dev + (size_t)(2 * l + 1) * clay, (long)S * d, d, (const int*)nullptr, S, part);
             LAUNCH_CHECK();
@@ -1021,6 +1229,63 @@ int tdx_whisper_decode(tdx_whisper* h, const float* enc_state_dev, int B, const 
         if (*h->pinned >= B) break;
     }
     return status;
+}
+
+int tdx_whisper_decode(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int prefix_len, const int* suppress_host, int n_suppress,
+                       const int* begin_suppress_host, int n_begin, int eos, int max_new, int* step_ids_dev, float* step_scores_dev, int* counts_dev,
+                       void* ws_, size_t ws_bytes, void* stream) {
+    return whisper_decode_impl("tdx_whisper_decode", nullptr, h, enc_state_dev, B, prefix_host, prefix_len, suppress_host, n_suppress, begin_suppress_host,
+                               n_begin, eos, max_new, step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
+}
+
+int tdx_whisper_decode_xattn(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int prefix_len, const int* suppress_host,
+                             int n_suppress, const int* begin_suppress_host, int n_begin, int eos, int max_new, const int* heads_host, int nh,
+                             int first_row, int max_rows, float* xattn_dev, int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_,
+                             size_t ws_bytes, void* stream) {
+    const WhCapture cap{heads_host, nh, first_row, max_rows, xattn_dev};
+    return whisper_decode_impl("tdx_whisper_decode_xattn", &cap, h, enc_state_dev, B, prefix_host, prefix_len, suppress_host, n_suppress,
+                               begin_suppress_host, n_begin, eos, max_new, step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
+}
+
+size_t tdx_token_align_workspace_bytes(int B, int nh, int max_rows, int n_audio_ctx) {
+    if (B < 1 || B > 65535 || nh < 1 || nh > WH_MAXHEADS || max_rows < 1 || max_rows > AL_MAXROWS || n_audio_ctx < 1 || n_audio_ctx > WH_MAXCTX) return 0;
+    return align_ws(B, nh, max_rows, n_audio_ctx).total * sizeof(float);
+}
+
+int tdx_token_align(const float* xattn_dev, int B, int nh, int max_rows, int n_audio_ctx, const int* nrows_dev, const int* nframes_dev, int median_width,
+                    int* frames_dev, float* matrix_dev, void* ws_, size_t ws_bytes, void* stream) {
+    if (nh < 1 || nh > WH_MAXHEADS) return tdx::fail(TDX_E_INVALID, "tdx_token_align: nh must be in [1, 64]");
+    if (max_rows < 1 || max_rows > AL_MAXROWS) return tdx::fail(TDX_E_INVALID, "tdx_token_align: max_rows must be in [1, 2048]");
+    if (median_width < 1 || median_width > AL_MAXW || median_width % 2 == 0)
+        return tdx::fail(TDX_E_INVALID, "tdx_token_align: median_width must be odd and in [1, 31]");
+    if (B < 1 || B > 65535 || n_audio_ctx < 1 || n_audio_ctx > WH_MAXCTX)
+        return tdx::fail(TDX_E_INVALID, "tdx_token_align: bad argument (1 <= B <= 65535, 1 <= n_audio_ctx <= 32768)");
+    if (!xattn_dev || !nrows_dev || !nframes_dev || !frames_dev || !ws_) return tdx::fail(TDX_E_INVALID, "tdx_token_align: NULL argument");
+    if (ws_bytes < tdx_token_align_workspace_bytes(B, nh, max_rows, n_audio_ctx)) return tdx::fail(TDX_E_WORKSPACE, "tdx_token_align: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const int S = n_audio_ctx;
+    const AlignWs w = align_ws(B, nh, max_rows, S);
+    float* f = (float*)ws_;
+    float *mean = f + w.mean, *sd = f + w.sd, *M = matrix_dev ? matrix_dev : f + w.M;
+    unsigned char* trace = (unsigned char*)(f + w.trace);
+    const unsigned nb = (unsigned)((S + 255) / 256);
+    hipLaunchKernelGGL(al_stats_kernel, dim3(nb, nh, B), dim3(256), 0, st, xattn_dev, max_rows, S, nrows_dev, nframes_dev, mean, sd);
+    LAUNCH_CHECK();
+    if (median_width == 7)
+        hipLaunchKernelGGL(al_filter_kernel<7>, dim3(nb, max_rows, B), dim3(256), 0, st, xattn_dev, nh, max_rows, S, nrows_dev, nframes_dev, 7, (const float*)mean,
+                           (const float*)sd, M);
+    else
+        hipLaunchKernelGGL(al_filter_kernel<0>, dim3(nb, max_rows, B), dim3(256), 0, st, xattn_dev, nh, max_rows, S, nrows_dev, nframes_dev, median_width,
+                           (const float*)mean, (const float*)sd, M);
+    LAUNCH_CHECK();
+    if (max_rows <= AL_NT)
+        hipLaunchKernelGGL(al_dtw_kernel<1>, dim3(B), dim3(AL_NT), 0, st, (const float*)M, max_rows, S, nrows_dev, nframes_dev, trace, frames_dev);
+    else if (max_rows <= 2 * AL_NT)
+        hipLaunchKernelGGL(al_dtw_kernel<2>, dim3(B), dim3(AL_NT), 0, st, (const float*)M, max_rows, S, nrows_dev, nframes_dev, trace, frames_dev);
+    else
+        hipLaunchKernelGGL(al_dtw_kernel<4>, dim3(B), dim3(AL_NT), 0, st, (const float*)M, max_rows, S, nrows_dev, nframes_dev, trace, frames_dev);
+    LAUNCH_CHECK();
+    return TDX_OK;
 }
 
 }  // extern "C"

@@ -91,7 +91,8 @@ class HotPath:
         # SenseVoiceSmall (sensevoice.py, tdx_sv_*): the recogniser of asr_engine="sensevoice"; None without weights
         from .sensevoice import build_sensevoice
         self.sv = build_sensevoice(sensevoice_state_dict, sensevoice_token_list, sensevoice_cmvn, sensevoice_model_dir, sensevoice_token_file, cuda_device)
-        # Whisper (whisper.py, tdx_whisper_*): the recogniser of asr_engine="whisper_finetune"; None without weights
+        # Whisper (whisper.py, tdx_whisper_*): the recogniser of asr_engine="whisper_finetune" / "whisper_v2" / "whisper_v3" (a
+        # transformers directory or one OpenAI-format .pt file); None without weights
         from .whisper import build_whisper
         self.whisper = build_whisper(whisper_state_dict, whisper_config, whisper_model_dir, whisper_token_list, whisper_tokenizer,
                                      whisper_generation_config, cuda_device)
@@ -216,21 +217,31 @@ class HotPath:
             res[si].append(r)
         return res
 
-    def recognise_whisper(self, streams, language: str = "chinese", prompt_ids=None):
+    def recognise_whisper(self, streams, language: str = "chinese", prompt_ids=None, timestamps: bool = False):
         """H3 with Whisper: the streams cut into the same <= 30 s segments, 32 segments per launch sequence -> per stream the list of
-        its segments' {"text", "token_ids", "scores"}"""
+        its segments' {"text", "token_ids", "scores"}.  timestamps (the whisper_v2 / whisper_v3 engines): every segment also carries
+        "token_times" and "words" [(word, [start_s, end_s]), ...], both on the stream's own clock (the segment's start added), and
+        "offset", that start in seconds"""
         if self.whisper is None:
             from ._lib import TdxError
             raise TdxError("recognise_whisper needs the Whisper weights (whisper_state_dict / whisper_model_dir)")
         streams = [self._dev(s) for s in streams]
-        segs, owner = [], []
+        segs, owner, starts = [], [], []
         for si, s in enumerate(streams):
             for a in range(0, int(s.shape[0]), self.asr_segment):
                 seg = s[a:a + self.asr_segment]
                 if seg.shape[0] >= 400:
-                    segs.append(seg); owner.append(si)
+                    segs.append(seg); owner.append(si); starts.append(a / 16000.0)
         res = [[] for _ in streams]
-        for si, r in zip(owner, self.whisper.generate(segs, language=language, prompt_ids=prompt_ids) if segs else []):
+        if not timestamps:
+            for si, r in zip(owner, self.whisper.generate(segs, language=language, prompt_ids=prompt_ids) if segs else []):
+                res[si].append(r)
+            return res
+        for si, t0, r in zip(owner, starts, self.whisper.generate(segs, language=language, prompt_ids=prompt_ids, return_timestamps=True) if segs else []):
+            r = dict(r)
+            r["offset"] = t0
+            r["token_times"] = [t + t0 for t in r["token_times"]]
+            r["words"] = [(w, [a + t0, b + t0]) for w, (a, b) in r["words"]]
             res[si].append(r)
         return res
 

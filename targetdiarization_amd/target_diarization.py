@@ -21,6 +21,8 @@ order of its steps, with two differences that are the point of the rewrite:
     funasr's model.pt and am.mvn (+ `sensevoice_token_file`) runs H3 through the device SenseVoiceSmall (sensevoice.py, csrc/sensevoice.hip).
     `asr_engine="whisper_finetune"` with `whisper_state_dict` + `whisper_config` (+ `whisper_token_list`, `whisper_tokenizer`,
     `whisper_generation_config`) or a transformers `whisper_model_dir` runs H3 through the device Whisper (whisper.py, csrc/whisper.hip).
+    `asr_engine="whisper_v2"` / `"whisper_v3"` (the same weights, or `whisper_model_dir` = one OpenAI-format .pt file) also asks for word
+    timestamps: the words go to the diarization chunks by their start times, as Paraformer's tokens do.
     `sd_state_dict` (CAM++ weights, 3D-Speaker names) or a `diarization_pipeline_dir` holding campplus_cn_common.bin puts the
     device diarizer (diarization.CamppDiarizer, csrc/campplus.hip) behind sd_pipeline.
     Defaults: one segment per utterance / no overlap detector / whole clip is speech / the device decoder / text unchanged.
@@ -307,11 +309,14 @@ class TargetDiarization:
         encs, dres = [], None
         # asr_engine="sensevoice" with its weights loaded: H3 is SenseVoiceSmall (sensevoice.py); without them the engine falls back to
         # the loaded one, like asr_detection (ASRProcessor.py:390-391)
-        svres = whres = None
+        svres = whres = whtres = None
         if str(self.asr_engine).lower() == "sensevoice" and getattr(self.hp, "sv", None) is not None:
             svres = self.hp.recognise_sensevoice(lines) if lines else []
         elif str(self.asr_engine).lower() == "whisper_finetune" and getattr(self.hp, "whisper", None) is not None:
             whres = self.hp.recognise_whisper(lines) if lines else []
+        elif str(self.asr_engine).lower() in ("whisper_v2", "whisper_v3") and getattr(self.hp, "whisper", None) is not None:
+            # the engines with word timestamps (ASRProcessor.py:443-488): the language is detected per segment (language="auto")
+            whtres = self.hp.recognise_whisper(lines, language="auto", timestamps=True) if lines else []
         elif self.hp.asr is not None and lines:
             if self.decoder is None and self.hp.dec is not None:       # the device CIF + NAR decoder (N2)
                 encs, dres = self.hp.encode_device(lines, decode=True)
@@ -338,6 +343,14 @@ class TargetDiarization:
                 text = "".join(seg["text"] for seg in whres[k]).strip()
                 k += 1
                 extra = {"language": ASRProcessor.detect_language(text)}
+            elif whtres is not None:
+                # Whisper with word timestamps: the words of the timeline's <= 30 s segments, already on the timeline's clock, in the
+                # [(word, [start, end])] shape of Paraformer's path; they go through the timestamp branch below (:798-818)
+                stamps = [(w.strip(), [round(a, 3), round(b, 3)]) for seg in whtres[k] for w, (a, b) in seg["words"]]
+                text = "".join(seg["text"] for seg in whtres[k]).strip()
+                lang = [next((seg["language"] for seg in whtres[k] if seg.get("language")), ASRProcessor.detect_language(text))]
+                extra = {"language": lang[0]}
+                k += 1
             else:
                 recognised = self.hp.asr is not None and (dres is not None or self.decoder is not None)
                 if not recognised:                       # no recogniser loaded (asr_detection prints and returns nothing): the chunks keep empty texts

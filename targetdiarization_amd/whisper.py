@@ -7,7 +7,13 @@ tests/test_whisper_host.py pins the restatement, the prefix and the language tab
 The device does everything up to the token ids: log-mel features, the encoder, the cross-attention K / V of every decoder layer and
 the greedy decoding loop over a KV cache (one host read per 16 steps).  The host builds the prefix, and turns ids into text through
 the byte-level BPE alphabet when a piece table is given.  Deviations from the reference: fp32 (it runs .half()), one prefix per call,
-greedy decoding only (no beams, temperature fallback, timestamps or long-form), tokenizer files are read when present, never required."""
+greedy decoding only (no beams, temperature fallback, timestamp tokens or long-form), tokenizer files are read when present, never required.
+
+Word timestamps (the reference's whisper_v2 / whisper_v3 engines, ASRProcessor.py:232-243, 443-488): decode_xattn() also
+captures the cross-attention rows of the alignment heads, token_align() turns them into one encoder frame per token on the device
+(transformers' _extract_token_timestamps: normalise over the tokens, median filter, mean over the heads, dynamic time warping), and the
+host groups tokens into words as transformers' _combine_tokens_into_words does.  detect_language() is one decode step over the
+language ids; load_openai_checkpoint() reads OpenAI's {"dims", "model_state_dict"} files."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,6 +27,13 @@ from . import _lib
 from .weights import pack_blob, whisper_config
 
 MAX_BATCH = 32
+TIME_PRECISION = 0.02                                  # seconds per encoder position
+MEDIAN_WIDTH = 7                                       # WhisperConfig.median_filter_width, openai/whisper timing.py
+MAX_ALIGN_HEADS = 64
+XATTN_BUDGET = 1 << 30                                 # bytes of captured attention per decode call on the alignment path
+UNSPACED_LANGUAGES = ("zh", "ja", "th", "lo", "my", "yue")
+PREPEND_PUNCTUATIONS = "\"'“¡¿([{-"
+APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
 
 # openai/whisper tokenizer.py LANGUAGES, in its order: the id of <|code|> is 50259 + the index
 LANGUAGES = (
@@ -143,11 +156,133 @@ def decode_text(ids, token_list, eos: int = 50257) -> str:
     return bytes(_BYTE_DECODER[ch] for ch in text if ch in _BYTE_DECODER).decode("utf-8", errors="replace")
 
 
+def default_alignment_heads(cfg) -> list:
+    """openai/whisper model.py: every head of the upper half of the decoder layers"""
+    c = whisper_config(cfg)
+    return [[l, h] for l in range(c["dec_layers"] // 2, c["dec_layers"]) for h in range(c["dec_heads"])]
+
+
+def _pieces_text(ids, token_list) -> str:
+    """tokenizer.decode of ordinary ids: the pieces joined, back to bytes, UTF-8 with errors="replace"; "<id>" without a table"""
+    if token_list is None:
+        return "".join(f"<{int(i)}>" for i in ids)
+    text = "".join(token_list[int(i)] if int(i) < len(token_list) else "" for i in ids)
+    return bytes(_BYTE_DECODER[ch] for ch in text if ch in _BYTE_DECODER).decode("utf-8", errors="replace")
+
+
+def split_tokens_on_unicode(ids, token_list):
+    """transformers' _split_tokens_on_unicode: cut wherever the ids so far decode to whole code points -> (words, ids per word,
+    indices per word)"""
+    full = _pieces_text(ids, token_list)
+    words, word_ids, word_idx, cur, cur_idx, offset = [], [], [], [], [], 0
+    for k, t in enumerate(ids):
+        cur.append(int(t))
+        cur_idx.append(k)
+        dec = _pieces_text(cur, token_list)
+        at = dec.find("\ufffd")
+        if at < 0 or offset + at >= len(full) or full[offset + at] == "\ufffd":
+            words.append(dec); word_ids.append(cur); word_idx.append(cur_idx)
+            cur, cur_idx = [], []
+            offset += len(dec)
+    return words, word_ids, word_idx
+
+
+def split_tokens_on_spaces(ids, token_list, eos: int = 50257):
+    """transformers' _split_tokens_on_spaces: a new word at a special id, a leading space, a punctuation mark or the start"""
+    words, word_ids, word_idx = [], [], []
+    for sub, sid, sidx in zip(*split_tokens_on_unicode(ids, token_list)):
+        if sid[0] >= eos or sub.startswith(" ") or sub.strip() in "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~" or not words:
+            words.append(sub); word_ids.append(sid); word_idx.append(sidx)
+        else:
+            words[-1] = words[-1] + sub
+            word_ids[-1].extend(sid)
+            word_idx[-1].extend(sidx)
+    return words, word_ids, word_idx
+
+
+def merge_punctuations(words, word_ids, word_idx, prepended=PREPEND_PUNCTUATIONS, appended=APPEND_PUNCTUATIONS):
+    """transformers' _merge_punctuations, in place: opening marks join the word after them, closing marks the word before"""
+    i, j = len(words) - 2, len(words) - 1
+    while i >= 0:
+        if words[i].startswith(" ") and words[i].strip() in prepended:
+            words[j] = words[i] + words[j]; word_ids[j] = word_ids[i] + word_ids[j]; word_idx[j] = word_idx[i] + word_idx[j]
+            words[i], word_ids[i], word_idx[i] = "", [], []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(words):
+        if not words[i].endswith(" ") and words[j] in appended:
+            words[i] += words[j]; word_ids[i] += word_ids[j]; word_idx[i] += word_idx[j]
+            words[j], word_ids[j], word_idx[j] = "", [], []
+        else:
+            i = j
+        j += 1
+    words[:] = [w for w in words if w]
+    word_ids[:] = [t for t in word_ids if t]
+    word_idx[:] = [t for t in word_idx if t]
+
+
+def combine_tokens_into_words(ids, token_list, language: str = "en", eos: int = 50257):
+    """transformers' _combine_tokens_into_words over token_list's byte-level pieces: the unicode split for the languages written
+    without spaces, the split on spaces otherwise, then the punctuation merges -> (words, ids per word, indices per word).
+    Without a piece table every id is its own word "<id>"."""
+    ids = [int(t) for t in ids]
+    if token_list is None:
+        return [f"<{t}>" for t in ids], [[t] for t in ids], [[k] for k in range(len(ids))]
+    if language_code(language) in UNSPACED_LANGUAGES:
+        words, word_ids, word_idx = split_tokens_on_unicode(ids, token_list)
+    else:
+        words, word_ids, word_idx = split_tokens_on_spaces(ids, token_list, eos)
+    merge_punctuations(words, word_ids, word_idx)
+    return words, word_ids, word_idx
+
+
+def word_timestamps(ids, times, token_list, language: str = "en", eos: int = 50257):
+    """generated ids + one time per id -> [(word, [start_s, end_s]), ...] over the ordinary ids (< eos): a word starts at its first
+    token's time and ends where the next word starts, the last one at the final entry of `times`"""
+    keep = [k for k, t in enumerate(ids) if int(t) < eos]
+    if not keep:
+        return []
+    words, _, word_idx = combine_tokens_into_words([ids[k] for k in keep], token_list, language, eos)
+    starts = [float(times[keep[idx[0]]]) for idx in word_idx]
+    ends = starts[1:] + [float(times[-1])]
+    return [(w, [s, e]) for w, s, e in zip(words, starts, ends)]
+
+
+def token_align(xattn: torch.Tensor, nrows, nframes, median_width: int = MEDIAN_WIDTH, want_matrix: bool = False):
+    """tdx_token_align: xattn float32 [B, nh, max_rows, n_audio_ctx] on the device, nrows / nframes per clip -> frames int32
+    [B, max_rows] (entry i of clip b: the encoder position at which token row i begins; entries >= nrows[b] hold -1) and, with
+    want_matrix, the normalised, filtered, head-averaged matrix [B, max_rows, n_audio_ctx] (zeros where nothing is written)"""
+    if xattn.dim() != 4 or xattn.dtype != torch.float32 or not xattn.is_cuda or not xattn.is_contiguous():
+        raise _lib.TdxError("token_align: xattn must be a contiguous float32 [B, nh, max_rows, n_audio_ctx] tensor on the device")
+    B, nh, R, S = xattn.shape
+    dev = xattn.device
+    l = _lib.lib()
+    nr = torch.as_tensor(nrows, dtype=torch.int32).reshape(-1).to(dev)
+    nf = torch.as_tensor(nframes, dtype=torch.int32).reshape(-1).to(dev)
+    if nr.numel() != B or nf.numel() != B:
+        raise _lib.TdxError(f"token_align: {B} clips, {nr.numel()} nrows, {nf.numel()} nframes")
+    frames = torch.full((B, R), -1, dtype=torch.int32, device=dev)
+    matrix = torch.zeros(B, R, S, device=dev) if want_matrix else None
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(1, int(l.tdx_token_align_workspace_bytes(B, nh, R, S))), dtype=torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(l.tdx_token_align(xattn.data_ptr(), B, nh, R, S, nr.data_ptr(), nf.data_ptr(), int(median_width), frames.data_ptr(),
+                                     matrix.data_ptr() if want_matrix else None, ws.data_ptr(), ws.numel(), st))
+        torch.cuda.current_stream(dev).synchronize()          # the workspace is this call's own
+    return (frames, matrix) if want_matrix else frames
+
+
 class WhisperASR:
-    def __init__(self, state_dict, config, device="cuda:0", token_list=None, tokenizer=None, generation_config=None):
+    def __init__(self, state_dict, config, device="cuda:0", token_list=None, tokenizer=None, generation_config=None, alignment_heads=None):
         self.cfg = c = whisper_config(config)
         self.token_list, self.tokenizer = token_list, tokenizer
         self.gen_cfg = _gen_dict(generation_config) if generation_config is not None else default_generation_config(c["vocab"])
+        heads = alignment_heads if alignment_heads is not None else self.gen_cfg.get("alignment_heads")
+        self.alignment_heads = [[int(l), int(h)] for l, h in (heads if heads is not None else default_alignment_heads(c))]
+        if any(not (0 <= l < c["dec_layers"] and 0 <= h < c["dec_heads"]) for l, h in self.alignment_heads):
+            raise ValueError(f"alignment_heads: (layer, head) pairs inside {c['dec_layers']} layers x {c['dec_heads']} heads")
         keep = {k: v for k, v in state_dict.items() if k.startswith(("model.", "proj_out."))}
         emb, po = keep.get("model.decoder.embed_tokens.weight"), keep.get("proj_out.weight")
         if po is not None and emb is not None and po.shape == emb.shape and (po is emb or torch.equal(po, emb)):
@@ -241,29 +376,122 @@ class WhisperASR:
                                                   counts.data_ptr(), ws.data_ptr(), ws.numel(), st))
         return ids, scores, counts
 
+    def decode_xattn(self, state: torch.Tensor, prefix, max_new: int, suppress=(), begin_suppress=(), eos=None, first_row=None, max_rows=None,
+                     heads=None, xattn=None):
+        """decode() through tdx_whisper_decode_xattn: the same ids, scores and counts (bit for bit), plus xattn float32
+        [B, nh, max_rows, n_audio_ctx]: row p - first_row of head k holds the cross-attention probabilities of `heads[k]` at the
+        step that fed position p.  Defaults: the model's alignment heads, first_row = len(prefix) (the first generated token),
+        max_rows = max(1, max_new - 1).  Rows no step reached keep what `xattn` held (zeros when it is allocated here)."""
+        self._check_open()
+        c = self.cfg
+        B = int(state.shape[2])
+        self._check_batch(B)
+        if tuple(state.shape) != (c["dec_layers"], 2, B, c["n_audio_ctx"], c["d_model"]) or not state.is_contiguous():
+            raise _lib.TdxError("WhisperASR.decode_xattn: state is not encode(..., with_state=True)'s")
+        eos = int(self.gen_cfg["eos_token_id"] if eos is None else eos)
+        prefix, suppress, begin_suppress = list(prefix), list(suppress), list(begin_suppress)
+        heads = [[int(l), int(h)] for l, h in (self.alignment_heads if heads is None else heads)]
+        first_row = len(prefix) if first_row is None else int(first_row)
+        max_rows = max(1, int(max_new) - 1) if max_rows is None else int(max_rows)
+        nh = len(heads)
+        if xattn is None and 1 <= nh <= MAX_ALIGN_HEADS and max_rows >= 1:
+            xattn = torch.zeros(B, nh, max_rows, c["n_audio_ctx"], device=self.device)
+        elif xattn is not None and (tuple(xattn.shape) != (B, nh, max_rows, c["n_audio_ctx"]) or xattn.dtype != torch.float32
+                                    or not xattn.is_contiguous() or xattn.device != torch.device(self.device)):
+            raise _lib.TdxError(f"WhisperASR.decode_xattn: xattn must be contiguous float32 [{B}, {nh}, {max_rows}, {c['n_audio_ctx']}] on {self.device}")
+        ids = torch.full((B, c["n_text_ctx"]), -1, dtype=torch.int32, device=self.device)
+        scores = torch.zeros(B, c["n_text_ctx"], device=self.device)
+        counts = torch.zeros(B, dtype=torch.int32, device=self.device)
+        arr = lambda v: (C.c_int * max(1, len(v)))(*[int(t) for t in v])
+        flat = [t for pair in heads for t in pair]
+        with self._guard.call():
+            ws = self._guard.workspace(self.workspace_bytes(B))
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self._l.tdx_whisper_decode_xattn(self._h, state.data_ptr(), B, arr(prefix), len(prefix), arr(suppress), len(suppress),
+                                                        arr(begin_suppress), len(begin_suppress), eos, int(max_new), arr(flat), nh, first_row, max_rows,
+                                                        xattn.data_ptr() if xattn is not None else None, ids.data_ptr(), scores.data_ptr(),
+                                                        counts.data_ptr(), ws.data_ptr(), ws.numel(), st))
+        return ids, scores, counts, xattn
+
+    def detect_language(self, state: torch.Tensor) -> list:
+        """the language code of every clip of encode()'s state: one decode step after <|startoftranscript|> with every id that is
+        not a language token suppressed (openai/whisper decoding.py detect_language; transformers' detect_language)"""
+        g = self.gen_cfg
+        lang_ids = sorted(int(v) for v in g["lang_to_id"].values())
+        allowed = set(lang_ids)
+        suppress = [i for i in range(self.cfg["vocab"]) if i not in allowed]
+        ids, _, _ = self.decode(state, [int(g["decoder_start_token_id"])], 1, suppress, ())
+        by_id = {int(v): k for k, v in g["lang_to_id"].items()}
+        return [language_code(by_id[int(t)]) for t in ids[:, 0].cpu().tolist()]
+
+    def num_frames(self, n_samples: int) -> int:
+        """encoder positions that a clip of n_samples covers: ceil(n / 320), within [1, n_audio_ctx]"""
+        return max(1, min(self.cfg["n_audio_ctx"], -(-int(n_samples) // 320)))
+
     def text_of(self, ids) -> str:
         return decode_text(ids, self.token_list, int(self.gen_cfg["eos_token_id"]))
 
-    def generate(self, wavs, language: str = "chinese", task: str = "transcribe", prompt_ids=None, max_new_tokens=None, keys=None):
+    def generate(self, wavs, language: str = "chinese", task: str = "transcribe", prompt_ids=None, max_new_tokens=None, keys=None,
+                 return_timestamps: bool = False):
         """list of 1-D 16 kHz clips (or one clip) -> per clip {"key", "text", "token_ids", "scores"}: the generated ids (a final
-        end-of-text included) and their log-probabilities.  Clips go through in batches of 32, cut to 30 s."""
+        end-of-text included) and their log-probabilities.  Clips go through in batches of 32, cut to 30 s.
+        language None or "auto": the language of every clip is detected and the clips are decoded grouped by language (one prefix
+        per decode call); each result then also carries "language" (the code).
+        return_timestamps: each result also carries "token_times" (seconds, one per generated id: 0.02 x the encoder position at
+        which the alignment heads' cross-attention path enters the token; the last id repeats the one before it, a lone id gets 0)
+        and "words" ([(word, [start_s, end_s]), ...] over the ordinary ids).  The ids and scores are those of the plain call."""
         self._check_open()
         if isinstance(wavs, (np.ndarray, torch.Tensor)):
             wavs = [wavs]
         g, T = self.gen_cfg, self.cfg["n_text_ctx"]
-        prefix = decode_prefix(language, task, prompt_ids, g, T)
-        max_new = new_token_limit(len(prefix), max_new_tokens, g, T)
+        auto = language is None or str(language).strip().lower() == "auto"
+        if return_timestamps and not 1 <= len(self.alignment_heads) <= MAX_ALIGN_HEADS:
+            raise ValueError(f"{len(self.alignment_heads)} alignment heads: pass 1..{MAX_ALIGN_HEADS} pairs as alignment_heads= or in the generation config")
+        sup, beg, eos = g.get("suppress_tokens") or (), g.get("begin_suppress_tokens") or (), int(g["eos_token_id"])
         out = []
         for c0 in range(0, len(wavs), MAX_BATCH):
             chunk = wavs[c0:c0 + MAX_BATCH]
+            nsamp = [min(self.n_samples, int(np.prod(np.shape(w)))) for w in chunk]
             _, state = self.encode(self.features(chunk), with_state=True)
-            ids, scores, counts = self.decode(state, prefix, max_new, g.get("suppress_tokens") or (), g.get("begin_suppress_tokens") or ())
-            ids, scores, counts = ids.cpu().numpy(), scores.cpu().numpy(), counts.cpu().tolist()
-            p0 = len(prefix) - 1                            # the step that wrote the first generated token
-            for b, n in enumerate(counts):
-                tok = [int(t) for t in ids[b, p0:p0 + n]]
-                out.append({"key": keys[c0 + b] if keys is not None else f"clip_{c0 + b}", "text": self.text_of(tok), "token_ids": tok,
-                            "scores": [float(s) for s in scores[b, p0:p0 + n]]})
+            if auto:
+                langs = self.detect_language(state)
+                groups = [(lg, [b for b, l in enumerate(langs) if l == lg]) for lg in sorted(set(langs))]
+            else:
+                langs, groups = None, [(language, list(range(len(chunk))))]
+            res = [None] * len(chunk)
+            for lg, members in groups:
+                prefix = decode_prefix(lg, task, prompt_ids, g, T)
+                max_new = new_token_limit(len(prefix), max_new_tokens, g, T)
+                p0 = len(prefix) - 1                        # the step that wrote the first generated token
+                step = len(members)
+                if return_timestamps:                       # smaller groups on the alignment path only: the capture buffer stays bounded
+                    row_bytes = 4 * len(self.alignment_heads) * max(1, max_new - 1) * self.cfg["n_audio_ctx"]
+                    step = max(1, min(step, XATTN_BUDGET // row_bytes))
+                for m0 in range(0, len(members), step):
+                    mem = members[m0:m0 + step]
+                    st = state if len(mem) == len(chunk) else state[:, :, mem].contiguous()
+                    if return_timestamps:
+                        ids, scores, counts, xattn = self.decode_xattn(st, prefix, max_new, sup, beg)
+                        counts_l = counts.cpu().tolist()
+                        nrows = [max(0, n - 1) for n in counts_l]
+                        frames = token_align(xattn, nrows, [self.num_frames(nsamp[b]) for b in mem]).cpu().tolist()
+                        del xattn
+                    else:
+                        ids, scores, counts = self.decode(st, prefix, max_new, sup, beg)
+                        counts_l = counts.cpu().tolist()
+                    ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
+                    for k, (b, n) in enumerate(zip(mem, counts_l)):
+                        tok = [int(t) for t in ids[k, p0:p0 + n]]
+                        r = {"key": keys[c0 + b] if keys is not None else f"clip_{c0 + b}", "text": self.text_of(tok), "token_ids": tok,
+                             "scores": [float(v) for v in scores[k, p0:p0 + n]]}
+                        if auto:
+                            r["language"] = langs[b]
+                        if return_timestamps:
+                            t = [f * TIME_PRECISION for f in frames[k][:max(0, n - 1)]]
+                            r["token_times"] = (t + [t[-1]]) if t else [0.0] * n
+                            r["words"] = word_timestamps(tok, r["token_times"], self.token_list, language_code(lg), eos)
+                        res[b] = r
+            out.extend(res)
         return out
 
     def close(self):
@@ -282,10 +510,54 @@ def load_token_list(vocab_json):
     return tl
 
 
-def build_whisper(state_dict=None, config=None, model_dir=None, token_list=None, tokenizer=None, generation_config=None, cuda_device: int = 0):
-    """The device recogniser from weights + config, or from a transformers model directory: config.json plus model.safetensors or
-    pytorch_model.bin, and when present generation_config.json, vocab.json (the piece table) and the tokenizer files (prompts).
+# openai/whisper model.py names -> transformers' (the pairs of transformers' convert_openai_to_hf.py), applied in this order
+OPENAI_NAME_MAP = (("blocks", "layers"), ("mlp.0", "fc1"), ("mlp.2", "fc2"), ("mlp_ln", "final_layer_norm"),
+                   (".attn.query", ".self_attn.q_proj"), (".attn.key", ".self_attn.k_proj"), (".attn.value", ".self_attn.v_proj"),
+                   (".attn_ln", ".self_attn_layer_norm"), (".attn.out", ".self_attn.out_proj"),
+                   (".cross_attn.query", ".encoder_attn.q_proj"), (".cross_attn.key", ".encoder_attn.k_proj"),
+                   (".cross_attn.value", ".encoder_attn.v_proj"), (".cross_attn_ln", ".encoder_attn_layer_norm"),
+                   (".cross_attn.out", ".encoder_attn.out_proj"), ("decoder.ln.", "decoder.layer_norm."), ("encoder.ln_post.", "encoder.layer_norm."),
+                   ("token_embedding", "embed_tokens"), ("encoder.positional_embedding", "encoder.embed_positions.weight"),
+                   ("decoder.positional_embedding", "decoder.embed_positions.weight"))
+
+
+def openai_to_hf_name(name: str) -> str:
+    for a, b in OPENAI_NAME_MAP:
+        name = name.replace(a, b)
+    return "model." + name
+
+
+def openai_dims_to_config(dims) -> dict:
+    """openai/whisper ModelDimensions -> whisper_config's dict"""
+    d = dict(dims)
+    if d["n_audio_state"] != d["n_text_state"]:
+        raise ValueError("OpenAI checkpoint: n_audio_state differs from n_text_state")
+    return whisper_config(n_mels=d["n_mels"], n_audio_ctx=d["n_audio_ctx"], d_model=d["n_audio_state"], enc_heads=d["n_audio_head"],
+                          enc_layers=d["n_audio_layer"], n_text_ctx=d["n_text_ctx"], dec_heads=d["n_text_head"], dec_layers=d["n_text_layer"],
+                          vocab=d["n_vocab"])
+
+
+def load_openai_checkpoint(path):
+    """One OpenAI-format .pt file ({"dims", "model_state_dict"}, what whisper.load_model reads; ASRProcessor.py:232-243) ->
+    (state dict in transformers' names, fp32, proj_out.weight tied to the token embedding; whisper_config's dict)"""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(ck, dict) or "dims" not in ck or "model_state_dict" not in ck:
+        raise ValueError(f"{path}: not an OpenAI Whisper checkpoint (no dims / model_state_dict)")
+    sd = {openai_to_hf_name(k): v.float() for k, v in ck["model_state_dict"].items()}
+    sd["proj_out.weight"] = sd["model.decoder.embed_tokens.weight"]
+    return sd, openai_dims_to_config(ck["dims"])
+
+
+def build_whisper(state_dict=None, config=None, model_dir=None, token_list=None, tokenizer=None, generation_config=None, cuda_device: int = 0,
+                  alignment_heads=None):
+    """The device recogniser from weights + config, from a transformers model directory: config.json plus model.safetensors or
+    pytorch_model.bin, and when present generation_config.json, vocab.json (the piece table) and the tokenizer files (prompts),
+    or from one OpenAI-format .pt file (a vocab.json next to it is read when present).
     None when there is neither source.  safetensors / transformers are imported here only, and only when a directory needs them."""
+    if state_dict is None and isinstance(model_dir, str) and os.path.isfile(model_dir):
+        state_dict, config = load_openai_checkpoint(model_dir)
+        if token_list is None:
+            token_list = load_token_list(os.path.join(os.path.dirname(model_dir), "vocab.json"))
     if state_dict is None:
         if not isinstance(model_dir, str) or not os.path.isfile(os.path.join(model_dir, "config.json")):
             return None
@@ -312,4 +584,5 @@ def build_whisper(state_dict=None, config=None, model_dir=None, token_list=None,
                 tokenizer = WhisperTokenizer.from_pretrained(model_dir, local_files_only=True)
             except Exception as e:
                 print(f"Whisper tokenizer not loaded (prompts will be ignored): {e}")
-    return WhisperASR(state_dict, config, device=f"cuda:{cuda_device}", token_list=token_list, tokenizer=tokenizer, generation_config=generation_config)
+    return WhisperASR(state_dict, config, device=f"cuda:{cuda_device}", token_list=token_list, tokenizer=tokenizer, generation_config=generation_config,
+                      alignment_heads=alignment_heads)
