@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import whisper_oracle as wo
+import whisper_widths_cases as wc
 from targetdiarization_amd import _lib
 from targetdiarization_amd import whisper as W
 from targetdiarization_amd.weights import pack_blob, recipe_whisper_state_dict, whisper_config, whisper_param_shapes
@@ -262,6 +263,43 @@ def test_argument_validation_without_gpu(lib):
     assert lib.tdx_whisper_encode(None, None, 1, None, None, None, 0, None) == 1
     assert lib.tdx_whisper_decode(None, None, 1, None, 0, None, 0, None, 0, 0, 0, None, None, None, None, 0, None) == 1
     assert b"tdx_whisper_decode" in lib.tdx_last_error()
+
+
+# ---- the wide, padded and long configurations of tests/test_gpu_whisper_widths.py: what that module asserts about the oracle alone
+@pytest.mark.parametrize("name,nb", wc.TEACHER)
+def test_width_oracle_stays_within_the_margin_cap(name, nb):
+    _, ids, _, mg = wc.teacher_case(name, nb)
+    share, distinct = float((mg <= wc.MARGIN).double().mean()), wc.distinct_clear_ids(ids, mg)
+    print(f"{name} B={nb}: {100 * share:.2f} % of the positions under the margin, {distinct} distinct ids at the clear ones")
+    assert ids.shape == (nb, 64) and int(ids.max()) < wc.VOCAB and max(wc.teacher_prefix()) < wc.VOCAB
+    assert share <= 0.01
+    assert distinct >= wc.MIN_DISTINCT
+
+
+@pytest.mark.parametrize("name", sorted(wc.GREEDY))
+def test_width_greedy_oracle_is_clear(name):
+    prefix, res = wc.greedy_case(name)
+    low = min(min(r["margins"]) for r in res)
+    print(f"{name}: prefix {prefix} (seed {wc.GREEDY[name][1]}), smallest margin {low:.2e}, {len({t for r in res for t in r['tokens']})} distinct ids")
+    assert len(prefix) == 4 and len(res) == wc.GREEDY[name][0]
+    assert low > wc.MARGIN
+    assert all(len(r["tokens"]) == wc.GREEDY_NEW and wc.GREEDY_EOS not in r["tokens"] for r in res)        # end-of-text is never emitted
+    assert len({t for r in res for t in r["tokens"]}) >= wc.MIN_DISTINCT
+
+
+@pytest.mark.parametrize("name", sorted(wc.CFGS))
+def test_width_configs_are_accepted(lib, name):
+    cfg, sd, _ = wc.weights(name)
+    assert cfg["d_model"] == 64 * cfg["enc_heads"] == 64 * cfg["dec_heads"]     # tdx_whisper_create's rule, from whisper_config's defaults
+    assert cfg["enc_ffn"] == cfg["dec_ffn"] == 4 * cfg["d_model"] and cfg["n_text_ctx"] == 448
+    shapes = dict(whisper_param_shapes(cfg))
+    assert {k: tuple(v.shape) for k, v in sd.items()} == shapes
+    assert shapes["model.decoder.embed_tokens.weight"] == (wc.VOCAB, cfg["d_model"])
+    assert shapes["model.encoder.embed_positions.weight"] == (cfg["n_audio_ctx"], cfg["d_model"])
+    rc, msg = _create(lib, cfg, sd)                      # every contract check and the strict loader pass: without a device the call
+    assert rc in (0, 3), (rc, msg)                       # then stops at the upload (TDX_E_HIP), with one it succeeds
+    rc, msg = _create(lib, cfg, sd, enc_heads=cfg["enc_heads"] + 1)
+    assert rc == 1 and "d_model / heads" in msg
 
 
 def test_no_cpu_path(small):

@@ -12,7 +12,10 @@ out.  End-of-text is suppressed so that every clip runs every step.  Per figure:
 The yardstick of a step is its byte count, computed here from the shapes: the decoder's weights, the tied head and the cross K / V
 every clip reads, over 6.0 TB/s (the HBM read-sweep rate of the MI355X).  `share_of_hbm_bound` is that time over the measured one.
 `step_us_b_over_b1` says what the batch costs: the weights are read once per step whatever B is, the cross K / V once per clip.
-The shader clock is read from the driver's pp_dpm_sclk table after the timed loops when the file is there ("not measured" otherwise)."""
+The shader clock is read from the driver's pp_dpm_sclk table after the timed loops when the file is there ("not measured" otherwise).
+
+This tool checks counts, never values.  The values at this width (d 1280, FFN 5120, 20 heads: K = 1280 and 5120 in every Linear, the
+head and the LayerNorms) are checked against the fp64 oracle by tests/test_gpu_whisper_widths.py."""
 from __future__ import annotations
 
 import argparse
