@@ -568,6 +568,36 @@ size_t tdx_token_align_workspace_bytes(int B, int nh, int max_rows, int n_audio_
 int tdx_token_align(const float* xattn_dev, int B, int nh, int max_rows, int n_audio_ctx, const int* nrows_dev, const int* nframes_dev,
                     int median_width, int* frames_dev, float* matrix_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * N6  noisereduce's spectral gate — replaces `nr.reduce_noise(y=audio_data, sr=sampling_rate)`   AudioProcessor.py:655
+ *     (third-party noisereduce, non-stationary mode with its defaults; restated from upstream).
+ *      STFT 1024 / hop 256 / periodic Hann with scipy's boundary="zeros", padded=False frame grid; |S| smoothed along time by
+ *      filtfilt([b], [1, b - 1]) (forward and backward, each pass seeded with the steady state of its first sample); mask =
+ *      sigmoid(((|S| - s) / s - thresh) * slope), 0 where s == 0 (upstream: NaN on digital silence); the mask smoothed by the
+ *      normalised triangles of 2 nf + 1 bins and 2 nt + 1 frames with zero boundaries; mask * prop_decrease + (1 - prop_decrease);
+ *      inverse STFT.  No model: create takes the device alone and builds the two DFT bases in double.
+ *      A call gates nbuf buffers: x_dev [n_total] holds the clips packed back to back, y_dev [n_total] receives the kept samples
+ *      (nothing else of it is written).  The table has 8 int64 per buffer — src_off, v0, v1, k0, k1, dst_off, L, row0 — and is
+ *      passed twice with equal contents: table_host is validated and planned from, table_dev is what the kernels read.
+ *      Buffer sample i is x[src_off + i] for v0 <= i < v1 and zero elsewhere in [0, L); F = 1 + L / 256 frames; samples [k0, k1)
+ *      go to y[dst_off ...], and each needs its four frames: 256 <= k0, k1 <= 256 * (L / 256 - 1).  A buffer takes
+ *      tdx_ngate_rows(L) = F + 3 rows; buffers fill rounds in order, a round is closed when the next buffer would take it past
+ *      rows_per_launch, and row0 is the buffer's first row in its round.  The workspace is sized by the rows of the largest
+ *      round.  Seven launches per round whatever nbuf.  The result of a buffer does not depend on the other buffers, on
+ *      rows_per_launch or on the call.  1 <= nbuf <= 65535, F <= 32768, 0 <= nf, nt <= 128, 0 < b <= 1, 0 <= prop_decrease <= 1;
+ *      every table entry is checked against n_total and L before the device is touched, each violation with its own message.
+ *      Taps (NULL or [F, 513] of buffer 0): |S|, the smoothed |S|, the mask before and after its smoothing.
+ * ---------------------------------------------------------------------------------- */
+typedef struct tdx_ngate tdx_ngate;
+int tdx_ngate_create(int device, tdx_ngate** out);
+int tdx_ngate_destroy(tdx_ngate* h);
+long tdx_ngate_rows(long L);
+size_t tdx_ngate_workspace_bytes(const tdx_ngate* h, long rows);
+int tdx_ngate_forward(tdx_ngate* h, const float* x_dev, long n_total, const int64_t* table_host, const int64_t* table_dev, int nbuf,
+                      long rows_per_launch, double b, int nf, int nt, float thresh, float slope, float prop_decrease, float* y_dev,
+                      float* tap_mag_dev, float* tap_smooth_dev, float* tap_mask_dev, float* tap_msmooth_dev, void* workspace_dev,
+                      size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,12 @@ SIGNATURES = {
                                       C.POINTER(C.c_int), _i, _i, _i, _fp, _vp, _fp, _vp, _vp, _sz, _vp]),
     "tdx_token_align_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "tdx_token_align": (_i, [_fp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _fp, _vp, _sz, _vp]),
+    "tdx_ngate_create": (_i, [_i, C.POINTER(_vp)]),
+    "tdx_ngate_destroy": (_i, [_vp]),
+    "tdx_ngate_rows": (C.c_long, [C.c_long]),
+    "tdx_ngate_workspace_bytes": (_sz, [_vp, C.c_long]),
+    "tdx_ngate_forward": (_i, [_vp, _fp, C.c_long, _vp, _vp, _i, C.c_long, C.c_double, _i, _i, C.c_float, C.c_float, C.c_float, _fp,
+                               _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
 }
 
 

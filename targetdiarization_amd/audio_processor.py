@@ -15,8 +15,13 @@ implementation of its architecture (`mdx_state_dict` -> `mdx.ConvTDFNetBody`, cs
 `restore_audio` (:959-980) runs the Apollo restorer on the device (`apollo.ApolloRestorer`, csrc/apollo.hip) from
 `<restorer_weights_folder>/pytorch_model.bin` like `init_restorer_model` (:277-281), or from an in-memory `restorer_state_dict`.
 
-Out of scope here: enhancer, noisereduce (fast_mode), file I/O — those flags are accepted and degrade to
-"module skipped" exactly like the reference does when a package is disabled.
+`denoise_vocal`'s other body (:654-656, `fast_mode=True` or no MDX model: `nr.reduce_noise(y=audio_data, sr=sampling_rate)`) is
+noisereduce's non-stationary spectral gate on the device (`noise_gate.SpectralGate`, csrc/noise_gate.hip) behind the constructor
+flag `noise_reduce=True`; with the default False the audio is returned unchanged, as before.  The third-party algorithm is
+restated from upstream (package parity unpinned); where the smoothed magnitude is exactly 0 the mask is 0 (upstream: NaN).
+
+Out of scope here: enhancer, file I/O — those flags are accepted and degrade to "module skipped" exactly like
+the reference does when a package is disabled.
 """
 from __future__ import annotations
 
@@ -38,7 +43,8 @@ class AudioProcessor:
                  is_restore_audio: bool = False, restorer_weights_folder: str = "JusperLee/Apollo",
                  verbose_log: bool = True, cuda_device: int = 0, quality: int = 2,
                  separater_state_dict=None, mdx_model=None, mdx_dim_f: int = 3072, mdx_n_fft: int = 6144, silero_vad=None,
-                 mdx_state_dict=None, mdx_args=None, restorer_state_dict=None, silero_state_dict=None, silero_model_file=None):
+                 mdx_state_dict=None, mdx_args=None, restorer_state_dict=None, silero_state_dict=None, silero_model_file=None,
+                 noise_reduce: bool = False):
         """`separater_state_dict` (extension): an in-memory state_dict instead of
         `<separater_weights_folder>/best_model.pth` — no checkpoint ships with the reference.
         `mdx_model` (extension): the MDX net body as a callable on device tensors, spec[n,4,dim_f,256] -> spec (the
@@ -47,7 +53,9 @@ class AudioProcessor:
         `restorer_state_dict` (extension): the Apollo weights in memory instead of `<restorer_weights_folder>/pytorch_model.bin`
         (the reference's 6 layers, or as many as the dict holds).
         `silero_state_dict` / `silero_model_file` (extension): silero-VAD's weights in memory or as a file; without a `silero_vad`
-        plug-in they put the device detector (silero.SileroVad.frames) behind `separate_speaker(low_gpu_ram=True)`."""
+        plug-in they put the device detector (silero.SileroVad.frames) behind `separate_speaker(low_gpu_ram=True)`.
+        `noise_reduce` (extension): run noisereduce's spectral gate on the device (noise_gate.SpectralGate) where the reference
+        calls `nr.reduce_noise` (:655): `denoise_vocal(fast_mode=True)` and the denoiser-off case.  False: audio returned unchanged."""
         if is_denoise_vocal and mdx_model is None and mdx_state_dict is not None:
             # the ConvTDFNet body on the device (mdx.ConvTDFNetBody, csrc/mdx.hip) from a state dict with the PyTorch module names;
             # `mdx_args`: its geometry (L, l, g, k, bn, dim_f, dim_t, max_blocks_per_launch).  A failure prints and leaves the denoiser
@@ -90,6 +98,15 @@ class AudioProcessor:
                 self.is_separate_audio = False
         else:
             self.is_separate_audio = False
+        self.noise_gate = None
+        self.noise_reduce = bool(noise_reduce) and str(self.device) != "cpu"
+        if self.noise_reduce:
+            try:
+                from .noise_gate import SpectralGate
+                self.noise_gate = SpectralGate("cuda:0" if self.device == "cuda" else self.device)
+            except Exception as e:
+                print(f"Failed to init noise gate: {e}")
+                self.noise_reduce = False
         self.restorer = None
         self.is_restore_audio = is_restore_audio
         if self.is_restore_audio and (restorer_state_dict is not None or os.path.isdir(self.restorer_weights_folder)):
@@ -330,8 +347,10 @@ class AudioProcessor:
         if self.verbose_log:
             print("\nRunning module: denoise_vocal")
             print("Using method: noisereduce" if fast_mode else f"Using method: MDX-Net\nUsing model: {self.mdx_weights_file}")
+        if fast_mode and self.noise_reduce:
+            return self.noise_gate.reduce_noise(audio_data, sampling_rate)                 # :655
         if fast_mode:
-            print("denoise_vocal: noisereduce (fast_mode) is a third-party CPU package outside the MI355X hot path; audio returned unchanged")
+            print("denoise_vocal: noisereduce (fast_mode) runs on the device only with noise_reduce=True; audio returned unchanged")
             return audio_data
         if self.mdx_net is None:
             self.init_mdx_model()

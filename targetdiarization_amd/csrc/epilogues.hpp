@@ -7,6 +7,7 @@
 //   EpiBiasResN<Act>   the same, columns n < nreal only (the residual is not read beyond them either)
 //   EpiBiasRes2<Act>   out[m][n] = act((v + b[n]) + (res[m][n] + res2[m][n])), res2 may be null
 //   EpiStoreZ          out[z][m][n] = v
+//   EpiSpecMag         PAIRED: spec[m][c] = re, spec[m][im_off + c] = im, mag[m][c] = sqrt(re^2 + im^2), columns c < nreal
 // A null b is a zero bias in all of them.  The order of the additions is fixed — bias first, then the residual (itself summed
 // first where there are two), then the activation — so that the results do not depend on which struct a call site picks.
 // The column guard is a struct of its own rather than nreal = INT_MAX in the unguarded one: the compare would sit in every
@@ -91,6 +92,22 @@ struct EpiStoreZ {
     __device__ EpiNone col(int, int) const { return EpiNone{}; }
     __device__ EpiNone row(int, int) const { return EpiNone{}; }
     __device__ void store(int z, int m, int n, float v, EpiNone, EpiNone) const { out[(long)z * strideZ + (long)m * (int)ld + n] = v; }
+};
+
+// ---- PAIRED (re, im) columns of a DFT: the spectrum as two half rows [re 0..nreal | im 0..nreal] and its magnitude
+struct EpiSpecMag {
+    float* spec; float* mag; long lds; long ldm; int im_off; int nreal;
+    __device__ EpiNone col(int, int) const { return EpiNone{}; }
+    __device__ EpiNone row(int, int) const { return EpiNone{}; }
+    __device__ void store2(int, int m, int c, float re, float im, EpiNone, EpiNone) const {
+        if (c < nreal) {
+            float* s = spec + (long)m * (int)lds + c;
+            s[0] = re; s[im_off] = im;
+            // an explicit fma: left to -ffp-contract the guarded and the unguarded epilogue of the core fused re^2 + im^2
+            // differently, and a row's last bit then depended on whether its tile was the last one
+            mag[(long)m * (int)ldm + c] = sqrtf(fmaf(re, re, im * im));
+        }
+    }
 };
 
 // ---- nn.Linear / 1x1 convolution: out = epi(A [M][K] (row pitch lda) x W[N][K]^T), one launch, a TDX status back

@@ -65,14 +65,15 @@ class HotPath:
                  mdx_state_dict=None, mdx_args=None, restorer_state_dict=None, restorer_weights_folder: str | None = None,
                  sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None, sensevoice_model_dir=None,
                  sensevoice_token_file=None, whisper_state_dict=None, whisper_config=None, whisper_model_dir=None, whisper_token_list=None,
-                 whisper_tokenizer=None, whisper_generation_config=None):
+                 whisper_tokenizer=None, whisper_generation_config=None, noise_reduce: bool = False):
         from .audio_processor import AudioProcessor
         self.device = torch.device(f"cuda:{cuda_device}")
         self.ap = AudioProcessor(is_separate_audio=True, separater_state_dict=sep_state_dict, cuda_device=cuda_device, verbose_log=False,
                                  is_denoise_vocal=mdx_model is not None or mdx_state_dict is not None, mdx_model=mdx_model,
                                  mdx_weights_file=mdx_weights_file, quality=3, mdx_state_dict=mdx_state_dict, mdx_args=mdx_args,
                                  is_restore_audio=restorer_state_dict is not None or bool(restorer_weights_folder),
-                                 restorer_weights_folder=restorer_weights_folder or "", restorer_state_dict=restorer_state_dict)
+                                 restorer_weights_folder=restorer_weights_folder or "", restorer_state_dict=restorer_state_dict,
+                                 noise_reduce=noise_reduce)
         if not self.ap.is_separate_audio:
             from ._lib import TdxError
             raise TdxError("separator failed to initialise")

@@ -120,7 +120,8 @@ def env_to_kwargs(environ=None) -> Dict[str, Any]:
     the constructor defaults, EXCEPT the three flags the reference always passes (VERBOSE_LOG == "1"; IS_VAD_BUFFER and
     USE_ASR_PROMPT true unless "0").  (ASR_ENGINE is in .env.example but main.py does not read it — neither does this.)
     SENSEVOICE_MODEL_DIR (funasr's model.pt + am.mvn) and SENSEVOICE_TOKEN_FILE (the piece table) are this project's: where the device
-    SenseVoiceSmall of asr_engine="sensevoice" loads from."""
+    SenseVoiceSmall of asr_engine="sensevoice" loads from.  NOISE_REDUCE=1 is this project's too: noisereduce's spectral gate on the
+    device as denoise_vocal's body when the MDX denoiser is off (noise_reduce=True); unset or anything else leaves the default."""
     import os
     env = os.environ if environ is None else environ
 
@@ -141,6 +142,7 @@ def env_to_kwargs(environ=None) -> Dict[str, Any]:
         "sensevoice_token_file": env.get("SENSEVOICE_TOKEN_FILE"),
         "vad_model_dir": env.get("VAD_MODEL_DIR"),
         "silero_model_file": env.get("SILERO_VAD_MODEL"),
+        "noise_reduce": True if env.get("NOISE_REDUCE") == "1" else None,
         "separater_weights_folder": env.get("SEPARATER_WEIGHTS_FOLDER"),
         "restorer_weights_folder": env.get("RESTORER_WEIGHTS_FOLDER"),
         "is_vad_buffer": env.get("IS_VAD_BUFFER") != "0",

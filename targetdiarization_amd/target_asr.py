@@ -93,13 +93,16 @@ class TargetASR:
                  asr_model_dir: Union[str, list, None] = None, mdx_weights_file: Optional[str] = None,
                  separater_weights_folder: Optional[str] = None, restorer_weights_folder: Optional[str] = None, verbose_log: bool = False,
                  *, spk_state_dict=None, vad: Optional[Callable] = None, loudness_control: Optional[Callable] = None,
-                 campp_state_dict=None, vad_state_dict=None, vad_cmvn=None):
+                 campp_state_dict=None, vad_state_dict=None, vad_cmvn=None, noise_reduce: bool = False):
         """campp_state_dict: CAM++ weights (3D-Speaker names) -> `self.embedding["campp"]` (TargetASR.py:109);
         vad(audio) -> [[start_s, end_s], ...]: FunASR FSMN-VAD (`self.asrp.vad_detection`); `vad_state_dict` (+ `vad_cmvn`) or a funasr
         `vad_model_dir` (model.pt + am.mvn) builds the device detector (vad.FsmnVad), default = whole clip;
         loudness_control(audio) -> audio: AudioProcessor.audio_loudness_control (:417-429), default = the BS.1770 host meter"""
         self.cuda_device = cuda_device
         self.verbose_log = verbose_log
+        # the reference's TargetASR owns the AudioProcessor whose denoise_vocal runs noisereduce (TargetASR.py:63-65); here that
+        # AudioProcessor belongs to pipeline.HotPath, which TargetDiarization builds with this flag
+        self.noise_reduce = bool(noise_reduce)
         if vad is None:
             from .vad import build_vad
             vad = build_vad(vad_state_dict, vad_cmvn, vad_model_dir, cuda_device)

@@ -64,8 +64,9 @@ class TargetDiarization:
                  od_state_dict=None, od_embed: Optional[Callable] = None, od_embed_state_dict=None, od_embed_model_dir=None,
                  sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None, sensevoice_model_dir=None,
                  sensevoice_token_file=None, whisper_state_dict=None, whisper_config=None, whisper_model_dir=None, whisper_token_list=None,
-                 whisper_tokenizer=None, whisper_generation_config=None, **kwargs):
+                 whisper_tokenizer=None, whisper_generation_config=None, noise_reduce: bool = False, **kwargs):
         self.target_similarity_threshold = target_similarity_threshold
+        self.noise_reduce = bool(noise_reduce)    # noisereduce's spectral gate on the device as denoise_vocal's body when the MDX denoiser is off
         self.asr_engine = asr_engine
         self.cuda_device = cuda_device
         self.verbose_log = verbose_log
@@ -98,7 +99,8 @@ class TargetDiarization:
                           sensevoice_state_dict=sensevoice_state_dict, sensevoice_token_list=sensevoice_token_list, sensevoice_cmvn=sensevoice_cmvn,
                           sensevoice_model_dir=sensevoice_model_dir, sensevoice_token_file=sensevoice_token_file,
                           whisper_state_dict=whisper_state_dict, whisper_config=whisper_config, whisper_model_dir=whisper_model_dir,
-                          whisper_token_list=whisper_token_list, whisper_tokenizer=whisper_tokenizer, whisper_generation_config=whisper_generation_config)
+                          whisper_token_list=whisper_token_list, whisper_tokenizer=whisper_tokenizer, whisper_generation_config=whisper_generation_config,
+                          **({"noise_reduce": True} if noise_reduce else {}))
         if od_pipeline is None:               # pyannote's overlap-aware diarization on the device (overlap.py, tdx_pyannet_*); neither source: none
             from .overlap import build_od_pipeline
             embed = od_embed if od_embed is not None else (self.hp.spk.get_speaker_embeddings if self.hp.spk is not None else None)
@@ -128,29 +130,53 @@ class TargetDiarization:
             return audio
         return (audio * (10.0 ** ((target_loudness - loud) / 20.0))).astype(np.float32)
 
-    def audio_preprocess(self, audio, sampling_rate: int = 16000, stream_mode: bool = False):
-        """:166-182: mono -> float32 -> 16 kHz -> -23 LUFS -> denoise_vocal (or, in stream mode, the louder separated stream) ->
-        -23 LUFS again; a failure inside the chain is printed and the audio of the last good step returned, like the reference"""
+    @staticmethod
+    def _mono_float32(audio):
         audio = np.asarray(audio)
         if audio.ndim > 1:
             audio = audio.mean(axis=-1)
         if audio.dtype == np.int16:
             audio = audio.astype(np.float32) / 32768.0
-        audio = audio.astype(np.float32)
+        return audio.astype(np.float32)
+
+    def audio_preprocess(self, audio, sampling_rate: int = 16000, stream_mode: bool = False):
+        """:166-182: mono -> float32 -> 16 kHz -> -23 LUFS -> denoise_vocal (or, in stream mode, the louder separated stream) ->
+        -23 LUFS again; a failure inside the chain is printed and the audio of the last good step returned, like the reference.
+        With the denoiser off, denoise_vocal is noisereduce's spectral gate when the model was built with noise_reduce=True
+        (noise_gate.SpectralGate); without the flag the chain ends after the first loudness pass."""
+        audio = self._mono_float32(audio)
         try:
             if sampling_rate != 16000:
                 audio, sampling_rate = self.hp.ap.audio_resample(audio, sampling_rate, 16000)
             audio = self.audio_loudness_control(audio)
             if stream_mode:
                 audio, _ = self.hp.ap.separate_speaker(audio, sampling_rate)
-            elif self.hp.ap.is_denoise_vocal:
+            elif self.hp.ap.is_denoise_vocal or getattr(self.hp.ap, "noise_reduce", False):
                 audio = self.hp.ap.denoise_vocal(audio, sampling_rate)[: audio.shape[0]]
             else:
-                return audio              # (denoiser off: the reference's fast_mode falls back to noisereduce, a third-party CPU package)
+                return audio              # (denoiser off and no noise_reduce flag: the reference's fast_mode runs noisereduce here)
             audio = self.audio_loudness_control(audio)
         except Exception as e:
             print(f"Failed in func audio_preprocess: {e}")
         return audio
+
+    def audio_preprocess_batch(self, items):
+        """audio_preprocess of several (audio, sampling_rate) pairs; where the spectral gate is denoise_vocal's body, all clips
+        go through ONE gate launch sequence (SpectralGate.reduce_noise_batch: a clip's result does not depend on its batch)"""
+        ap = self.hp.ap
+        if ap.is_denoise_vocal or not getattr(ap, "noise_reduce", False) or len(items) < 2:
+            return [self.audio_preprocess(a, sr) for a, sr in items]
+        try:
+            heads = []
+            for a, sr in items:
+                a = self._mono_float32(a)
+                if sr != 16000:
+                    a, sr = ap.audio_resample(a, sr, 16000)
+                heads.append(self.audio_loudness_control(a))
+            return [self.audio_loudness_control(g) for g in ap.noise_gate.reduce_noise_batch(heads, 16000)]
+        except Exception as e:
+            print(f"Failed in func audio_preprocess: {e}")
+            return [self.audio_preprocess(a, sr) for a, sr in items]
 
     # ---- segmentation parsers ----------------------------------------------------------------
     def od_result_parser(self, od_result, sd_result={}, is_single=False, output_overlap=True):
@@ -462,11 +488,12 @@ class TargetDiarization:
 
     def _infer(self, wav_file, target_file, sampling_rate, is_single, output_target_audio):
         wav, sr = self.read_audio(wav_file, sampling_rate)
-        audio = self.audio_preprocess(wav, sr)
         target_embedding = None
-        if target_file is not None:
+        if target_file is None:
+            audio = self.audio_preprocess(wav, sr)
+        else:
             tw, tsr = self.read_audio(target_file, sampling_rate)
-            tgt = self.audio_preprocess(tw, tsr)
+            audio, tgt = self.audio_preprocess_batch([(wav, sr), (tw, tsr)])
             v = self.vad(tgt)
             if v:
                 tgt = self.split_audio_by_time(tgt, v[0][0], v[-1][1])
