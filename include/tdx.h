@@ -598,6 +598,42 @@ int tdx_ngate_forward(tdx_ngate* h, const float* x_dev, long n_total, const int6
                       float* tap_mag_dev, float* tap_smooth_dev, float* tap_mask_dev, float* tap_msmooth_dev, void* workspace_dev,
                       size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * N11  emotion2vec — replaces funasr's `AutoModel(model=emotion_model_dir)` + `self.emotion(wav, granularity="utterance",
+ *      extract_embedding=False)`   ASRProcessor.py:277-283, :945.  A data2vec 2.0 audio encoder and a linear head, fp32,
+ *      restated from upstream (parity with iic/emotion2vec_plus_large is unpinned).
+ *      Clip normalisation (x - mean) / sqrt(var + 1e-5) (digital silence gives zeros); n_conv strided convolutions without
+ *      bias, each followed by LayerNorm over the C channels and erf-GELU; LayerNorm + Linear C -> D; x + P(x) with P =
+ *      pos_layers x [Conv1d(D, D, pos_k, groups pos_groups) -> LayerNorm without affine -> GELU]; E learned prefix rows; a
+ *      LayerNorm, then prenet_depth + depth post-LN blocks with head width 64 whose scores carry the symmetric ALiBi bias
+ *      -slope_h max(alibi_scale_h, 0) |i - j| between frames and none to or from a prefix row; outputs: the T frame rows
+ *      [B][T][D], their mean [B][D], softmax(head(mean)) [B][n_classes] — each optional (NULL).
+ *      The blob holds the tensors under the short names of targetdiarization_amd/emotion.py PARAM_NAMES: conv.{i}.weight,
+ *      conv.{i}.ln.{weight,bias}, proj.ln.*, proj.*, pos.{l}.{weight,bias}, extra_tokens, alibi_scale, prenet.norm.*,
+ *      prenet.blocks.{l}.* and blocks.{l}.* with attn.qkv, attn.proj, norm1, mlp.fc1, mlp.fc2, norm2, head.*; shapes are strict
+ *      and a tensor nobody asked for is an error.  create refuses D != 64 H, D % pos_groups != 0 and a group width that is not
+ *      a multiple of 4 (or above 64), C not a multiple of 64 in [64, 1024], each with its own message.
+ *      A launch takes B clips of the same length N; T = tdx_emo2v_frames(h, N) must be >= 1 (N >= 400 with the published
+ *      kernels).  forward_taps also returns (each NULL or a buffer): the projection [B][T][D], x + P(x) [B][T][D], and the
+ *      qkv [B][S][3 D] and attention output [B][S][D] of the first block, S = E + T.
+ * ---------------------------------------------------------------------------------- */
+typedef struct tdx_emo2v tdx_emo2v;
+typedef struct tdx_emo2v_config {
+    int32_t C, D, H, E, prenet_depth, depth, n_conv;
+    int32_t conv_k[8], conv_s[8];
+    int32_t pos_layers, pos_k, pos_groups, n_classes;
+    int32_t reserved[4];
+} tdx_emo2v_config;
+int tdx_emo2v_create(const tdx_emo2v_config* cfg, const void* weights_blob, size_t blob_bytes, int device, tdx_emo2v** out);
+int tdx_emo2v_destroy(tdx_emo2v* h);
+long tdx_emo2v_frames(const tdx_emo2v* h, long N);
+size_t tdx_emo2v_workspace_bytes(const tdx_emo2v* h, int B, long N);
+int tdx_emo2v_forward(tdx_emo2v* h, const float* wav_dev, int B, long N, float* feats_dev, float* emb_dev, float* scores_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
+int tdx_emo2v_forward_taps(tdx_emo2v* h, const float* wav_dev, int B, long N, float* feats_dev, float* emb_dev, float* scores_dev,
+                           float* tap_proj_dev, float* tap_pos_dev, float* tap_qkv_dev, float* tap_attn_dev, void* workspace_dev,
+                           size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

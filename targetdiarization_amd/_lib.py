@@ -29,6 +29,12 @@ class WhisperConfig(C.Structure):
                 ("dec_layers", C.c_int32), ("dec_ffn", C.c_int32), ("vocab", C.c_int32), ("gelu", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class Emo2vConfig(C.Structure):
+    _fields_ = [("C", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("E", C.c_int32), ("prenet_depth", C.c_int32), ("depth", C.c_int32),
+                ("n_conv", C.c_int32), ("conv_k", C.c_int32 * 8), ("conv_s", C.c_int32 * 8), ("pos_layers", C.c_int32), ("pos_k", C.c_int32),
+                ("pos_groups", C.c_int32), ("n_classes", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 _lib = None
 
 # every symbol include/tdx.h declares: (restype, argtypes)
@@ -150,6 +156,12 @@ SIGNATURES = {
     "tdx_ngate_workspace_bytes": (_sz, [_vp, C.c_long]),
     "tdx_ngate_forward": (_i, [_vp, _fp, C.c_long, _vp, _vp, _i, C.c_long, C.c_double, _i, _i, C.c_float, C.c_float, C.c_float, _fp,
                                _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "tdx_emo2v_create": (_i, [C.POINTER(Emo2vConfig), _vp, _sz, _i, C.POINTER(_vp)]),
+    "tdx_emo2v_destroy": (_i, [_vp]),
+    "tdx_emo2v_frames": (C.c_long, [_vp, C.c_long]),
+    "tdx_emo2v_workspace_bytes": (_sz, [_vp, _i, C.c_long]),
+    "tdx_emo2v_forward": (_i, [_vp, _fp, _i, C.c_long, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "tdx_emo2v_forward_taps": (_i, [_vp, _fp, _i, C.c_long, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
 }
 
 

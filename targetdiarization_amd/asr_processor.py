@@ -22,7 +22,8 @@ class ASRProcessor:
                  punc_state_dict=None, punc_vocab=None, vad_state_dict=None, vad_cmvn=None,
                  sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None,
                  whisper_state_dict=None, whisper_config=None, whisper_token_list=None, whisper_tokenizer=None, whisper_generation_config=None,
-                 whisper_engine: str = "whisper_finetune", whisper_alignment_heads=None):
+                 whisper_engine: str = "whisper_finetune", whisper_alignment_heads=None,
+                 emotion_state_dict=None, emotion_config=None, emotion_labels=None):
         self.is_asr = is_asr
         self.verbose_log = verbose_log
         self.ap = ap
@@ -37,6 +38,17 @@ class ASRProcessor:
             except Exception as e:
                 self.is_vad = False
                 print(f"Failed to load FunASR VAD model: {e}")
+        self.is_emotion = is_emotion
+        self.emotion = None
+        if is_emotion:                                   # ASRProcessor.py:277-283: load, or print and switch the feature off
+            try:
+                from .emotion import build_emotion
+                self.emotion = build_emotion(emotion_state_dict, emotion_config, emotion_labels, emotion_model_dir, cuda_device)
+                if self.emotion is None:
+                    raise FileNotFoundError(f"no emotion_state_dict, and {emotion_model_dir!r} is not a directory holding model.pt")
+            except Exception as e:
+                self.is_emotion = False
+                print(f"Failed to load Modelscope emotion detection model: {e}")
         self.decoder = decoder
         self.punctuation = punctuation
         if punctuation is None and punc_state_dict is not None:      # ASRProcessor.py:261-268: load, or print and switch the feature off
@@ -186,6 +198,53 @@ class ASRProcessor:
                         base_name = os.path.abspath(output_folder).replace("\\", "/").split("/")[-1]
                     self.ap.write_to_file(output_path=f"{output_folder}/{base_name}_{i}.{output_format}", audio_data=audio_clip, sampling_rate=sampling_rate)
         return value_sec if format_to_sec else value
+
+    # ASRProcessor.py:935-973
+    def emotion_detection(self, wav_file, output_emotion_only: bool = False):
+        """16 kHz float32 audio, or a list of clips -> [{"key", "cls", "emotion", "label_score"}, ...]; with output_emotion_only
+        the emotion of the single clip, or the list of emotions.  `self.emotion(...)` (:945) is the device emotion2vec
+        (emotion.Emotion2vec); a list goes through one call, bucketed by length."""
+        if self.verbose_log:
+            print("\nRunning module: emotion_detection")
+        result_list = []
+        if not self.is_emotion or self.emotion is None:
+            print("Modelscope emotion detection model hasn't been loaded. Return empty result.")
+            return "" if output_emotion_only else result_list
+        clips = []
+        for w in (wav_file if isinstance(wav_file, list) else [wav_file]):
+            if isinstance(w, str):
+                if not hasattr(self.ap, "read_audio"):
+                    raise ValueError("emotion_detection: pass 16 kHz float32 numpy audio (file decoding is outside the MI355X hot path)")
+                audio_data, sampling_rate = self.ap.read_audio(w)
+                if sampling_rate != 16000:
+                    audio_data, _ = self.ap.audio_resample(audio_data=audio_data, orig_sr=sampling_rate, target_sr=16000)
+                w = self.ap.audio_to_mono(audio_data)
+            elif isinstance(w, bytes):
+                if not hasattr(self.ap, "raw_bytes_to_ndarray"):
+                    raise ValueError("emotion_detection: pass 16 kHz float32 numpy audio (byte decoding is outside the MI355X hot path)")
+                w = self.ap.raw_bytes_to_ndarray(audio_bytes=w)
+            clips.append(np.asarray(w, dtype=np.float32).reshape(-1))
+        res = self.emotion(clips, granularity="utterance", extract_embedding=False)
+        for r in res:
+            key = r["key"]
+            labels = r["labels"]
+            scores = [round(score, 6) for score in r["scores"]]
+            top_results = sorted(zip(labels, scores), key=lambda x: x[1], reverse=True)
+            emotion = top_results[0][0].split("/")[-1].strip()
+            score = top_results[0][1]
+            if score >= 0.95 and emotion not in ["excited"]:
+                if emotion in ["fearful", "disgusted", "sad", "angry"]:
+                    emotion_cls = "negative"
+                else:
+                    emotion_cls = "positive"
+            else:
+                emotion_cls = "neutral"
+            result_list.append({"key": key, "cls": emotion_cls, "emotion": emotion, "label_score": top_results})
+        if output_emotion_only:
+            if len(result_list) == 1:
+                return result_list[0]["emotion"]
+            return [result["emotion"] for result in result_list]
+        return result_list
 
     def asr_detection(self, wav_file, language: str = "auto", prompt: str = "", asr_engine: str = "paraformer", no_punc: bool = False,
                       output_text_only: bool = False, output_raw_result: bool = False):

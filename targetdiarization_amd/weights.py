@@ -1025,3 +1025,135 @@ def recipe_whisper_state_dict(seed: int, cfg) -> "OrderedDict[str, torch.Tensor]
             v = 0.08 * n
         out[name] = v.to(torch.float32).contiguous()
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# emotion2vec (funasr `Emotion2vec`: a data2vec 2.0 audio encoder + a linear head; iic/emotion2vec_plus_large behind the
+# reference's emotion_detection, ASRProcessor.py:277-283).  [upstream-recall]: no checkpoint and no funasr here, the parameter
+# names below are restated from fairseq's data2vec 2.0 / funasr and are unpinned.  EMOTION2VEC_NAMES is the ONE table that
+# says where a tensor lives upstream: (name in the TDXW blob, upstream name, what is added to the blob's index to get the
+# upstream one).  {n} is a layer / block index.
+# ---------------------------------------------------------------------------------------
+_E2V_AUDIO = "modality_encoders.AUDIO."
+EMOTION2VEC_NAMES = (
+    ("conv.{n}.weight", _E2V_AUDIO + "local_encoder.conv_layers.{n}.0.weight", 0),
+    ("conv.{n}.ln.weight", _E2V_AUDIO + "local_encoder.conv_layers.{n}.2.1.weight", 0),
+    ("conv.{n}.ln.bias", _E2V_AUDIO + "local_encoder.conv_layers.{n}.2.1.bias", 0),
+    ("proj.ln.weight", _E2V_AUDIO + "project_features.1.weight", 0),
+    ("proj.ln.bias", _E2V_AUDIO + "project_features.1.bias", 0),
+    ("proj.weight", _E2V_AUDIO + "project_features.2.weight", 0),
+    ("proj.bias", _E2V_AUDIO + "project_features.2.bias", 0),
+    ("pos.{n}.weight", _E2V_AUDIO + "relative_positional_encoder.{n}.0.weight", 1),
+    ("pos.{n}.bias", _E2V_AUDIO + "relative_positional_encoder.{n}.0.bias", 1),
+    ("extra_tokens", _E2V_AUDIO + "extra_tokens", 0),
+    ("alibi_scale", _E2V_AUDIO + "alibi_scale", 0),
+    ("prenet.norm.weight", _E2V_AUDIO + "context_encoder.norm.weight", 0),
+    ("prenet.norm.bias", _E2V_AUDIO + "context_encoder.norm.bias", 0),
+    ("prenet.blocks.{n}.", _E2V_AUDIO + "context_encoder.blocks.{n}.", 0),      # + a leaf of EMOTION2VEC_BLOCK_LEAVES
+    ("blocks.{n}.", "blocks.{n}.", 0),
+    ("head.weight", "proj.weight", 0),
+    ("head.bias", "proj.bias", 0),
+)
+EMOTION2VEC_BLOCK_LEAVES = ("attn.qkv", "attn.proj", "norm1", "mlp.fc1", "mlp.fc2", "norm2")
+EMOTION2VEC_IGNORED = (_E2V_AUDIO + "decoder.", "_ema.")       # and any key that contains "mask_emb"
+EMOTION2VEC_STRIDES = (5, 2, 2, 2, 2, 2, 2)
+EMOTION2VEC_CONFIG_KEYS = ("C", "D", "H", "E", "prenet_depth", "depth", "conv_kernels", "conv_strides", "pos_layers", "pos_k", "pos_groups",
+                           "n_classes")
+
+
+def emotion2vec_upstream_name(blob_pattern: str, n: int = 0, leaf: str = "") -> str:
+    """the upstream name of the tensor the blob calls `blob_pattern` (an entry of EMOTION2VEC_NAMES) at index n"""
+    for pat, up, off in EMOTION2VEC_NAMES:
+        if pat == blob_pattern:
+            return up.replace("{n}", str(n + off)) + leaf
+    raise KeyError(blob_pattern)
+
+
+def emotion2vec_config(cfg=None, **kw) -> dict:
+    """The emotion2vec sizes as one dict (EMOTION2VEC_CONFIG_KEYS); the defaults are iic/emotion2vec_plus_large (C 512, D 1024,
+    16 heads, 10 extra tokens, 4 + 24 blocks, kernels (10, 3, 3, 3, 3, 2, 2), strides (5, 2, 2, 2, 2, 2, 2), 5 positional layers
+    of 19 taps in 16 groups, 9 classes)."""
+    c = dict(cfg or {})
+    c.update(kw)
+    D = int(c.get("D", 1024))
+    kernels = tuple(int(k) for k in c.get("conv_kernels", (10, 3, 3, 3, 3, 2, 2)))
+    strides = c.get("conv_strides")
+    strides = tuple(int(s) for s in strides) if strides is not None else EMOTION2VEC_STRIDES[:len(kernels)]
+    if len(strides) != len(kernels):
+        raise ValueError(f"emotion2vec_config: {len(kernels)} conv kernels but {len(strides)} strides")
+    return {"C": int(c.get("C", 512)), "D": D, "H": int(c.get("H", D // 64)), "E": int(c.get("E", 10)),
+            "prenet_depth": int(c.get("prenet_depth", 4)), "depth": int(c.get("depth", 24)), "conv_kernels": kernels, "conv_strides": strides,
+            "pos_layers": int(c.get("pos_layers", 5)), "pos_k": int(c.get("pos_k", 19)), "pos_groups": int(c.get("pos_groups", 16)),
+            "n_classes": int(c.get("n_classes", 9))}
+
+
+def emotion2vec_frames(n: int, cfg=None) -> int:
+    """frames of a clip of n samples: L' = floor((L - k) / s) + 1 per conv layer (0 when the clip is too short)"""
+    c = emotion2vec_config(cfg)
+    L = int(n)
+    for k, s in zip(c["conv_kernels"], c["conv_strides"]):
+        if L < k:
+            return 0
+        L = (L - k) // s + 1
+    return L
+
+
+def emotion2vec_param_shapes(cfg=None) -> "OrderedDict[str, tuple]":
+    """the state dict of funasr's Emotion2vec in upstream names (without the pre-training decoder, the EMA copy and mask_emb)"""
+    c = emotion2vec_config(cfg)
+    C, D = c["C"], c["D"]
+    s = OrderedDict()
+    up = emotion2vec_upstream_name
+    for i, k in enumerate(c["conv_kernels"]):
+        s[up("conv.{n}.weight", i)] = (C, 1 if i == 0 else C, k)
+        s[up("conv.{n}.ln.weight", i)] = (C,)
+        s[up("conv.{n}.ln.bias", i)] = (C,)
+    s[up("proj.ln.weight")] = (C,)
+    s[up("proj.ln.bias")] = (C,)
+    s[up("proj.weight")] = (D, C)
+    s[up("proj.bias")] = (D,)
+    for l in range(c["pos_layers"]):
+        s[up("pos.{n}.weight", l)] = (D, D // c["pos_groups"], c["pos_k"])
+        s[up("pos.{n}.bias", l)] = (D,)
+    s[up("extra_tokens")] = (1, c["E"], D)
+    s[up("alibi_scale")] = (1, 1, c["H"], 1, 1)
+    s[up("prenet.norm.weight")] = (D,)
+    s[up("prenet.norm.bias")] = (D,)
+    for pat, nb in (("prenet.blocks.{n}.", c["prenet_depth"]), ("blocks.{n}.", c["depth"])):
+        for b in range(nb):
+            for leaf, shp in (("attn.qkv", (3 * D, D)), ("attn.proj", (D, D)), ("norm1", (D,)), ("mlp.fc1", (4 * D, D)), ("mlp.fc2", (D, 4 * D)),
+                              ("norm2", (D,))):
+                s[up(pat, b, leaf + ".weight")] = shp
+                s[up(pat, b, leaf + ".bias")] = (shp[0],)
+    s[up("head.weight")] = (c["n_classes"], D)
+    s[up("head.bias")] = (c["n_classes"],)
+    return s
+
+
+def recipe_emotion2vec_state_dict(seed: int = 0, cfg=None, head_gain: float = 4.0) -> "OrderedDict[str, torch.Tensor]":
+    """Deterministic fp32 weights in the upstream layout, from the Philox recipe: matrices and kernels u / sqrt(fan_in) (the
+    head times head_gain: a flat head would make the top-1 test say nothing), biases 0.1 u, LayerNorm gains 1 + 0.2 u.  Upstream
+    initialises alibi_scale to 1 and extra_tokens to 0; here alibi_scale lies in [0.5, 2] with head 1 NEGATIVE (the clamp at 0
+    is exercised) and extra_tokens are 0.5 u (a zero prefix would hide indexing errors)."""
+    c = emotion2vec_config(cfg)
+    out = OrderedDict()
+    for name, shape in emotion2vec_param_shapes(c).items():
+        n = int(np.prod(shape))
+        u = torch.from_numpy(philox_uniform("emotion2vec:" + name, n, seed)).reshape(shape)
+        leaf = name.rsplit(".", 1)[-1]
+        is_norm = any(t in name for t in (".norm.", ".norm1.", ".norm2.", ".2.1.", "project_features.1."))
+        if name.endswith("alibi_scale"):
+            v = 1.25 + 0.75 * u
+            if c["H"] > 1:
+                v.reshape(-1)[1] = -0.5
+        elif name.endswith("extra_tokens"):
+            v = 0.5 * u
+        elif is_norm:
+            v = (1.0 + 0.2 * u) if leaf == "weight" else 0.1 * u
+        elif leaf == "bias":
+            v = 0.1 * u
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            v = u * float((head_gain if name == "proj.weight" else 1.0) / np.sqrt(fan_in))
+        out[name] = v.to(torch.float32).contiguous()
+    return out
