@@ -634,6 +634,49 @@ int tdx_emo2v_forward_taps(tdx_emo2v* h, const float* wav_dev, int B, long N, fl
                            float* tap_proj_dev, float* tap_pos_dev, float* tap_qkv_dev, float* tap_attn_dev, void* workspace_dev,
                            size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Probabilistic YIN pitch tracking (librosa.pyin, restated from upstream; parity with the package is unpinned) — DESIGN 8.21.
+ *      x_dev holds the clips back to back (n_total floats).  The table has one entry of 4 int64 per clip: off (index of the
+ *      clip's sample 0 in x_dev), n (samples), frame0 (first row of the clip in every per-frame output: the frames of the clips
+ *      before it), T (frames: 1 + n / hop_length with center, 1 + (n - frame_length) / hop_length without).  It is passed twice
+ *      with equal contents: table_host is validated, table_dev is what the kernels read.  The parameters are the host-side
+ *      plan of the call (pitch.pyin_plan): periods, bins and the transition width are NOT recomputed here.  tables_dev, fp64:
+ *          thr[n_thresholds + 1] | beta_probs[n_thresholds] | cumulative beta_probs [n_thresholds + 1] |
+ *          Boltzmann factor (1 - e^-l) / (1 - e^(-l n)) [n_lags + 1] | e^(-l pos) [n_lags + 1] |
+ *          log triangle [width] | -log of the sum of each source row of the band [n_pitch_bins]
+ *      with n_lags = max_period - min_period + 1; tables_len is their total length.  Outputs per frame: states (int32; below
+ *      n_pitch_bins voiced, bin = state % n_pitch_bins) and voiced_prob.  Taps (NULL, or all frames of the call): yin
+ *      [frames][n_lags], shifts [frames][n_lags], obs [frames][2 n_pitch_bins].  Three launches whatever nclips; the result of a
+ *      clip does not depend on the other clips of the call.  The difference function is summed directly in fp32 (upstream: FFT
+ *      autocorrelation with values below 1e-6 flushed to 0); the padding is zeros.
+ *      Limits, each rejected with its own message before the device is touched: frame_length 4 .. 8192, 1 <= win_length <
+ *      frame_length, max_period <= min(frame_length - win_length - 1, 4096), max_period - min_period >= 2, 2 n_pitch_bins <= 4096,
+ *      width odd and <= n_pitch_bins, n_thresholds 1 .. 254, 1 <= nclips <= 65535, every table entry.
+ *
+ *      tdx_pyin_viterbi: the decoding stage alone over obs_dev [T][2 n_pitch_bins] (probabilities, fp32); only n_pitch_bins,
+ *      width, the three logs and the last two tables are read, the layout of tables_dev is the same.  tdx_pyin_forward runs
+ *      the same kernel.  The path is the dense librosa.sequence.viterbi's: scores in fp64, first maximum on ties.
+ * ---------------------------------------------------------------------------------- */
+typedef struct tdx_pyin tdx_pyin;
+typedef struct tdx_pyin_params {
+    int32_t frame_length, win_length, hop_length, center;
+    int32_t min_period, max_period, n_pitch_bins, n_thresholds;
+    int32_t width;
+    int32_t reserved[3];
+    double sr, fmin, bins_per_octave;                  /* bins_per_octave = 12 * ceil(1 / resolution) */
+    double no_trough_prob;
+    double log_stay, log_switch, log_init_unvoiced;    /* log(1 - switch_prob + tiny), log(switch_prob + tiny), log(1 / n_pitch_bins + tiny) */
+} tdx_pyin_params;
+int tdx_pyin_create(int device, tdx_pyin** out);
+int tdx_pyin_destroy(tdx_pyin* h);
+size_t tdx_pyin_workspace_bytes(const tdx_pyin* h, const tdx_pyin_params* params, long total_frames);
+int tdx_pyin_forward(tdx_pyin* h, const float* x_dev, long n_total, const int64_t* table_host, const int64_t* table_dev, int nclips,
+                     const tdx_pyin_params* params, const double* tables_dev, size_t tables_len, int* states_dev, float* voiced_prob_dev,
+                     float* tap_yin_dev, float* tap_shifts_dev, float* tap_obs_dev, void* workspace_dev, size_t workspace_bytes,
+                     void* stream);
+int tdx_pyin_viterbi(tdx_pyin* h, const float* obs_dev, long T, const tdx_pyin_params* params, const double* tables_dev, size_t tables_len,
+                     int* states_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,13 @@ class Emo2vConfig(C.Structure):
                 ("pos_groups", C.c_int32), ("n_classes", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class PyinParams(C.Structure):
+    _fields_ = [("frame_length", C.c_int32), ("win_length", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32),
+                ("min_period", C.c_int32), ("max_period", C.c_int32), ("n_pitch_bins", C.c_int32), ("n_thresholds", C.c_int32),
+                ("width", C.c_int32), ("reserved", C.c_int32 * 3), ("sr", C.c_double), ("fmin", C.c_double), ("bins_per_octave", C.c_double),
+                ("no_trough_prob", C.c_double), ("log_stay", C.c_double), ("log_switch", C.c_double), ("log_init_unvoiced", C.c_double)]
+
+
 _lib = None
 
 # every symbol include/tdx.h declares: (restype, argtypes)
@@ -162,6 +169,11 @@ SIGNATURES = {
     "tdx_emo2v_workspace_bytes": (_sz, [_vp, _i, C.c_long]),
     "tdx_emo2v_forward": (_i, [_vp, _fp, _i, C.c_long, _fp, _fp, _fp, _vp, _sz, _vp]),
     "tdx_emo2v_forward_taps": (_i, [_vp, _fp, _i, C.c_long, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "tdx_pyin_create": (_i, [_i, C.POINTER(_vp)]),
+    "tdx_pyin_destroy": (_i, [_vp]),
+    "tdx_pyin_workspace_bytes": (_sz, [_vp, C.POINTER(PyinParams), C.c_long]),
+    "tdx_pyin_forward": (_i, [_vp, _fp, C.c_long, _vp, _vp, _i, C.POINTER(PyinParams), _vp, _sz, _vp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "tdx_pyin_viterbi": (_i, [_vp, _fp, C.c_long, C.POINTER(PyinParams), _vp, _sz, _vp, _vp, _sz, _vp]),
 }
 
 

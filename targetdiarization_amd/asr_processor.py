@@ -27,6 +27,8 @@ class ASRProcessor:
         self.is_asr = is_asr
         self.verbose_log = verbose_log
         self.ap = ap
+        self.cuda_device = cuda_device
+        self.pitch = None                                # pitch.Pyin, created by the first f0_compute
         self.is_vad = is_vad
         self.vad = None
         if is_vad:                                       # ASRProcessor.py:253-260: load, or print and switch the feature off
@@ -245,6 +247,29 @@ class ASRProcessor:
                 return result_list[0]["emotion"]
             return [result["emotion"] for result in result_list]
         return result_list
+
+    # ASRProcessor.py:1003-1010
+    def f0_compute(self, wav_file, sampling_rate: int = 16000, fmin: float = 50.0, fmax: float = 300.0):
+        """audio (any rate, float) -> f0 in Hz, one value per 512-sample hop, NaN where the frame is unvoiced:
+        `librosa.pyin(audio_data, fmin=fmin, fmax=fmax, sr=sampling_rate)[0]` (:1009) on the device (pitch.Pyin).  No device,
+        a failed init or parameters pyin rejects: the reason is printed and an empty float64 array returned."""
+        if isinstance(wav_file, str):
+            if not (hasattr(self.ap, "read_audio") and hasattr(self.ap, "audio_to_mono")):
+                raise ValueError("f0_compute: pass float numpy audio (file decoding is outside the MI355X hot path)")
+            audio_data, sampling_rate = self.ap.read_audio(wav_file)
+            audio_data = self.ap.audio_to_mono(audio_data)
+        else:
+            audio_data = wav_file
+        try:
+            if self.pitch is None:
+                if self.cuda_device is None or int(self.cuda_device) < 0:
+                    raise RuntimeError("no device (cuda_device < 0); there is no CPU path")
+                from .pitch import Pyin
+                self.pitch = Pyin(f"cuda:{int(self.cuda_device)}")
+            return self.pitch.pyin(np.asarray(audio_data), fmin=fmin, fmax=fmax, sr=sampling_rate)[0]
+        except Exception as e:
+            print(f"Failed in f0_compute: {e}")
+            return np.zeros(0, dtype=np.float64)
 
     def asr_detection(self, wav_file, language: str = "auto", prompt: str = "", asr_engine: str = "paraformer", no_punc: bool = False,
                       output_text_only: bool = False, output_raw_result: bool = False):
