@@ -2,8 +2,9 @@
  *
  * NOT part of the product boundary (include/tdx.h / libtdx.so).  libtdx_diag.so is a separate library built
  * from csrc/diag.hip over the same kernel headers; tests/test_gpu_h3.py checks the numerics of the split-f16 x3
- * core through it and tools/ time its variants.  Same conventions as tdx.h (device pointers, void* stream,
- * 0 = ok). */
+ * core through it, tests/test_gpu_gemm_f32.py the operand modes and tile maps of the fp32 MFMA core,
+ * tests/test_gpu_epilogues.py the shared epilogues, tests/test_gpu_attention_gate.py the gated attention launch,
+ * and tools/ time its variants.  Same conventions as tdx.h (device pointers, void* stream, 0 = ok). */
 #ifndef TDX_TEST_H
 #define TDX_TEST_H
 
@@ -36,6 +37,36 @@ int tdx_linear_variant(const float* a_dev, const float* w_dev, int M, int N, int
  * EpiBiasRes(N) from the arguments.  act: 0 none, 1 relu, 2 relu20, 3 silu, 4 leaky_relu(0.01).  Npad % 128 == 0, K % 32 == 0. */
 int tdx_linear_epi(const float* a_dev, const float* w_dev, const float* bias_or_null, const float* res_or_null, float* out_dev,
                    int M, int Npad, int nreal, int K, int act, void* stream);
+
+/* the fp32-MFMA core (csrc/gemm.hpp gemm_f32_kernel / launch_gemm) in every operand mode the product issues, with a plain store:
+ *   out[z*strideO + m*ldo + n] = sum over segments, sum over k of A_seg[z][m][k] * B_seg[z][k][n]      for n < nreal.
+ * One K segment as GemmSeg has it: A row-major [M][lda] (K contiguous) or, with a_kmajor, [K][lda] (M contiguous); B row-major
+ * [N][ldb] (a weight) or, with b_kmajor, [K][ldb].  Batch z = z1 * zdiv + z2 reads A + z1*strideA + z2*strideA2 (B likewise); rows
+ * k >= ktotal - z2*kchunk of a K-major operand count as zero (row-major operands ignore kchunk / ktotal). */
+typedef struct tdx_gemm_seg {
+    const float* A;
+    const float* B;
+    long lda, ldb, strideA, strideB, strideA2, strideB2;
+    int K, zdiv, kchunk, ktotal;
+} tdx_gemm_seg;
+/* a_kmajor / b_kmajor / paired pick the template instance: <F,F>, <T,F>, <F,T>, <T,T>, and PAIRED on <F,F> and <F,T>.  PAIRED: N pair
+ * columns; column c pairs B column c with B column pair_off + c and stores them to out columns c and pair_off + c (c < nreal; n_valid
+ * unused).  Otherwise columns >= n_valid are skipped by the kernel, and nreal <= n_valid <= N.  plan_or_null (host, 5 ints) receives
+ * what launch_gemm planned for this launch: map_mode, mp, gw, tiles_m, tiles_n.
+ * Refused (TDX_E_INVALID): K % 32, N % 128 (PAIRED: N % 64), lda % 4, ldb % 4, strides % 4, M < 1, M % 128 with a_kmajor (no row
+ * guard on that path), zdiv < 1, ktotal - z2*kchunk < 1 for a z2 of the launch with a K-major operand (the clamped row would be -1),
+ * a null pointer.  The caller owns the extents: a row-major B needs N (PAIRED: pair_off + N) rows, a K-major B 128-column reads from
+ * every valid row (32 floats of slack behind the last row when ldb < 128), a K-major A needs M % 128 == 0 columns. */
+int tdx_gemm_f32(int a_kmajor, int b_kmajor, int paired, const tdx_gemm_seg* seg0, const tdx_gemm_seg* seg1_or_null, int M, int N,
+                 int n_valid, int pair_off, int batches, float* out_dev, long ldo, long strideO, int nreal, int* plan_or_null,
+                 void* stream);
+/* CONV = true, the implicit GEMM of the 3x3 (ntaps 9, zero padding 1) and 1x1 (ntaps 1) NHWC convolutions, set up as conv_gemm
+ * (eres2net.hip, wespeaker.hip) and head_conv (campplus.hip) do: a [B*Hin*Win][lda], w [N][ntaps*cin] (tap-major), out row
+ * m = (b, ho, wo) reads input row (b, ho*stride + dy, wo*(stride_w ? stride_w : stride) + dx).  out[m*ldo + n] for n < nreal.
+ * Refused: ntaps outside {1, 9}, cin % 32, lda % 4, lda < cin, N % 128, nreal > n_valid, n_valid > N, a null pointer. */
+int tdx_gemm_f32_conv(const float* a_dev, long lda, const float* w_dev, int B, int Hin, int Win, int Hout, int Wout, int stride,
+                      int stride_w, int ntaps, int cin, int N, int n_valid, float* out_dev, long ldo, int nreal, int* plan_or_null,
+                      void* stream);
 
 /* the gated attention launch of a FLASH layer exactly as tdx_mf2_forward issues it (csrc/mf2_attention.hpp attention_core_h3 with the
  * planes-out gate): o = (att_u*v) * sigmoid(att_v*u) as row-major split-f16 planes oP [B*S][4E bytes] with one scale os and one sum of

@@ -204,6 +204,14 @@ def lib():
 
 # every symbol include/tdx_test.h declares (libtdx_diag.so: test hooks, never used by the product path)
 _l = C.c_long
+
+
+class GemmSeg(C.Structure):
+    """tdx_gemm_seg of include/tdx_test.h: one K segment of a tdx_gemm_f32 launch."""
+    _fields_ = [("A", _vp), ("B", _vp), ("lda", _l), ("ldb", _l), ("strideA", _l), ("strideB", _l), ("strideA2", _l), ("strideB2", _l),
+                ("K", _i), ("zdiv", _i), ("kchunk", _i), ("ktotal", _i)]
+
+
 DIAG_SIGNATURES = {
     "tdx_diag_last_error": (C.c_char_p, []),
     "tdx_h3_split_rows": (_i, [_vp, _l, _vp, _vp, _l, _i, _vp]),
@@ -213,6 +221,8 @@ DIAG_SIGNATURES = {
     "tdx_h3_gemm_variant": (_i, [_vp] * 6 + [_i] * 4 + [_vp]),
     "tdx_linear_variant": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "tdx_linear_epi": (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
+    "tdx_gemm_f32": (_i, [_i] * 3 + [C.POINTER(GemmSeg)] * 2 + [_i] * 5 + [_vp, _l, _l, _i, C.POINTER(_i), _vp]),
+    "tdx_gemm_f32_conv": (_i, [_vp, _l, _vp] + [_i] * 11 + [_vp, _l, _i, C.POINTER(_i), _vp]),
     "tdx_attn_gate_planes_workspace_bytes": (_sz, [_i, _i, _i]),
     "tdx_attn_gate_planes": (_i, [_vp] * 7 + [_i] * 5 + [_vp] * 5 + [_sz, _vp]),
     "tdx_fill_bench": (_i, [_i, _vp, _l, _i, _i, _vp, _vp]),

@@ -1,9 +1,12 @@
 // diag.hip — libtdx_diag.so: test hooks and timing diagnostics of the GEMM cores (declared in include/tdx_test.h).
 // NOT part of the product library: libtdx.so exports only what include/tdx.h declares.  Used by tests/test_gpu_h3.py
-// (numerics of the split-f16 x3 core in all operand modes), tests/test_gpu_attention_gate.py (the gated attention launch exactly as
-// the model issues it) and by tools/ (timing variants, operand fill rates).
+// (numerics of the split-f16 x3 core in all operand modes), tests/test_gpu_gemm_f32.py (the fp32 MFMA core in every operand mode and
+// on both tile maps), tests/test_gpu_epilogues.py (the shared epilogue family), tests/test_gpu_attention_gate.py (the gated attention
+// launch exactly as the model issues it) and by tools/ (timing variants, operand fill rates).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/tdx.h"
@@ -20,6 +23,61 @@ int linear_epi(const float* a, const float* w, const float* bias, const float* r
     if (res) return linear_f32(a, K, w, M, Npad, K, EpiBiasRes<Act>{bias, res, out, Npad}, st);
     if (nreal < Npad) return linear_f32(a, K, w, M, Npad, K, EpiBiasActN<Act>{bias, out, Npad, nreal}, st);
     return linear_f32(a, K, w, M, Npad, K, EpiBiasAct<Act>{bias, out, Npad}, st);
+}
+
+// test-local plain stores of the fp32 core's operand-mode hooks (tdx_gemm_f32 / tdx_gemm_f32_conv): out[z][m][n] = v for n < nreal.
+// (EpiStoreZ also stores the zero accumulators of the column tiles the kernel skipped, which would hide a wrongly skipped tile.)
+struct EpiPlainN {
+    float* out; long ld, strideZ; int nreal;
+    __device__ EpiNone col(int, int) const { return EpiNone{}; }
+    __device__ EpiNone row(int, int) const { return EpiNone{}; }
+    __device__ void store(int z, int m, int n, float v, EpiNone, EpiNone) const {
+        if (n < nreal) out[(long)z * strideZ + (long)m * ld + n] = v;
+    }
+};
+struct EpiPlainPair {      // PAIRED: v0 -> column c, v1 -> column pair_off + c, for c < nreal
+    float* out; long ld, strideZ; int nreal, pair_off;
+    __device__ EpiNone col(int, int) const { return EpiNone{}; }
+    __device__ EpiNone row(int, int) const { return EpiNone{}; }
+    __device__ void store2(int z, int m, int c, float v0, float v1, EpiNone, EpiNone) const {
+        if (c < nreal) {
+            float* o = out + (long)z * strideZ + (long)m * ld;
+            o[c] = v0; o[pair_off + c] = v1;
+        }
+    }
+};
+
+void plan_out(const GemmArgs& g, int* plan) {
+    if (plan) { plan[0] = g.map_mode; plan[1] = g.mp; plan[2] = g.gw; plan[3] = g.tiles_m; plan[4] = g.tiles_n; }
+}
+template <bool PAIRED, bool CONV>
+void plan_of(GemmArgs g, int batches, int* plan) {       // what launch_gemm is about to compute for g
+    plan_gemm<PAIRED, CONV>(g, batches);
+    plan_out(g, plan);
+}
+
+const char* seg_error(const tdx_gemm_seg& s, bool a_kmajor, bool b_kmajor, int batches) {
+    if (!s.A || !s.B) return "null operand";
+    if (s.K < 32 || s.K % 32) return "need K >= 32, K % 32 == 0";
+    if (s.lda < 1 || s.ldb < 1 || s.lda % 4 || s.ldb % 4) return "need lda % 4 == 0, ldb % 4 == 0";
+    if (s.strideA < 0 || s.strideB < 0 || s.strideA2 < 0 || s.strideB2 < 0 || s.strideA % 4 || s.strideB % 4 || s.strideA2 % 4 || s.strideB2 % 4)
+        return "need batch strides >= 0 and % 4 == 0 (16-byte loads)";
+    if (s.zdiv < 1 || s.kchunk < 0) return "need zdiv >= 1, kchunk >= 0";
+    // K-major operands read row min(k, kvalid - 1): kvalid = ktotal - z2 * kchunk must stay >= 1 for the largest z2 of the launch
+    if ((a_kmajor || b_kmajor) && (long)s.ktotal - (long)(std::min(s.zdiv, batches) - 1) * s.kchunk < 1)
+        return "need ktotal - z2 * kchunk >= 1 for every z2 of a K-major operand";
+    return nullptr;
+}
+GemmSeg seg_of(const tdx_gemm_seg& s) {
+    GemmSeg r = make_seg(s.A, s.lda, s.B, s.ldb, s.K, s.strideA, s.strideB, s.ktotal);
+    r.zdiv = s.zdiv; r.strideA2 = s.strideA2; r.strideB2 = s.strideB2; r.kchunk = s.kchunk; r.ktotal = s.ktotal;
+    return r;
+}
+template <bool A_KMAJOR, bool B_KMAJOR, bool PAIRED, bool CONV, class Epi>
+int run_gemm_f32(const GemmArgs& g, int batches, Epi e, int* plan, hipStream_t st) {
+    plan_of<PAIRED, CONV>(g, batches, plan);
+    const hipError_t r = launch_gemm<A_KMAJOR, B_KMAJOR, PAIRED, false, Epi, 0, CONV>(g, batches, e, st);
+    return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
 }
 }  // namespace
 
@@ -55,6 +113,60 @@ int tdx_linear_epi(const float* a, const float* w, const float* bias, const floa
     case 4: return linear_epi<ActLeaky<1, 100>>(a, w, bias, res, out, M, Npad, nreal, K, st);
     default: return linear_epi<ActNone>(a, w, bias, res, out, M, Npad, nreal, K, st);
     }
+}
+
+// ---- the fp32 core in every operand mode the product issues: tests/test_gpu_gemm_f32.py ------------------------------------------
+// Both hooks build a GemmArgs from their arguments and call launch_gemm itself with a plain store (EpiPlainN / EpiPlainPair above).
+// They refuse whatever the kernel cannot run safely; the buffers' extents are the caller's business (see include/tdx_test.h).
+
+int tdx_gemm_f32(int a_kmajor, int b_kmajor, int paired, const tdx_gemm_seg* seg0, const tdx_gemm_seg* seg1_or_null, int M, int N, int n_valid,
+                 int pair_off, int batches, float* out, long ldo, long strideO, int nreal, int* plan_or_null, void* stream) {
+    const auto bad = [](const char* m) { return tdx::fail(TDX_E_INVALID, std::string("tdx_gemm_f32: ") + m); };
+    if (!seg0 || !out) return bad("null argument");
+    if (paired && a_kmajor) return bad("PAIRED with a K-major A is no product configuration");
+    if (M < 1 || batches < 1) return bad("need M >= 1, batches >= 1");
+    if (a_kmajor && M % 128) return bad("need M % 128 == 0 with a K-major A (that path has no row guard)");
+    if (paired ? (N < 64 || N % 64) : (N < 128 || N % 128)) return bad("need N % 128 == 0 (PAIRED: N % 64 == 0)");
+    if (paired ? (nreal < 1 || nreal > N || pair_off < 0 || pair_off % 4) : (nreal < 1 || nreal > n_valid || n_valid > N))
+        return bad("need 1 <= nreal <= n_valid <= N (PAIRED: 1 <= nreal <= N, pair_off >= 0, pair_off % 4 == 0)");
+    if (ldo < 1 || strideO < 0) return bad("need ldo >= 1, strideO >= 0");
+    for (const tdx_gemm_seg* s : {seg0, seg1_or_null})
+        if (s)
+            if (const char* m = seg_error(*s, a_kmajor != 0, b_kmajor != 0, batches)) return bad(m);
+    GemmArgs g = make_args(M, N, seg_of(*seg0));
+    if (seg1_or_null) { g.seg[1] = seg_of(*seg1_or_null); g.nseg = 2; }
+    if (!paired) g.n_valid = n_valid;
+    g.pair_off = paired ? pair_off : 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (paired) {
+        const EpiPlainPair e{out, ldo, strideO, nreal, pair_off};
+        return b_kmajor ? run_gemm_f32<false, true, true, false>(g, batches, e, plan_or_null, st)
+                        : run_gemm_f32<false, false, true, false>(g, batches, e, plan_or_null, st);
+    }
+    const EpiPlainN e{out, ldo, strideO, nreal};
+    if (a_kmajor && b_kmajor) return run_gemm_f32<true, true, false, false>(g, batches, e, plan_or_null, st);
+    if (a_kmajor) return run_gemm_f32<true, false, false, false>(g, batches, e, plan_or_null, st);
+    if (b_kmajor) return run_gemm_f32<false, true, false, false>(g, batches, e, plan_or_null, st);
+    return run_gemm_f32<false, false, false, false>(g, batches, e, plan_or_null, st);
+}
+
+// CONV set the way conv_gemm (eres2net.hip, wespeaker.hip) and head_conv (campplus.hip) set it
+int tdx_gemm_f32_conv(const float* a, long lda, const float* w, int B, int Hin, int Win, int Hout, int Wout, int stride, int stride_w, int ntaps,
+                      int cin, int N, int n_valid, float* out, long ldo, int nreal, int* plan_or_null, void* stream) {
+    const auto bad = [](const char* m) { return tdx::fail(TDX_E_INVALID, std::string("tdx_gemm_f32_conv: ") + m); };
+    if (!a || !w || !out) return bad("null argument");
+    if (ntaps != 1 && ntaps != 9) return bad("need ntaps 1 or 9");
+    if (cin < 32 || cin % 32) return bad("need cin >= 32, cin % 32 == 0");
+    if (lda < cin || lda % 4) return bad("need lda >= cin, lda % 4 == 0");
+    if (N < 128 || N % 128) return bad("need N % 128 == 0");
+    if (nreal < 1 || nreal > n_valid || n_valid > N) return bad("need 1 <= nreal <= n_valid <= N");
+    if (B < 1 || Hin < 1 || Win < 1 || Hout < 1 || Wout < 1 || stride < 1 || stride_w < 0) return bad("need positive extents, stride >= 1, stride_w >= 0");
+    if ((long)B * Hout * Wout > 0x7fffffffL || (long)B * Hin * Win > 0x7fffffffL) return bad("rows beyond int");
+    if (ldo < 1) return bad("need ldo >= 1");
+    GemmArgs g = make_args(B * Hout * Wout, N, make_seg(a, lda, w, (long)ntaps * cin, cin));
+    g.n_valid = n_valid;
+    g.cv_Hin = Hin; g.cv_Win = Win; g.cv_Hout = Hout; g.cv_Wout = Wout; g.cv_stride = stride; g.cv_stride_w = stride_w; g.cv_ntaps = ntaps; g.cv_cin = cin;
+    return run_gemm_f32<false, false, false, true>(g, 1, EpiPlainN{out, ldo, 0, nreal}, plan_or_null, (hipStream_t)stream);
 }
 
 // diagnostics for the split-f16 x3 core: tests/test_gpu_h3.py, tools/h3_test.py

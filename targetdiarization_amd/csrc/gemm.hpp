@@ -430,8 +430,10 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_f32_kernel(GemmArgs g, E
     if (m0 + GEMM_BM <= g.M) epilogue(std::false_type{}); else epilogue(std::true_type{});
 }
 
-template <bool A_KMAJOR, bool B_KMAJOR, bool PAIRED, bool SHIFT, class Epi, int VARIANT = 0, bool CONV = false>
-inline hipError_t launch_gemm(GemmArgs g, int batches, Epi epi, hipStream_t st) {
+// Host side of a launch: fills the block -> tile map of g (tiles_m, tiles_n, batches, map_mode, mp, gw) and returns the grid.
+// launch_gemm is its only product caller; tests/test_gpu_gemm_f32.py reads the plan back through libtdx_diag.so.
+template <bool PAIRED, bool CONV>
+inline dim3 plan_gemm(GemmArgs& g, int batches) {
     g.tiles_m = (g.M + GEMM_BM - 1) / GEMM_BM;
     g.tiles_n = PAIRED ? g.N / (GEMM_BN / 2) : g.N / GEMM_BN;
     g.batches = batches;
@@ -453,6 +455,12 @@ inline hipError_t launch_gemm(GemmArgs g, int batches, Epi epi, hipStream_t st) 
         g.mp = 0; g.gw = 1;
         grid = dim3(8 * ((batches + 7) / 8) * g.tiles_m * g.tiles_n, 1, 1);
     }
+    return grid;
+}
+
+template <bool A_KMAJOR, bool B_KMAJOR, bool PAIRED, bool SHIFT, class Epi, int VARIANT = 0, bool CONV = false>
+inline hipError_t launch_gemm(GemmArgs g, int batches, Epi epi, hipStream_t st) {
+    const dim3 grid = plan_gemm<PAIRED, CONV>(g, batches);
     hipLaunchKernelGGL((gemm_f32_kernel<A_KMAJOR, B_KMAJOR, PAIRED, SHIFT, Epi, VARIANT, CONV>), grid, dim3(GEMM_THREADS), 0, st, g, epi);
     return hipGetLastError();
 }
