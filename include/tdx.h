@@ -677,6 +677,69 @@ int tdx_pyin_forward(tdx_pyin* h, const float* x_dev, long n_total, const int64_
 int tdx_pyin_viterbi(tdx_pyin* h, const float* obs_dev, long T, const tdx_pyin_params* params, const double* tables_dev, size_t tables_len,
                      int* states_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Phase-vocoder time stretch, pitch shift and EQ match (librosa 0.10's stft / phase_vocoder / istft and resample's role,
+ * restated from upstream; parity with the package is unpinned) — AudioProcessor.py:452-546, DESIGN 8.22.
+ *      Transforms: periodic Hann of n_fft points, center=True with ZERO padding of n_fft / 2 on both sides, T = 1 + n / hop
+ *      frames.  tdx_pvoc_stretch is fixed at n_fft 2048, hop 512 (librosa's defaults); the others take (n_fft, hop) under the
+ *      rule of the GEMM core: n_fft a multiple of 128 in [128, 4096] (the synthesis GEMM's N in tiles of 128, its K n_fft + 32),
+ *      hop a multiple of 4 (the analysis rows overlap with pitch hop and are read 16 bytes at a time) with n_fft / 16 <= hop <=
+ *      n_fft (the gather sums at most 16 frames per sample).  Anything else is TDX_E_INVALID with its own message.  create
+ *      builds the bases of n_fft 2048 in double; tdx_pvoc_prepare builds those of another n_fft (allocates and copies: not for
+ *      a captured stream), and a call with an n_fft nobody prepared is TDX_E_INVALID.
+ *      Spectra that cross the ABI are complex64 [C][frames][n_fft / 2 + 1] (re, im interleaved), frames major.
+ *
+ *      tdx_pvoc_stretch: x_dev [C][n] -> y_dev [C][length].  The plan (effects.stretch_plan) is steps = arange(0, T, rate) in
+ *      float64: idx[t] = int(steps[t]) (int32, passed twice: idx_host is validated, idx_dev is read by the kernel), alpha[t] =
+ *      steps[t] mod 1 (fp64), Tout entries.  Output frame t: mag = (1 - alpha) |D[idx]| + alpha |D[idx + 1]| in fp32, columns
+ *      >= T being exact zeros (magnitude 0, angle 0); phase acc[t] with acc[0] = angle(D[0]), acc[t + 1] = acc[t] + phi_k +
+ *      wrap(angle(D[idx + 1]) - angle(D[idx]) - phi_k), phi_k = 2 pi k hop / n_fft, wrap(d) = d - 2 pi rint(d / 2 pi): all in
+ *      fp64 (atan2, wrap, running sum, sincos).  The running sum is cut into segments of TDX_PVOC_SEG frames, TDX_PVOC_SLOTS of
+ *      them per sweep, so its order depends on the clip alone.  Synthesis: inverse DFT x Hann, then every sample is the sum of
+ *      the entries of the frames that cover it (first frame first) divided by the sum of Hann^2 of the same frames unless that
+ *      is <= FLT_MIN; min(Tout, ceil((length + n_fft) / hop)) frames are used and samples beyond them are 0.
+ *      Taps (NULL or complex64): the analysis spectrum [C][T][1025], the stretched spectrum [C][Tout][1025].
+ *      Channel c of a call is computed exactly as a call with that channel alone.
+ *      tdx_pvoc_vocode: the phase vocoder alone on D_dev complex64 [T][nbin] -> out_dev [Tout][nbin], n_fft = 2 (nbin - 1).
+ *      tdx_pvoc_istft: D_dev complex64 [T][n_fft / 2 + 1] -> y_dev [length]; length < 0 means hop (T - 1).
+ *      tdx_pvoc_eq_match: gain[k] = clip(mean_t |S_tgt[k]| / mean_t |S_src[k]|, 0.1, 10) with the means summed in fp64 in a
+ *      fixed order; a source mean of exactly 0 gives gain 10 (the bin's output is 0 either way; upstream: 0 / 0 = NaN through
+ *      the whole clip).  y_dev [hop (T_src - 1)] = istft(S_src gain).  The target is samples (tgt_dev, n_tgt) or a spectrum
+ *      (tgt_stft_dev complex64 [T_tgt][n_fft / 2 + 1]), one of the two.  Taps (NULL or): the source spectrum, the two mean
+ *      curves (fp64 [n_fft / 2 + 1]) and the gain (fp32).
+ *      tdx_pvoc_workspace_bytes(h, n_fft, hop, C, n, Tout): stretch (2048, 512, C, n, Tout); istft (n_fft, hop, 1, 0, T);
+ *      eq_match (n_fft, hop, 1, max(n_src, n_tgt), 0).  0 for arguments outside the limits.
+ *      Limits, each rejected with its own message before the device is touched: 1 <= C <= 65535, 1 <= n, length <= 2^36, at
+ *      most 2e9 frame rows per call, 1 <= Tout <= 2^30, every plan entry in [0, T).
+ *
+ *      tdx_resample_sinc: resampling by any ratio rho = target / orig in [1/64, 64], no handle.  n_out =
+ *      tdx_resample_sinc_length(n_in, rho) = ceil(n_in rho).  Output m lies at the input position p = m / rho (fp64); with c =
+ *      min(1, rho) and H = 10 / c, h(d) = c sinc(c d) I0(5 sqrt(1 - (d / H)^2)) / I0(5) for |d| <= H — the continuous form of
+ *      the Kaiser(5.0) design with 10 zero crossings that tdx_resample_poly's filters sample — and y[m] = sum_j h(j - p) x[j] /
+ *      sum_j h(j - p) over all integer j in the window, samples outside the clip being zero.  Taps and sums in fp64 (I0 by
+ *      its power series).  x_dev [C][n_in] -> y_dev [C][n_store]: the first min(n_out, n_store) samples, zeros after them
+ *      (librosa.util.fix_length in the same launch).
+ * ---------------------------------------------------------------------------------- */
+#define TDX_PVOC_SEG 16
+#define TDX_PVOC_SLOTS 32
+typedef struct tdx_pvoc tdx_pvoc;
+int tdx_pvoc_create(int device, tdx_pvoc** out);
+int tdx_pvoc_destroy(tdx_pvoc* h);
+int tdx_pvoc_prepare(tdx_pvoc* h, int n_fft);
+size_t tdx_pvoc_workspace_bytes(const tdx_pvoc* h, int n_fft, int hop, int C, long n, long Tout);
+int tdx_pvoc_stretch(tdx_pvoc* h, const float* x_dev, int C, long n, const int32_t* idx_host, const int32_t* idx_dev, const double* alpha_dev,
+                     int Tout, long length, float* y_dev, float* tap_spec_dev, float* tap_stretched_dev, void* workspace_dev,
+                     size_t workspace_bytes, void* stream);
+int tdx_pvoc_vocode(tdx_pvoc* h, const float* D_dev, int nbin, int T, int hop, const int32_t* idx_host, const int32_t* idx_dev,
+                    const double* alpha_dev, int Tout, float* out_dev, void* stream);
+int tdx_pvoc_istft(tdx_pvoc* h, const float* D_dev, int T, int n_fft, int hop, long length, float* y_dev, void* workspace_dev,
+                   size_t workspace_bytes, void* stream);
+int tdx_pvoc_eq_match(tdx_pvoc* h, const float* src_dev, long n_src, const float* tgt_dev, long n_tgt, const float* tgt_stft_dev, int T_tgt,
+                      int n_fft, int hop, float* y_dev, float* tap_spec_dev, double* tap_mean_src_dev, double* tap_mean_tgt_dev,
+                      float* tap_gain_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+long tdx_resample_sinc_length(long n_in, double ratio);
+int tdx_resample_sinc(const float* x_dev, int C, long n_in, double ratio, float* y_dev, long n_store, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

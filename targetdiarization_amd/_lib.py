@@ -174,6 +174,16 @@ SIGNATURES = {
     "tdx_pyin_workspace_bytes": (_sz, [_vp, C.POINTER(PyinParams), C.c_long]),
     "tdx_pyin_forward": (_i, [_vp, _fp, C.c_long, _vp, _vp, _i, C.POINTER(PyinParams), _vp, _sz, _vp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
     "tdx_pyin_viterbi": (_i, [_vp, _fp, C.c_long, C.POINTER(PyinParams), _vp, _sz, _vp, _vp, _sz, _vp]),
+    "tdx_pvoc_create": (_i, [_i, C.POINTER(_vp)]),
+    "tdx_pvoc_destroy": (_i, [_vp]),
+    "tdx_pvoc_prepare": (_i, [_vp, _i]),
+    "tdx_pvoc_workspace_bytes": (_sz, [_vp, _i, _i, _i, C.c_long, C.c_long]),
+    "tdx_pvoc_stretch": (_i, [_vp, _fp, _i, C.c_long, _vp, _vp, _vp, _i, C.c_long, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "tdx_pvoc_vocode": (_i, [_vp, _fp, _i, _i, _i, _vp, _vp, _vp, _i, _fp, _vp]),
+    "tdx_pvoc_istft": (_i, [_vp, _fp, _i, _i, _i, C.c_long, _fp, _vp, _sz, _vp]),
+    "tdx_pvoc_eq_match": (_i, [_vp, _fp, C.c_long, _fp, C.c_long, _fp, _i, _i, _i, _fp, _fp, _vp, _vp, _fp, _vp, _sz, _vp]),
+    "tdx_resample_sinc_length": (C.c_long, [C.c_long, C.c_double]),
+    "tdx_resample_sinc": (_i, [_fp, _i, C.c_long, C.c_double, _fp, C.c_long, _vp]),
 }
 
 

@@ -20,6 +20,11 @@ noisereduce's non-stationary spectral gate on the device (`noise_gate.SpectralGa
 flag `noise_reduce=True`; with the default False the audio is returned unchanged, as before.  The third-party algorithm is
 restated from upstream (package parity unpinned); where the smoothed magnitude is exactly 0 the mask is 0 (upstream: NaN).
 
+`audio_stretch` (:468-499), `audio_pitch` (:452-465) and `eq_match` (:502-546) run librosa's phase-vocoder time stretch, its pitch
+shift and the reference's spectral-mean equaliser on the device (`effects.PhaseVocoder`, csrc/pvoc.hip), created by the first
+call; the audiostretchy branch of `audio_stretch` is not taken, the resampler behind the pitch shift is the project's own, and
+a file name as the EQ target is refused.  They never raise: the reason is printed and the input returned.
+
 Out of scope here: enhancer, file I/O — those flags are accepted and degrade to "module skipped" exactly like
 the reference does when a package is disabled.
 """
@@ -107,6 +112,7 @@ class AudioProcessor:
             except Exception as e:
                 print(f"Failed to init noise gate: {e}")
                 self.noise_reduce = False
+        self.effects = None                              # effects.PhaseVocoder, created by the first audio_stretch / audio_pitch / eq_match
         self.restorer = None
         self.is_restore_audio = is_restore_audio
         if self.is_restore_audio and (restorer_state_dict is not None or os.path.isdir(self.restorer_weights_folder)):
@@ -308,6 +314,107 @@ class AudioProcessor:
 
     def _dev(self):
         return torch.device("cuda:0" if self.device == "cuda" else self.device)
+
+    def _effects(self):
+        if self.effects is None:
+            if str(self.device) == "cpu":
+                raise _lib.TdxError("no device (cuda_device=-1); there is no CPU path")
+            from .effects import PhaseVocoder
+            self.effects = PhaseVocoder(self._dev())
+        return self.effects
+
+    @staticmethod
+    def _channels_first(audio_data, who):
+        a = np.asarray(audio_data)
+        if a.ndim not in (1, 2) or a.size == 0:
+            raise ValueError(f"{who}: the audio must be [n] or [n, C] and not empty, got shape {a.shape}")
+        return np.ascontiguousarray(a.T, dtype=np.float32)
+
+    # AudioProcessor.py:452-465
+    def audio_pitch(self, audio_data: np.ndarray, sampling_rate: int, pitch_semitone: float):
+        """`librosa.effects.pitch_shift(audio_data, sr=sampling_rate, n_steps=pitch_semitone)` per channel on the device:
+        [n] -> [n], [n, C] -> [n, C] float32.  A failure prints its reason and returns the input."""
+        if self.verbose_log:
+            print("\nRunning module: audio_pitch")
+            print(f"Pitch semitone: {pitch_semitone}")
+        if pitch_semitone == 0.0:
+            if self.verbose_log:
+                print("Pitch semitone is zero. Skip.")
+            return audio_data
+        try:
+            out = self._effects().pitch_shift(self._channels_first(audio_data, "audio_pitch"), sampling_rate, float(pitch_semitone))
+            return np.ascontiguousarray(out.T)
+        except Exception as e:
+            print(f"Failed in audio_pitch: {e}")
+            return audio_data
+
+    # AudioProcessor.py:468-499 (the librosa branch; the int16 round trip of the audiostretchy branch is not taken)
+    def audio_stretch(self, audio_data: np.ndarray, sampling_rate: int, speed_factor: float):
+        """`librosa.effects.time_stretch(audio_data, rate=speed_factor)` per channel on the device: [n] -> [round(n / speed_factor)],
+        [n, C] -> [n', C] float32.  A negative factor or a failure prints its reason and returns the input."""
+        if self.verbose_log:
+            print("\nRunning module: audio_stretch")
+            print(f"Speed factor: {speed_factor}")
+        if speed_factor == 0.0:
+            if self.verbose_log:
+                print("Speed factor is zero. Skip.")
+            return audio_data
+        if not speed_factor > 0:
+            print(f"Speed factor {speed_factor} is not positive. Skip.")
+            return audio_data
+        try:
+            out = self._effects().time_stretch(self._channels_first(audio_data, "audio_stretch"), float(speed_factor))
+            return np.ascontiguousarray(out.T)
+        except Exception as e:
+            print(f"Failed in audio_stretch: {e}")
+            return audio_data
+
+    # AudioProcessor.py:502-546
+    def eq_match(self, source_audio: np.ndarray, target_audio, source_sampling_rate: int = 16000, target_sampling_rate: int = 16000,
+                 n_fft: int = 2048, hop_length: int = 512):
+        """The reference's EQ match of a mono source to a target given as an ndarray or as a dict with `array` / `stft` /
+        `sampling_rate` / `n_fft` / `hop_length` (:511-518).  A file name as the target (audio or .pkl: there is no file decoding
+        here, and this library does not unpickle files), a 2-D source or a failure prints its reason and returns the source."""
+        target_stft = None
+        if isinstance(target_audio, str):
+            print("eq_match: a file name as the target is not supported (pass the array, or the dict of a target pickle); source returned unchanged")
+            return source_audio
+        if isinstance(target_audio, dict):
+            target_dict = target_audio.copy()
+            target_audio = target_dict.get("array", None)
+            target_stft = target_dict.get("stft", None)
+            target_sampling_rate = target_dict.get("sampling_rate", 16000)
+            n_fft = target_dict.get("n_fft", 2048)
+            hop_length = target_dict.get("hop_length", 512)
+        if hop_length > n_fft:
+            hop_length = int(n_fft / 4)
+        if self.verbose_log:
+            print("\nRunning module: eq_match")
+            print(f"FFT window size: {n_fft}")
+            print(f"Hop length: {hop_length}")
+        if np.asarray(source_audio).ndim != 1:
+            print(f"eq_match: the source must be mono [n], got shape {np.asarray(source_audio).shape}; source returned unchanged")
+            return source_audio
+        try:
+            fx = self._effects()
+            source = np.asarray(source_audio, dtype=np.float32)
+            if source_sampling_rate < target_sampling_rate:
+                source, _ = self.audio_resample(source, source_sampling_rate, target_sampling_rate)
+            elif source_sampling_rate > target_sampling_rate:
+                if target_audio is None and target_stft is not None:
+                    target_audio = fx.istft(target_stft, hop_length=hop_length)          # :529 (n_fft from the bins, as upstream)
+                    target_stft = None
+                target_audio, _ = self.audio_resample(np.asarray(target_audio, dtype=np.float32), target_sampling_rate, source_sampling_rate)
+            if target_stft is None:
+                out = fx.eq_match(source, target=target_audio, n_fft=n_fft, hop_length=hop_length)
+            else:
+                out = fx.eq_match(source, target_stft=target_stft, n_fft=n_fft, hop_length=hop_length)
+            if source_sampling_rate < target_sampling_rate:
+                out, _ = self.audio_resample(out, target_sampling_rate, source_sampling_rate)
+            return out
+        except Exception as e:
+            print(f"Failed in eq_match: {e}")
+            return source_audio
 
     def init_mdx_model(self):
         """:224-241: the block STFT geometry (hop by `quality`, dim_t = 2**8 frames)"""
