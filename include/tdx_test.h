@@ -79,6 +79,14 @@ int tdx_attn_gate_planes(const float* quad_q, const float* lin_q, const float* q
                          const float* u, const float* freqs, int B, int S, int E, int h3a, int swap, void* oP_dev, float* os_dev,
                          float* oss_dev, float* kvu_out_dev, void* workspace, size_t workspace_bytes, void* stream);
 
+/* the host-built "window x DFT" GEMM operands (csrc/dft_basis.hpp fill_dft_analysis / fill_dft_synthesis) into a HOST buffer the caller
+ * has zeroed; no device is touched: tests/test_dft_basis_host.py.  Analysis: out [rows][ld], re X_k in row k, im X_k in row im_row0 + k
+ * (k < nbin), columns n < N, periodic Hann window if `hann`, else none.  Synthesis (c2r of the bins k < nbin): out [N][ld], re weights in
+ * column k, im weights in column im_off + k; gain_kind 0: 1 / N, 1: hann[n] / 4, 2: hann[n] / N.  Refused: nbin > N / 2 + 1, im blocks that
+ * overlap the re blocks or leave the buffer, ld < N (analysis). */
+int tdx_diag_dft_analysis(int N, int nbin, long im_row0, long ld, long rows, int hann, float* out_host);
+int tdx_diag_dft_synthesis(int N, int nbin, long im_off, long ld, int gain_kind, float* out_host);
+
 /* per-CU operand fill rates (tools/fill_bench*.py) */
 int tdx_fill_bench(int mode, const void* src_dev, long bytes_per_block, int blocks, int iters, float* sink_dev, void* stream);
 int tdx_fill_bench2(int mode, const void* src_dev, int stride, int blocks, int iters, float* sink_dev, void* stream);

@@ -235,6 +235,8 @@ DIAG_SIGNATURES = {
     "tdx_gemm_f32_conv": (_i, [_vp, _l, _vp] + [_i] * 11 + [_vp, _l, _i, C.POINTER(_i), _vp]),
     "tdx_attn_gate_planes_workspace_bytes": (_sz, [_i, _i, _i]),
     "tdx_attn_gate_planes": (_i, [_vp] * 7 + [_i] * 5 + [_vp] * 5 + [_sz, _vp]),
+    "tdx_diag_dft_analysis": (_i, [_i, _i, _l, _l, _l, _i, _vp]),
+    "tdx_diag_dft_synthesis": (_i, [_i, _i, _l, _l, _i, _vp]),
     "tdx_fill_bench": (_i, [_i, _vp, _l, _i, _i, _vp, _vp]),
     "tdx_fill_bench2": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
     "tdx_fill_bench3": (_i, [_vp, _l, _i, _l, _i, _i, _i, _vp, _vp]),

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/tdx.h"
+#include "dft_basis.hpp"
 #include "epilogues.hpp"
 
 using namespace tdx;
@@ -263,22 +264,14 @@ int tdx_apollo_create(int num_layers, const void* blob, size_t blob_bytes, int d
     h->L = num_layers;
     // analysis / synthesis DFT bases (double, exact angle reduction), periodic hann window
     {
-        std::vector<double> w(NFFT);
-        for (int k = 0; k < NFFT; ++k) w[k] = 0.5 - 0.5 * cos(2.0 * M_PI * k / NFFT);
+        const std::vector<double> w = tdx::hann_periodic(NFFT);
         h->bana = ld.room((size_t)KP * KP);
         h->bsyn = ld.room((size_t)KP * KP);
         h->w2 = ld.room(NFFT);
         for (int k = 0; k < NFFT; ++k) ld.host[h->w2 + k] = (float)(w[k] * w[k]);
-        for (int f = 0; f < NBIN; ++f) {
-            const double cre = (f == 0 || f == NBIN - 1) ? 1.0 : 2.0, cim = (f == 0 || f == NBIN - 1) ? 0.0 : 2.0;
-            for (int k = 0; k < NFFT; ++k) {
-                const double ang = 2.0 * M_PI * (double)(((long)f * k) % NFFT) / NFFT, c = cos(ang), s = sin(ang);
-                ld.host[h->bana + (size_t)f * KP + k] = (float)(w[k] * c);                    // Re X_f = sum w x cos
-                ld.host[h->bana + (size_t)(NBIN + f) * KP + k] = (float)(-w[k] * s);          // Im X_f = -sum w x sin
-                ld.host[h->bsyn + (size_t)k * KP + f] = (float)(cre * c * w[k] / NFFT);       // C2R: Im of bins 0 and 441 ignored
-                ld.host[h->bsyn + (size_t)k * KP + NBIN + f] = (float)(-cim * s * w[k] / NFFT);
-            }
-        }
+        tdx::fill_dft_analysis(ld.host.data() + h->bana, NFFT, NBIN, NBIN, KP, w.data());      // im rows at NBIN + f
+        // C2R with hann / NFFT; Im of bins 0 and 441 ignored: this image has always held -0 there (it was -0.0 * sin * w / NFFT)
+        tdx::fill_dft_synthesis(ld.host.data() + h->bsyn, NFFT, NBIN, NBIN, KP, tdx::divided(w, NFFT).data(), -0.f);
     }
     // band-split input: Wt[11 b + k][c] = W_b[c][k] * gain_b[k], bias [80][256]
     h->Wt = ld.room((size_t)FEAT * AD);

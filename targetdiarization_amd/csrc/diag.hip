@@ -2,7 +2,8 @@
 // NOT part of the product library: libtdx.so exports only what include/tdx.h declares.  Used by tests/test_gpu_h3.py
 // (numerics of the split-f16 x3 core in all operand modes), tests/test_gpu_gemm_f32.py (the fp32 MFMA core in every operand mode and
 // on both tile maps), tests/test_gpu_epilogues.py (the shared epilogue family), tests/test_gpu_attention_gate.py (the gated attention
-// launch exactly as the model issues it) and by tools/ (timing variants, operand fill rates).
+// launch exactly as the model issues it), tests/test_dft_basis_host.py (the host-built DFT bases, no device) and by tools/ (timing
+// variants, operand fill rates).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +12,7 @@
 
 #include "../../include/tdx.h"
 #include "../../include/tdx_test.h"
+#include "dft_basis.hpp"
 #include "epilogues.hpp"
 #include "mf2_attention.hpp"
 
@@ -167,6 +169,23 @@ int tdx_gemm_f32_conv(const float* a, long lda, const float* w, int B, int Hin, 
     g.n_valid = n_valid;
     g.cv_Hin = Hin; g.cv_Win = Win; g.cv_Hout = Hout; g.cv_Wout = Wout; g.cv_stride = stride; g.cv_stride_w = stride_w; g.cv_ntaps = ntaps; g.cv_cin = cin;
     return run_gemm_f32<false, false, false, true>(g, 1, EpiPlainN{out, ldo, 0, nreal}, plan_or_null, (hipStream_t)stream);
+}
+
+// ---- the host-built DFT bases (dft_basis.hpp): tests/test_dft_basis_host.py.  Host buffers, no device call.  The fillers write
+// their entries and nothing else: `out` is the caller's zeroed image, [rows][ld] for the analysis and [N][ld] for the synthesis.
+int tdx_diag_dft_analysis(int N, int nbin, long im_row0, long ld, long rows, int hann, float* out) {
+    if (!out || N < 1 || nbin < 1 || nbin > N / 2 + 1 || im_row0 < nbin || im_row0 + nbin > rows || ld < N)
+        return tdx::fail(TDX_E_INVALID, "tdx_diag_dft_analysis: need 1 <= nbin <= N / 2 + 1, nbin <= im_row0, im_row0 + nbin <= rows, ld >= N");
+    fill_dft_analysis(out, N, nbin, (size_t)im_row0, (size_t)ld, hann ? hann_periodic(N).data() : nullptr);
+    return TDX_OK;
+}
+// gain_kind: 0 = 1 / N (MDX), 1 = hann / 4 (the spectral gate), 2 = hann / N (the phase vocoder, Apollo)
+int tdx_diag_dft_synthesis(int N, int nbin, long im_off, long ld, int gain_kind, float* out) {
+    if (!out || N < 1 || nbin < 1 || nbin > N / 2 + 1 || im_off < nbin || im_off + nbin > ld || gain_kind < 0 || gain_kind > 2)
+        return tdx::fail(TDX_E_INVALID, "tdx_diag_dft_synthesis: need 1 <= nbin <= N / 2 + 1, nbin <= im_off, im_off + nbin <= ld, gain_kind in 0..2");
+    const std::vector<double> gain = gain_kind == 0 ? std::vector<double>(N, 1.0 / N) : divided(hann_periodic(N), gain_kind == 1 ? 4.0 : (double)N);
+    fill_dft_synthesis(out, N, nbin, (size_t)im_off, (size_t)ld, gain.data());
+    return TDX_OK;
 }
 
 // diagnostics for the split-f16 x3 core: tests/test_gpu_h3.py, tools/h3_test.py

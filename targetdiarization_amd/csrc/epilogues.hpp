@@ -20,6 +20,9 @@
 // EpiAffGate; apollo.hip EpiRow, EpiGate, EpiRowBiasSilu; pyannet.hip EpiConv; frontend.hip EpiPower, EpiLogMel, EpiSpec,
 // EpiWinFrame), and so do the one-wave LayerNorms and softmaxes: they look alike but sum in different orders, and merging
 // them moves the last bit of everything downstream.
+//
+// The host side of a GEMM's B operand lives elsewhere: weight_pack.hpp repacks the conv, BatchNorm, Linear and LSTM weights a create
+// fetched, dft_basis.hpp builds the window x DFT bases of the spectral front ends.
 #pragma once
 #include <hip/hip_runtime.h>
 

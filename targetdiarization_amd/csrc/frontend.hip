@@ -17,7 +17,7 @@
 #include "../../include/tdx.h"
 #include "gemm.hpp"
 #include "devutil.hpp"
-#include "tdx_common.hpp"
+#include "dft_basis.hpp"
 
 using namespace tdx;
 
@@ -157,16 +157,8 @@ int tdx_fbank_create(int mode, int device, tdx_fbank** out) {
     if (!out || mode < 0 || mode > 2) return tdx::fail(TDX_E_INVALID, "tdx_fbank_create: mode must be 0 (SV), 1 (ASR) or 2 (WeSpeaker)");
     tdx::Loader ld;       // (no blob: the tables are computed here, then staged and uploaded like weights)
     std::vector<float>& host = ld.host;
-    const size_t oW = 0, nW = (size_t)2 * NBIN_PAD * NF;
-    host.resize(al(nW), 0.f);
-    std::vector<double> cs(NF), sn(NF);
-    for (int i = 0; i < NF; ++i) { cs[i] = cos(2.0 * M_PI * i / NF); sn[i] = sin(2.0 * M_PI * i / NF); }
-    for (int k = 0; k <= NF / 2; ++k)
-        for (int n = 0; n < NF; ++n) {
-            const int idx = (int)(((long)k * n) % NF);
-            host[oW + (size_t)k * NF + n] = (float)cs[idx];
-            host[oW + (size_t)(NBIN_PAD + k) * NF + n] = (float)(-sn[idx]);
-        }
+    const size_t oW = ld.room((size_t)2 * NBIN_PAD * NF);      // DFT [2 * 320][512]: re rows k, im rows 320 + k, no window
+    tdx::fill_dft_analysis(host.data() + oW, NF, NF / 2 + 1, NBIN_PAD, NF, nullptr);
     // mel banks [128][320] (torchaudio get_mel_banks; last FFT bin column is zero)
     const size_t oM = host.size();
     host.resize(oM + al((size_t)128 * NBIN_PAD), 0.f);
@@ -254,35 +246,18 @@ int tdx_stft_create(int n_fft, int hop, int dim_f, int dim_t, int device, tdx_st
         dim_t % 128 || (long)hop * (dim_t - 1) <= n_fft / 2)
         return tdx::fail(TDX_E_INVALID, "tdx_stft_create: unsupported geometry (need n_fft%128==0, dim_f%64==0, dim_t%128==0)");
     const int N = n_fft, T = dim_t, chunk = hop * (dim_t - 1);
-    std::vector<double> cs(N), sn(N);
-    for (int i = 0; i < N; ++i) { cs[i] = cos(2.0 * M_PI * i / N); sn[i] = sin(2.0 * M_PI * i / N); }
     tdx::Loader ld;       // (no blob: the tables are computed here, then staged and uploaded like weights)
     std::vector<float>& host = ld.host;
     // forward: rows m = ri*dim_f + f over k=n (time):  re: cos, im: -sin
-    const size_t oWf = 0;
-    host.resize(al((size_t)2 * dim_f * N), 0.f);
-    for (int f = 0; f < dim_f; ++f)
-        for (int n = 0; n < N; ++n) {
-            const int idx = (int)(((long)f * n) % N);
-            host[oWf + (size_t)f * N + n] = (float)cs[idx];
-            host[oWf + (size_t)(dim_f + f) * N + n] = (float)(-sn[idx]);
-        }
+    const size_t oWf = ld.room((size_t)2 * dim_f * N);
+    tdx::fill_dft_analysis(host.data() + oWf, N, dim_f, dim_f, N, nullptr);
     // inverse (c2r, bins >= dim_f are zero): rows n (time) over k = ri*dim_f + f
     //   y[n] = 1/N [X0.re + 2 sum_{f>=1} (X_f.re cos - X_f.im sin)] (+ Nyquist term if dim_f covers it)
-    const size_t oWi = host.size();
-    host.resize(oWi + al((size_t)N * 2 * dim_f), 0.f);
-    for (int n = 0; n < N; ++n)
-        for (int f = 0; f < dim_f; ++f) {
-            const int idx = (int)(((long)f * n) % N);
-            const bool edge = (f == 0) || (2 * f == N);
-            const double wgt = (edge ? 1.0 : 2.0) / N;
-            host[oWi + (size_t)n * 2 * dim_f + f] = (float)(wgt * cs[idx]);
-            host[oWi + (size_t)n * 2 * dim_f + dim_f + f] = edge ? 0.f : (float)(-wgt * sn[idx]);
-        }
-    const size_t oWin = host.size();
-    host.resize(oWin + al(N), 0.f);
-    std::vector<double> w(N);
-    for (int i = 0; i < N; ++i) { w[i] = 0.5 - 0.5 * cos(2.0 * M_PI * i / N); host[oWin + i] = (float)w[i]; }   // hann, periodic
+    const size_t oWi = ld.room((size_t)N * 2 * dim_f);
+    tdx::fill_dft_synthesis(host.data() + oWi, N, dim_f, dim_f, (size_t)2 * dim_f, std::vector<double>(N, 1.0 / N).data());
+    const size_t oWin = ld.room(N);
+    const std::vector<double> w = tdx::hann_periodic(N);
+    for (int i = 0; i < N; ++i) host[oWin + i] = (float)w[i];
     const size_t oEnv = host.size();
     const int L = N + hop * (T - 1);
     host.resize(oEnv + al(L), 0.f);

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/tdx.h"
+#include "dft_basis.hpp"
 #include "epilogues.hpp"
 
 using namespace tdx;
@@ -37,6 +38,8 @@ constexpr int NFFT = 1024, HOP = 256, NBIN = 513;
 constexpr int BP = 528;                  // pitch of a bin row (columns 513.. of the spectrum halves are exact zeros)
 constexpr int NPAIR = 576;               // bins padded to the paired GEMM's 64-column tiles
 constexpr int KS = 2 * BP;               // spectrum row [re | im]: the K of the synthesis GEMM (33 x 32)
+constexpr tdx::StftGeo GEO = tdx::stft_geo(NFFT);
+static_assert(NBIN == GEO.nbin && BP == GEO.BP && NPAIR == GEO.NPAIR && KS == GEO.KS, "the kernels' constants are the shared STFT geometry");
 constexpr int XROWS = 3;                 // rows a buffer owns beyond its frames
 constexpr int SEG = 64;                  // frames per scan segment: fixed, so that the summation order depends on the buffer alone
 constexpr int SC_BINS = 16, SC_SLOTS = 64, SC_THREADS = SC_BINS * SC_SLOTS;
@@ -232,30 +235,12 @@ int tdx_ngate_create(int device, tdx_ngate** out) {
     if (!out) return tdx::fail(TDX_E_INVALID, "tdx_ngate_create: null argument");
     if (device < 0) return tdx::fail(TDX_E_INVALID, "tdx_ngate_create: device must be >= 0");
     tdx::Loader ld;       // (no blob: the bases are computed here in double, then staged and uploaded like weights)
-    std::vector<double> cs(NFFT), sn(NFFT), win(NFFT);
-    for (int i = 0; i < NFFT; ++i) {
-        cs[i] = cos(2.0 * M_PI * i / NFFT); sn[i] = sin(2.0 * M_PI * i / NFFT);
-        win[i] = 0.5 - 0.5 * cos(2.0 * M_PI * i / NFFT);                                   // hann, periodic
-    }
     // analysis [2 * 576][1024]: row k = hann * cos, row 576 + k = -hann * sin; rows of the bins 513.. are zero
-    const size_t oA = ld.room((size_t)2 * NPAIR * NFFT);
-    for (int k = 0; k < NBIN; ++k)
-        for (int n = 0; n < NFFT; ++n) {
-            const int idx = (int)(((long)k * n) % NFFT);
-            ld.host[oA + (size_t)k * NFFT + n] = (float)(win[n] * cs[idx]);
-            ld.host[oA + (size_t)(NPAIR + k) * NFFT + n] = (float)(-win[n] * sn[idx]);
-        }
     // synthesis [1024][2 * 528]: frame[n] = hann[n] / 4 * 1/1024 * sum_k w_k (re_k cos - im_k sin), w = 1 at DC and Nyquist, else 2
     // (the 1/4 and the gather's 1/384 make the overlap-add envelope: four hann^2 at hop 256 sum to 1.5 = 4 * 384 / 1024)
-    const size_t oS = ld.room((size_t)NFFT * KS);
-    for (int n = 0; n < NFFT; ++n)
-        for (int k = 0; k < NBIN; ++k) {
-            const int idx = (int)(((long)k * n) % NFFT);
-            const bool edge = k == 0 || k == NFFT / 2;
-            const double w = win[n] * 0.25 * (edge ? 1.0 : 2.0);
-            ld.host[oS + (size_t)n * KS + k] = (float)(w * cs[idx]);
-            ld.host[oS + (size_t)n * KS + BP + k] = edge ? 0.f : (float)(-w * sn[idx]);
-        }
+    const std::vector<double> win = tdx::hann_periodic(NFFT);
+    size_t oA, oS;
+    tdx::push_stft_basis(ld, GEO, win.data(), tdx::divided(win, 4.0).data(), oA, oS);
     std::unique_ptr<tdx_ngate> h(new tdx_ngate());
     TRY(ld.finish("tdx_ngate_create", false, device, h->dev));
     const float* dev = h->dev;

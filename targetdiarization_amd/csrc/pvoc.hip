@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/tdx.h"
+#include "dft_basis.hpp"
 #include "epilogues.hpp"
 
 using namespace tdx;
@@ -35,13 +36,8 @@ constexpr int MAX_NFFT = 4096, MAX_CH = 65535;
 constexpr long MAX_N = 1L << 36;
 constexpr int MAX_GRID_Y = 32768;
 
-struct Geo { int n_fft, hop, nbin, BP, NPAIR, KS, cover; };      // cover = ceil(n_fft / hop): frames over one sample, at most
-inline Geo geo(int n_fft, int hop) {
-    Geo g;
-    g.n_fft = n_fft; g.hop = hop; g.nbin = n_fft / 2 + 1; g.BP = n_fft / 2 + 16; g.NPAIR = n_fft / 2 + 64; g.KS = 2 * g.BP;
-    g.cover = (n_fft + hop - 1) / hop;
-    return g;
-}
+struct Geo : tdx::StftGeo { int hop, cover; };      // cover = ceil(n_fft / hop): frames over one sample, at most
+inline Geo geo(int n_fft, int hop) { return Geo{tdx::stft_geo(n_fft), hop, (n_fft + hop - 1) / hop}; }
 // The rule of include/tdx.h: the synthesis GEMM's N is n_fft (tiles of 128), its K is n_fft + 32; the analysis GEMM's row pitch
 // is hop (16-byte loads); the gather sums at most 16 frames per sample.
 inline const char* geo_error(int n_fft, int hop) {
@@ -258,33 +254,14 @@ struct Basis { Geo g; tdx::DevBuf dev; const float *Wa, *Ws, *win2; };
 
 int make_basis(int n_fft, int device, std::unique_ptr<Basis>& out) {
     const Geo g = geo(n_fft, n_fft / 4);
-    const int N = n_fft;
     tdx::Loader ld;       // (no blob: the bases are computed here in double, then staged and uploaded like weights)
-    std::vector<double> cs(N), sn(N), win(N);
-    for (int i = 0; i < N; ++i) {
-        cs[i] = cos(2.0 * M_PI * i / N); sn[i] = sin(2.0 * M_PI * i / N);
-        win[i] = 0.5 - 0.5 * cos(2.0 * M_PI * i / N);                                   // hann, periodic
-    }
     // analysis [2 * NPAIR][n_fft]: row k = hann * cos, row NPAIR + k = -hann * sin; rows of the bins nbin.. are zero
-    const size_t oA = ld.room((size_t)2 * g.NPAIR * N);
-    for (int k = 0; k < g.nbin; ++k)
-        for (int n = 0; n < N; ++n) {
-            const int idx = (int)(((long)k * n) % N);
-            ld.host[oA + (size_t)k * N + n] = (float)(win[n] * cs[idx]);
-            ld.host[oA + (size_t)(g.NPAIR + k) * N + n] = (float)(-win[n] * sn[idx]);
-        }
     // synthesis [n_fft][KS]: frame[n] = hann[n] / n_fft * sum_k w_k (re_k cos - im_k sin), w = 1 at DC and Nyquist, else 2
-    const size_t oS = ld.room((size_t)N * g.KS);
-    for (int n = 0; n < N; ++n)
-        for (int k = 0; k < g.nbin; ++k) {
-            const int idx = (int)(((long)k * n) % N);
-            const bool edge = k == 0 || k == N / 2;
-            const double w = win[n] / N * (edge ? 1.0 : 2.0);
-            ld.host[oS + (size_t)n * g.KS + k] = (float)(w * cs[idx]);
-            ld.host[oS + (size_t)n * g.KS + g.BP + k] = edge ? 0.f : (float)(-w * sn[idx]);
-        }
-    const size_t oW = ld.room((size_t)N);
-    for (int n = 0; n < N; ++n) ld.host[oW + n] = (float)(win[n] * win[n]);
+    const std::vector<double> win = tdx::hann_periodic(n_fft);
+    size_t oA, oS;
+    tdx::push_stft_basis(ld, g, win.data(), tdx::divided(win, n_fft).data(), oA, oS);
+    const size_t oW = ld.room((size_t)n_fft);
+    for (int n = 0; n < n_fft; ++n) ld.host[oW + n] = (float)(win[n] * win[n]);
     std::unique_ptr<Basis> b(new Basis());
     TRY(ld.finish("tdx_pvoc_prepare", false, device, b->dev));
     const float* dev = b->dev;

@@ -2,6 +2,7 @@
 // Linear and LSTM weights into the Loader's image (tdx_common.hpp).  Host code only.  The helpers take pointers, not tensor
 // names: the caller does its own ld.get(...) calls (by size or by shape, in its own order, with its own error text) and may
 // hand over nullptr for a tensor the Loader reported missing; the room is then reserved and left zero, and finish() fails.
+// (GEMM operands that come from no checkpoint — the window x DFT bases of the STFT front ends — are built by dft_basis.hpp.)
 #pragma once
 #include <cmath>
 #include <vector>

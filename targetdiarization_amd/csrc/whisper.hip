@@ -28,6 +28,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "dft_basis.hpp"
 #include "epilogues.hpp"
 
 using namespace tdx;
@@ -938,14 +939,8 @@ int tdx_whisper_create(const tdx_whisper_config* cfg, const void* blob, size_t b
 
     // window x DFT basis, rows c (re) and NBINP + c (im); the Slaney mel bank [MELP][PWP]
     size_t o_dft = ld.room((size_t)2 * NBINP * KFR), o_mel = ld.room((size_t)MELP * PWP);
+    tdx::fill_dft_analysis(ld.host.data() + o_dft, NFFT, NBIN, NBINP, KFR, tdx::hann_periodic(NFFT).data());
     {
-        const double PI = 3.14159265358979323846;
-        for (int b = 0; b < NBIN; ++b)
-            for (int k = 0; k < NFFT; ++k) {
-                const double w = 0.5 - 0.5 * std::cos(2.0 * PI * k / NFFT), a = 2.0 * PI * (double)((long)b * k % NFFT) / NFFT;
-                ld.host[o_dft + (size_t)b * KFR + k] = (float)(w * std::cos(a));
-                ld.host[o_dft + (size_t)(NBINP + b) * KFR + k] = (float)(-w * std::sin(a));
-            }
         const int nm = c.n_mels;
         std::vector<double> ff(nm + 2);
         const double m0 = hz_to_mel(0.0), m1 = hz_to_mel(8000.0);
