@@ -87,6 +87,16 @@ int tdx_attn_gate_planes(const float* quad_q, const float* lin_q, const float* q
 int tdx_diag_dft_analysis(int N, int nbin, long im_row0, long ld, long rows, int hann, float* out_host);
 int tdx_diag_dft_synthesis(int N, int nbin, long im_off, long ld, int gain_kind, float* out_host);
 
+/* the weight loader's pointer binding (csrc/tdx_common.hpp Loader::bind / resolve), on the host alone: tests/test_loaders.py.  Reads from
+ * a TDXW blob the tensors plain [n], padded [n], twice [n], lin.weight [N][K], lin.bias [N] and, for l < L, layers.l.tap [C][k] and
+ * layers.l.rows [N][K]; stages them through the binding forms (push, push with padding to npad, room + bind of 2 x twice, push_linear to
+ * [Npad][Kp] with its two binds, push_tapmajor, push_rows_padded to Kp), runs the strict checks, resolves against a host copy of the image
+ * and copies every staged tensor out through its bound pointer: plain [n] | padded [npad] | twice [n] | W [Npad][Kp] | b [Npad] | per layer
+ * tap [k][C], rows [N][Kp] (out_floats must be exactly that).  *nonnull = the bound fields that are not null on return: 5 + 2 L on
+ * success, 0 when a check fails (TDX_E_BLOB with the tensor's name in tdx_last_error). */
+int tdx_diag_loader_bind(const void* blob, size_t blob_bytes, int n, int npad, int L, int C, int k, int N, int K, int Npad, int Kp,
+                         float* out_host, size_t out_floats, int* nonnull);
+
 /* per-CU operand fill rates (tools/fill_bench*.py) */
 int tdx_fill_bench(int mode, const void* src_dev, long bytes_per_block, int blocks, int iters, float* sink_dev, void* stream);
 int tdx_fill_bench2(int mode, const void* src_dev, int stride, int blocks, int iters, float* sink_dev, void* stream);

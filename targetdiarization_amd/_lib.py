@@ -237,6 +237,7 @@ DIAG_SIGNATURES = {
     "tdx_attn_gate_planes": (_i, [_vp] * 7 + [_i] * 5 + [_vp] * 5 + [_sz, _vp]),
     "tdx_diag_dft_analysis": (_i, [_i, _i, _l, _l, _l, _i, _vp]),
     "tdx_diag_dft_synthesis": (_i, [_i, _i, _l, _l, _i, _vp]),
+    "tdx_diag_loader_bind": (_i, [_vp, _sz] + [_i] * 9 + [_vp, _sz, C.POINTER(_i)]),
     "tdx_fill_bench": (_i, [_i, _vp, _l, _i, _i, _vp, _vp]),
     "tdx_fill_bench2": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
     "tdx_fill_bench3": (_i, [_vp, _l, _i, _l, _i, _i, _i, _vp, _vp]),

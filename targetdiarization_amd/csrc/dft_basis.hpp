@@ -67,11 +67,11 @@ struct StftGeo { int n_fft, nbin, BP, NPAIR, KS; };
 constexpr StftGeo stft_geo(int n_fft) { return StftGeo{n_fft, n_fft / 2 + 1, n_fft / 2 + 16, n_fft / 2 + 64, 2 * (n_fft / 2 + 16)}; }
 
 // analysis [2 * NPAIR][n_fft] at Wa (window `win`), synthesis [n_fft][KS] at Ws (gain `syn_gain`)
-inline void push_stft_basis(Loader& ld, const StftGeo& g, const double* win, const double* syn_gain, size_t& Wa, size_t& Ws) {
-    Wa = ld.room((size_t)2 * g.NPAIR * g.n_fft);
-    Ws = ld.room((size_t)g.n_fft * g.KS);
-    fill_dft_analysis(ld.host.data() + Wa, g.n_fft, g.nbin, g.NPAIR, g.n_fft, win);
-    fill_dft_synthesis(ld.host.data() + Ws, g.n_fft, g.nbin, g.BP, g.KS, syn_gain);
+inline void push_stft_basis(Loader& ld, const StftGeo& g, const double* win, const double* syn_gain, const float*& Wa, const float*& Ws) {
+    const size_t oA = ld.room(Wa, (size_t)2 * g.NPAIR * g.n_fft);
+    const size_t oS = ld.room(Ws, (size_t)g.n_fft * g.KS);
+    fill_dft_analysis(ld.host.data() + oA, g.n_fft, g.nbin, g.NPAIR, g.n_fft, win);
+    fill_dft_synthesis(ld.host.data() + oS, g.n_fft, g.nbin, g.BP, g.KS, syn_gain);
 }
 
 }  // namespace tdx

@@ -2,8 +2,8 @@
 // NOT part of the product library: libtdx.so exports only what include/tdx.h declares.  Used by tests/test_gpu_h3.py
 // (numerics of the split-f16 x3 core in all operand modes), tests/test_gpu_gemm_f32.py (the fp32 MFMA core in every operand mode and
 // on both tile maps), tests/test_gpu_epilogues.py (the shared epilogue family), tests/test_gpu_attention_gate.py (the gated attention
-// launch exactly as the model issues it), tests/test_dft_basis_host.py (the host-built DFT bases, no device) and by tools/ (timing
-// variants, operand fill rates).
+// launch exactly as the model issues it), tests/test_dft_basis_host.py (the host-built DFT bases, no device), tests/test_loaders.py
+// (the Loader's pointer binding, no device) and by tools/ (timing variants, operand fill rates).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +15,7 @@
 #include "dft_basis.hpp"
 #include "epilogues.hpp"
 #include "mf2_attention.hpp"
+#include "weight_pack.hpp"
 
 using namespace tdx;
 
@@ -185,6 +186,49 @@ int tdx_diag_dft_synthesis(int N, int nbin, long im_off, long ld, int gain_kind,
         return tdx::fail(TDX_E_INVALID, "tdx_diag_dft_synthesis: need 1 <= nbin <= N / 2 + 1, nbin <= im_off, im_off + nbin <= ld, gain_kind in 0..2");
     const std::vector<double> gain = gain_kind == 0 ? std::vector<double>(N, 1.0 / N) : divided(hann_periodic(N), gain_kind == 1 ? 4.0 : (double)N);
     fill_dft_synthesis(out, N, nbin, (size_t)im_off, (size_t)ld, gain.data());
+    return TDX_OK;
+}
+
+// ---- the Loader's pointer binding (tdx_common.hpp Loader::bind / resolve): tests/test_loaders.py.  Host buffers, no device call: every
+// binding form into a struct of pointer fields and a pre-sized vector of them, the strict checks, resolve() against a host copy of the
+// image, every tensor copied out through its bound pointer (the layout is in include/tdx_test.h).
+namespace {
+struct BindLayer { const float *tap = nullptr, *rows = nullptr; };
+struct BindProbe { const float *plain = nullptr, *padded = nullptr, *twice = nullptr, *W = nullptr, *b = nullptr; std::vector<BindLayer> layers; };
+}  // namespace
+int tdx_diag_loader_bind(const void* blob, size_t blob_bytes, int n, int npad, int L, int C, int k, int N, int K, int Npad, int Kp, float* out,
+                         size_t out_floats, int* nonnull) {
+    const char* fn = "tdx_diag_loader_bind";
+    if (!blob || !out || !nonnull || n < 1 || npad < n || L < 0 || C < 1 || k < 1 || N < 1 || K < 1 || Npad < N || Kp < K)
+        return fail(TDX_E_INVALID, std::string(fn) + ": bad argument");
+    const size_t sizes[5] = {(size_t)n, (size_t)npad, (size_t)n, (size_t)Npad * Kp, (size_t)Npad}, tap = (size_t)k * C, rows = (size_t)N * Kp;
+    if (out_floats != sizes[0] + sizes[1] + sizes[2] + sizes[3] + sizes[4] + L * (tap + rows)) return fail(TDX_E_INVALID, std::string(fn) + ": out_floats does not match");
+    Loader ld;
+    if (!ld.parse(blob, blob_bytes)) return fail(TDX_E_BLOB, std::string(fn) + ": malformed TDXW blob");
+    BindProbe p;
+    p.layers.resize(L);           // final size before anything binds into it
+    ld.push(p.plain, ld.get("plain", n), n);
+    ld.push(p.padded, ld.get("padded", n), n, npad);
+    const float* src = ld.get("twice", n);
+    const size_t o = ld.room(n);
+    ld.bind(p.twice, o);
+    if (src) for (int i = 0; i < n; ++i) ld.host[o + i] = 2.0f * src[i];
+    bind(ld, p.W, p.b, push_linear(ld, ld.get("lin.weight", {(uint32_t)N, (uint32_t)K}), ld.get("lin.bias", N), N, K, Npad, Kp));
+    for (int l = 0; l < L; ++l) {
+        const std::string q = "layers." + std::to_string(l) + ".";
+        ld.push_tapmajor(p.layers[l].tap, ld.get(q + "tap", (size_t)C * k), C, k);
+        ld.push_rows_padded(p.layers[l].rows, ld.get(q + "rows", {(uint32_t)N, (uint32_t)K}), N, K, Kp);
+    }
+    const int rc = ld.check(fn, true);
+    const std::vector<float> image = ld.host;
+    if (rc == 0) ld.resolve(image.data());
+    const float* field[5] = {p.plain, p.padded, p.twice, p.W, p.b};
+    *nonnull = 0;
+    for (const float* f : field) *nonnull += f != nullptr;
+    for (const BindLayer& w : p.layers) *nonnull += (w.tap != nullptr) + (w.rows != nullptr);
+    if (rc != 0) return rc;
+    for (int i = 0; i < 5; ++i) { std::copy(field[i], field[i] + sizes[i], out); out += sizes[i]; }
+    for (const BindLayer& w : p.layers) { out = std::copy(w.tap, w.tap + tap, out); out = std::copy(w.rows, w.rows + rows, out); }
     return TDX_OK;
 }
 

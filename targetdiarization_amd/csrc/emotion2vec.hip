@@ -392,8 +392,10 @@ __global__ __launch_bounds__(256) void e2v_head_kernel(const float* __restrict__
     }
 }
 
-struct Block { const float *Wqkv, *bqkv, *Wo, *bo, *g1, *b1n, *W1, *b1, *W2, *b2, *g2, *b2n; };
-struct BlockOff { GemmW qkv, o, f1, f2; size_t g1, b1n, g2, b2n; };
+struct Block {
+    const float *Wqkv = nullptr, *bqkv = nullptr, *Wo = nullptr, *bo = nullptr, *g1 = nullptr, *b1n = nullptr, *W1 = nullptr, *b1 = nullptr,
+        *W2 = nullptr, *b2 = nullptr, *g2 = nullptr, *b2n = nullptr;
+};
 
 // the standard ALiBi slopes (get_slopes): powers of 2^(-8 / n) for n a power of two, otherwise those of the power of two below
 // followed by every other one of the next power of two
@@ -420,11 +422,11 @@ struct tdx_emo2v {
     tdx_emo2v_config c{};
     int gw = 0, NP = 0;
     tdx::DevBuf dev;
-    const float *w0, *ln0g, *ln0b;
-    const float *cw[MAX_CONV], *clg[MAX_CONV], *clb[MAX_CONV];
-    const float *plg, *plb, *pw, *pb;
+    const float *w0 = nullptr, *ln0g = nullptr, *ln0b = nullptr;
+    const float *cw[MAX_CONV] = {}, *clg[MAX_CONV] = {}, *clb[MAX_CONV] = {};     // layers 1 .. n_conv - 1 (layer 0: w0, ln0g, ln0b)
+    const float *plg = nullptr, *plb = nullptr, *pw = nullptr, *pb = nullptr;
     std::vector<const float*> gcw, gcb;
-    const float *extra, *nslope, *eng, *enb, *hw, *hb;
+    const float *extra = nullptr, *nslope = nullptr, *eng = nullptr, *enb = nullptr, *hw = nullptr, *hb = nullptr;
     std::vector<Block> blocks;          // prenet blocks, then the main blocks
 };
 
@@ -598,64 +600,51 @@ int tdx_emo2v_create(const tdx_emo2v_config* cfg, const void* blob, size_t blob_
     std::unique_ptr<tdx_emo2v> h(new tdx_emo2v());
     h->device = device; h->c = c; h->gw = gw; h->NP = NP;
 
+    const int nb = c.prenet_depth + c.depth;
+    h->gcw.resize(c.pos_layers); h->gcb.resize(c.pos_layers); h->blocks.resize(nb);      // final sizes: their elements are bound below
+
     // conv 0 [C][1][k] -> tap-major [k][C]
-    const size_t o_w0 = ld.push_tapmajor(ld.get("conv.0.weight", {uC, 1u, (uint32_t)c.conv_k[0]}), C, c.conv_k[0]);
-    size_t o_clg[MAX_CONV], o_clb[MAX_CONV];
-    GemmW cw[MAX_CONV];
+    ld.push_tapmajor(h->w0, ld.get("conv.0.weight", {uC, 1u, (uint32_t)c.conv_k[0]}), C, c.conv_k[0]);
     for (int i = 0; i < c.n_conv; ++i) {
         const std::string p = "conv." + std::to_string(i) + ".";
-        if (i > 0) cw[i] = push_conv_gemm<float>(ld, ld.get(p + "weight", {uC, uC, (uint32_t)c.conv_k[i]}), nullptr, nullptr, C, C, c.conv_k[i], Cp, C);
-        o_clg[i] = ld.push(ld.get(p + "ln.weight", {uC}), C);
-        o_clb[i] = ld.push(ld.get(p + "ln.bias", {uC}), C);
+        if (i > 0) ld.bind(h->cw[i], push_conv_gemm<float>(ld, ld.get(p + "weight", {uC, uC, (uint32_t)c.conv_k[i]}), nullptr, nullptr, C, C, c.conv_k[i], Cp, C).w);
+        ld.push(i ? h->clg[i] : h->ln0g, ld.get(p + "ln.weight", {uC}), C);
+        ld.push(i ? h->clb[i] : h->ln0b, ld.get(p + "ln.bias", {uC}), C);
     }
-    const size_t o_plg = ld.push(ld.get("proj.ln.weight", {uC}), C), o_plb = ld.push(ld.get("proj.ln.bias", {uC}), C);
-    const GemmW pw = push_linear(ld, ld.get("proj.weight", {uD, uC}), ld.get("proj.bias", {uD}), D, C, Dp, C);
+    ld.push(h->plg, ld.get("proj.ln.weight", {uC}), C); ld.push(h->plb, ld.get("proj.ln.bias", {uC}), C);
+    bind(ld, h->pw, h->pb, push_linear(ld, ld.get("proj.weight", {uD, uC}), ld.get("proj.bias", {uD}), D, C, Dp, C));
     // positional conv [D][gw][k] -> [G][k][NP][gw]
-    std::vector<size_t> o_gw(c.pos_layers), o_gb(c.pos_layers);
     for (int l = 0; l < c.pos_layers; ++l) {
         const std::string p = "pos." + std::to_string(l) + ".";
         const float* W = ld.get(p + "weight", {uD, (uint32_t)gw, (uint32_t)c.pos_k});
-        o_gw[l] = ld.room((size_t)c.pos_groups * c.pos_k * NP * gw);
+        const size_t gcw = ld.room(h->gcw[l], (size_t)c.pos_groups * c.pos_k * NP * gw);
         if (W)
             for (int g = 0; g < c.pos_groups; ++g) for (int t = 0; t < c.pos_k; ++t) for (int n = 0; n < gw; ++n) for (int ci = 0; ci < gw; ++ci)
-                ld.host[o_gw[l] + (((size_t)g * c.pos_k + t) * NP + n) * gw + ci] = W[((size_t)(g * gw + n) * gw + ci) * c.pos_k + t];
-        o_gb[l] = ld.push(ld.get(p + "bias", {uD}), D);
+                ld.host[gcw + (((size_t)g * c.pos_k + t) * NP + n) * gw + ci] = W[((size_t)(g * gw + n) * gw + ci) * c.pos_k + t];
+        ld.push(h->gcb[l], ld.get(p + "bias", {uD}), D);
     }
-    const size_t o_extra = ld.push(c.E ? ld.get("extra_tokens", {1u, (uint32_t)c.E, uD}) : nullptr, (size_t)c.E * D, 64);
+    ld.push(h->extra, c.E ? ld.get("extra_tokens", {1u, (uint32_t)c.E, uD}) : nullptr, (size_t)c.E * D, 64);
     // -slope_h max(scale_h, 0)
-    const size_t o_ns = ld.room(c.H);
+    const size_t nslope = ld.room(h->nslope, c.H);
     if (const float* sc = ld.get("alibi_scale", {1u, 1u, (uint32_t)c.H, 1u, 1u})) {
         std::vector<double> sl;
         alibi_slopes(c.H, sl);
-        for (int i = 0; i < c.H; ++i) ld.host[o_ns + i] = (float)(-sl[i] * std::max((double)sc[i], 0.0));
+        for (int i = 0; i < c.H; ++i) ld.host[nslope + i] = (float)(-sl[i] * std::max((double)sc[i], 0.0));
     }
-    const size_t o_eng = ld.push(ld.get("prenet.norm.weight", {uD}), D), o_enb = ld.push(ld.get("prenet.norm.bias", {uD}), D);
-    const int nb = c.prenet_depth + c.depth;
-    std::vector<BlockOff> bo(nb);
+    ld.push(h->eng, ld.get("prenet.norm.weight", {uD}), D); ld.push(h->enb, ld.get("prenet.norm.bias", {uD}), D);
     for (int l = 0; l < nb; ++l) {
         const std::string p = (l < c.prenet_depth ? "prenet.blocks." + std::to_string(l) : "blocks." + std::to_string(l - c.prenet_depth)) + ".";
-        BlockOff& o = bo[l];
-        o.qkv = push_linear(ld, ld.get(p + "attn.qkv.weight", {3 * uD, uD}), ld.get(p + "attn.qkv.bias", {3 * uD}), 3 * D, D, up(3 * D, 128), D);
-        o.o = push_linear(ld, ld.get(p + "attn.proj.weight", {uD, uD}), ld.get(p + "attn.proj.bias", {uD}), D, D, Dp, D);
-        o.g1 = ld.push(ld.get(p + "norm1.weight", {uD}), D); o.b1n = ld.push(ld.get(p + "norm1.bias", {uD}), D);
-        o.f1 = push_linear(ld, ld.get(p + "mlp.fc1.weight", {4 * uD, uD}), ld.get(p + "mlp.fc1.bias", {4 * uD}), 4 * D, D, up(4 * D, 128), D);
-        o.f2 = push_linear(ld, ld.get(p + "mlp.fc2.weight", {uD, 4 * uD}), ld.get(p + "mlp.fc2.bias", {uD}), D, 4 * D, Dp, 4 * D);
-        o.g2 = ld.push(ld.get(p + "norm2.weight", {uD}), D); o.b2n = ld.push(ld.get(p + "norm2.bias", {uD}), D);
+        Block& w = h->blocks[l];
+        bind(ld, w.Wqkv, w.bqkv, push_linear(ld, ld.get(p + "attn.qkv.weight", {3 * uD, uD}), ld.get(p + "attn.qkv.bias", {3 * uD}), 3 * D, D, up(3 * D, 128), D));
+        bind(ld, w.Wo, w.bo, push_linear(ld, ld.get(p + "attn.proj.weight", {uD, uD}), ld.get(p + "attn.proj.bias", {uD}), D, D, Dp, D));
+        ld.push(w.g1, ld.get(p + "norm1.weight", {uD}), D); ld.push(w.b1n, ld.get(p + "norm1.bias", {uD}), D);
+        bind(ld, w.W1, w.b1, push_linear(ld, ld.get(p + "mlp.fc1.weight", {4 * uD, uD}), ld.get(p + "mlp.fc1.bias", {4 * uD}), 4 * D, D, up(4 * D, 128), D));
+        bind(ld, w.W2, w.b2, push_linear(ld, ld.get(p + "mlp.fc2.weight", {uD, 4 * uD}), ld.get(p + "mlp.fc2.bias", {uD}), D, 4 * D, Dp, 4 * D));
+        ld.push(w.g2, ld.get(p + "norm2.weight", {uD}), D); ld.push(w.b2n, ld.get(p + "norm2.bias", {uD}), D);
     }
-    const size_t o_hw = ld.push(ld.get("head.weight", {(uint32_t)c.n_classes, uD}), (size_t)c.n_classes * D);
-    const size_t o_hb = ld.push(ld.get("head.bias", {(uint32_t)c.n_classes}), c.n_classes);
+    ld.push(h->hw, ld.get("head.weight", {(uint32_t)c.n_classes, uD}), (size_t)c.n_classes * D);
+    ld.push(h->hb, ld.get("head.bias", {(uint32_t)c.n_classes}), c.n_classes);
     TRY(ld.finish("tdx_emo2v_create", true, device, h->dev));
-    const float* dev = h->dev;
-    h->w0 = dev + o_w0; h->ln0g = dev + o_clg[0]; h->ln0b = dev + o_clb[0];
-    for (int i = 1; i < c.n_conv; ++i) { h->cw[i] = dev + cw[i].w; h->clg[i] = dev + o_clg[i]; h->clb[i] = dev + o_clb[i]; }
-    h->plg = dev + o_plg; h->plb = dev + o_plb; h->pw = dev + pw.w; h->pb = dev + pw.b;
-    for (int l = 0; l < c.pos_layers; ++l) { h->gcw.push_back(dev + o_gw[l]); h->gcb.push_back(dev + o_gb[l]); }
-    h->extra = dev + o_extra; h->nslope = dev + o_ns; h->eng = dev + o_eng; h->enb = dev + o_enb; h->hw = dev + o_hw; h->hb = dev + o_hb;
-    for (int l = 0; l < nb; ++l) {
-        const BlockOff& o = bo[l];
-        h->blocks.push_back(Block{dev + o.qkv.w, dev + o.qkv.b, dev + o.o.w, dev + o.o.b, dev + o.g1, dev + o.b1n, dev + o.f1.w, dev + o.f1.b,
-                                  dev + o.f2.w, dev + o.f2.b, dev + o.g2, dev + o.b2n});
-    }
     *out = h.release();
     return TDX_OK;
 }

@@ -142,13 +142,13 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
 
 struct tdx_fbank {
     int device = 0;
-    int mode; float scale;
-    tdx::DevBuf dev; const float *Wdft, *mel, *win;
+    int mode = 0; float scale = 1.0f;
+    tdx::DevBuf dev; const float *Wdft = nullptr, *mel = nullptr, *win = nullptr;
 };
 struct tdx_stft {
     int device = 0;
-    int nfft, hop, dimf, T, chunk;
-    tdx::DevBuf dev; const float *Wf, *Wi, *win, *env;
+    int nfft = 0, hop = 0, dimf = 0, T = 0, chunk = 0;
+    tdx::DevBuf dev; const float *Wf = nullptr, *Wi = nullptr, *win = nullptr, *env = nullptr;
 };
 
 extern "C" {
@@ -157,11 +157,12 @@ int tdx_fbank_create(int mode, int device, tdx_fbank** out) {
     if (!out || mode < 0 || mode > 2) return tdx::fail(TDX_E_INVALID, "tdx_fbank_create: mode must be 0 (SV), 1 (ASR) or 2 (WeSpeaker)");
     tdx::Loader ld;       // (no blob: the tables are computed here, then staged and uploaded like weights)
     std::vector<float>& host = ld.host;
-    const size_t oW = ld.room((size_t)2 * NBIN_PAD * NF);      // DFT [2 * 320][512]: re rows k, im rows 320 + k, no window
+    std::unique_ptr<tdx_fbank> h(new tdx_fbank());
+    h->device = device; h->mode = mode; h->scale = mode != 0 ? 32768.0f : 1.0f;
+    const size_t oW = ld.room(h->Wdft, (size_t)2 * NBIN_PAD * NF);      // DFT [2 * 320][512]: re rows k, im rows 320 + k, no window
     tdx::fill_dft_analysis(host.data() + oW, NF, NF / 2 + 1, NBIN_PAD, NF, nullptr);
     // mel banks [128][320] (torchaudio get_mel_banks; last FFT bin column is zero)
-    const size_t oM = host.size();
-    host.resize(oM + al((size_t)128 * NBIN_PAD), 0.f);
+    const size_t oM = ld.room(h->mel, (size_t)128 * NBIN_PAD);
     {
         auto mel = [](double f) { return 1127.0 * log(1.0 + f / 700.0); };
         const double mlow = mel(20.0), mhigh = mel(8000.0), delta = (mhigh - mlow) / (NMEL + 1);
@@ -175,17 +176,12 @@ int tdx_fbank_create(int mode, int device, tdx_fbank** out) {
             }
         }
     }
-    const size_t oWin = host.size();
-    host.resize(oWin + al(FLEN), 0.f);
+    const size_t oWin = ld.room(h->win, FLEN);
     for (int i = 0; i < FLEN; ++i) {
         if (mode == 0) host[oWin + i] = (float)pow(0.5 - 0.5 * cos(2.0 * M_PI * i / (FLEN - 1)), 0.85);   // povey
         else host[oWin + i] = (float)(0.54 - 0.46 * cos(2.0 * M_PI * i / (FLEN - 1)));                     // hamming
     }
-    std::unique_ptr<tdx_fbank> h(new tdx_fbank());
     TRY(ld.finish("tdx_fbank_create", false, device, h->dev));
-    const float* dev = h->dev;
-    h->device = device;
-    h->mode = mode; h->scale = mode != 0 ? 32768.0f : 1.0f; h->Wdft = dev + oW; h->mel = dev + oM; h->win = dev + oWin;
     *out = h.release();
     return TDX_OK;
 }
@@ -248,27 +244,24 @@ int tdx_stft_create(int n_fft, int hop, int dim_f, int dim_t, int device, tdx_st
     const int N = n_fft, T = dim_t, chunk = hop * (dim_t - 1);
     tdx::Loader ld;       // (no blob: the tables are computed here, then staged and uploaded like weights)
     std::vector<float>& host = ld.host;
+    std::unique_ptr<tdx_stft> h(new tdx_stft());
+    h->device = device;
+    h->nfft = N; h->hop = hop; h->dimf = dim_f; h->T = T; h->chunk = chunk;
     // forward: rows m = ri*dim_f + f over k=n (time):  re: cos, im: -sin
-    const size_t oWf = ld.room((size_t)2 * dim_f * N);
+    const size_t oWf = ld.room(h->Wf, (size_t)2 * dim_f * N);
     tdx::fill_dft_analysis(host.data() + oWf, N, dim_f, dim_f, N, nullptr);
     // inverse (c2r, bins >= dim_f are zero): rows n (time) over k = ri*dim_f + f
     //   y[n] = 1/N [X0.re + 2 sum_{f>=1} (X_f.re cos - X_f.im sin)] (+ Nyquist term if dim_f covers it)
-    const size_t oWi = ld.room((size_t)N * 2 * dim_f);
+    const size_t oWi = ld.room(h->Wi, (size_t)N * 2 * dim_f);
     tdx::fill_dft_synthesis(host.data() + oWi, N, dim_f, dim_f, (size_t)2 * dim_f, std::vector<double>(N, 1.0 / N).data());
-    const size_t oWin = ld.room(N);
+    const size_t oWin = ld.room(h->win, N);
     const std::vector<double> w = tdx::hann_periodic(N);
     for (int i = 0; i < N; ++i) host[oWin + i] = (float)w[i];
-    const size_t oEnv = host.size();
     const int L = N + hop * (T - 1);
-    host.resize(oEnv + al(L), 0.f);
+    const size_t oEnv = ld.room(h->env, L);
     for (int t = 0; t < T; ++t)
         for (int n = 0; n < N; ++n) host[oEnv + (size_t)t * hop + n] += (float)((double)host[oWin + n] * (double)host[oWin + n]);
-    std::unique_ptr<tdx_stft> h(new tdx_stft());
     TRY(ld.finish("tdx_stft_create", false, device, h->dev));
-    const float* dev = h->dev;
-    h->device = device;
-    h->nfft = N; h->hop = hop; h->dimf = dim_f; h->T = T; h->chunk = chunk;
-    h->Wf = dev + oWf; h->Wi = dev + oWi; h->win = dev + oWin; h->env = dev + oEnv;
     *out = h.release();
     return TDX_OK;
 }

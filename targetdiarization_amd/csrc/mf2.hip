@@ -213,15 +213,18 @@ __global__ void zero_words_kernel(unsigned* __restrict__ p, int n) {
 // ------------------------------------------------------------------ model
 struct LayerW {
     // FLASH
-    const float *Whq, *ghq, *bhq, *cw_h, *cw_qk, *gamma, *beta, *Wo, *go, *bo, *cw_o;
+    const float *Whq = nullptr, *ghq = nullptr, *bhq = nullptr, *cw_h = nullptr, *cw_qk = nullptr, *gamma = nullptr, *beta = nullptr,
+        *Wo = nullptr, *go = nullptr, *bo = nullptr, *cw_o = nullptr;
     // FSMN
-    const float *W1, *b1, *a1, *ln1g, *ln1b, *Wuv, *buv, *cw_uv, *Wl, *bl, *Wp, *w1T, *w2T, *ing, *inb, *pre, *ln2g, *ln2b, *W2, *b2;
+    const float *W1 = nullptr, *b1 = nullptr, *a1 = nullptr, *ln1g = nullptr, *ln1b = nullptr, *Wuv = nullptr, *buv = nullptr,
+        *cw_uv = nullptr, *Wl = nullptr, *bl = nullptr, *Wp = nullptr, *w1T = nullptr, *w2T = nullptr, *ing = nullptr, *inb = nullptr,
+        *pre = nullptr, *ln2g = nullptr, *ln2b = nullptr, *W2 = nullptr, *b2 = nullptr;
     // nn.Linear weights as split-f16 planes + row scales (gemm_h3.hpp), made once at create
     H3W hWhq, hWo, hW1, hWuv, hWl, hWp, hW2;
     // static power-of-two scales of the K-major planes of v|u and lin_k (bounds from the weights, see tdx_mf2_create):
     // sv_* multiplies the value before the f16 split, st points at the device copy of {1/sv_vu, 1/sv_lk}
     float sv_vu, sv_lk;
-    const float* st;
+    const float* st = nullptr;
 };
 
 }  // namespace
@@ -237,8 +240,9 @@ struct tdx_mf2 {
     tdx::DevBuf dev_static;         // [L][2] inverse static scales
     H3W hWenc, hWout, hWtg, hWdec1;
     std::vector<LayerW> layers;
-    const float *encT, *gn1g, *gn1b, *Wenc, *pe_scale, *inv_freq, *rot_freqs, *lnfg, *lnfb, *gn2g, *gn2b, *prelu, *Wout, *bout,
-        *Wtg, *btg, *Wdec1, *decT;
+    const float *encT = nullptr, *gn1g = nullptr, *gn1b = nullptr, *Wenc = nullptr, *pe_scale = nullptr, *inv_freq = nullptr,
+        *rot_freqs = nullptr, *lnfg = nullptr, *lnfb = nullptr, *gn2g = nullptr, *gn2b = nullptr, *prelu = nullptr, *Wout = nullptr,
+        *bout = nullptr, *Wtg = nullptr, *btg = nullptr, *Wdec1 = nullptr, *decT = nullptr;
     int taps;
     // optional live profiling of the dominant kernel (to_hidden GEMM): event pairs recorded on
     // the forward's stream, read back by tdx_mf2_profile_collect after the caller synchronised.
@@ -476,11 +480,12 @@ int tdx_mf2_create(const tdx_mf2_config* cfg, const void* blob, size_t blob_byte
     ld.host.reserve(60u * 1000 * 1000);
     std::vector<float> stat_host((size_t)L * 2, 1.f);
     std::vector<float> sv_host((size_t)L * 2, 1.f);
-    struct Off { size_t Whq, ghq, bhq, cw_h, cw_qk, gamma, beta, Wo, go, bo, cw_o, W1, b1, a1, ln1g, ln1b, Wuv, buv, cw_uv, Wl, bl, Wp, w1T, w2T, ing, inb, pre, ln2g, ln2b, W2, b2; };
-    std::vector<Off> offs(L);
+    std::unique_ptr<tdx_mf2> h(new tdx_mf2());
+    h->device = device; h->L = L; h->taps = 0; h->ev_used = 0;
+    h->layers.resize(L);
     const std::string PFX = "mask_net.mdl.intra_mdl.mossformerM.";
     for (int l = 0; l < L && ld.ok(); ++l) {
-        Off& o = offs[l];
+        LayerW& w = h->layers[l];
         const std::string p = PFX + "layers." + std::to_string(l) + ".";
         const float* Wh = ld.get(p + "to_hidden.mdl.1.weight", (size_t)HID * C);
         const float* Wq = ld.get(p + "to_qk.mdl.1.weight", (size_t)QK * C);
@@ -491,19 +496,19 @@ int tdx_mf2_create(const tdx_mf2_config* cfg, const void* blob, size_t blob_byte
         const float* cwh = ld.get(p + "to_hidden.mdl.3.sequential.1.conv.weight", (size_t)HID * 17);
         const float* cwq = ld.get(p + "to_qk.mdl.3.sequential.1.conv.weight", (size_t)QK * 17);
         if (!ld.ok()) break;
-        o.Whq = ld.push(Wh, (size_t)HID * C); ld.push(Wq, (size_t)QK * C);       // contiguous [2176][512] (HID*C is 64-aligned)
+        ld.push(w.Whq, Wh, (size_t)HID * C); ld.push(Wq, (size_t)QK * C);       // contiguous [2176][512] (HID*C is 64-aligned)
         ld.host.resize(ld.host.size() + (size_t)128 * C, 0.f);                     // zero rows up to 2304: the x6 GEMM reads W in 256-row tiles
-        o.ghq = ld.room(HQ);
-        for (int i = 0; i < HQ; ++i) ld.host[o.ghq + i] = i < HID ? gh[0] : gq[0];
-        o.bhq = ld.room(HQ);
-        for (int i = 0; i < HQ; ++i) ld.host[o.bhq + i] = i < HID ? bh[i] : bq[i - HID];
-        o.cw_h = ld.push_tapmajor(cwh, HID, 17);
-        o.cw_qk = ld.push_tapmajor(cwq, QK, 17);
+        const size_t ghq = ld.room(w.ghq, HQ);
+        for (int i = 0; i < HQ; ++i) ld.host[ghq + i] = i < HID ? gh[0] : gq[0];
+        const size_t bhq = ld.room(w.bhq, HQ);
+        for (int i = 0; i < HQ; ++i) ld.host[bhq + i] = i < HID ? bh[i] : bq[i - HID];
+        ld.push_tapmajor(w.cw_h, cwh, HID, 17);
+        ld.push_tapmajor(w.cw_qk, cwq, QK, 17);
         (void)ld.get(p + "rotary_pos_emb.freqs", 16);      // one RotaryEmbedding object shared by all layers (mossformer_block.py:453): layer 0's copy is used
         const float* gam = ld.get(p + "qk_offset_scale.gamma", 4 * QK);
         const float* bet = ld.get(p + "qk_offset_scale.beta", 4 * QK);
-        o.gamma = ld.push(gam, 4 * QK);
-        o.beta = ld.push(bet, 4 * QK);
+        ld.push(w.gamma, gam, 4 * QK);
+        ld.push(w.beta, bet, 4 * QK);
         if (!ld.ok()) break;
         {
             // Static bounds for the K-major planes (gemm_h3.hpp).  After ScaleNorm the (shifted) row has norm
@@ -536,22 +541,22 @@ int tdx_mf2_create(const tdx_mf2_config* cfg, const void* blob, size_t blob_byte
             sv_host[l * 2] = (float)pow2scale(vub); sv_host[l * 2 + 1] = (float)pow2scale(lkb);
             stat_host[l * 2] = 1.0f / sv_host[l * 2]; stat_host[l * 2 + 1] = 1.0f / sv_host[l * 2 + 1];
         }
-        o.Wo = ld.push(ld.get(p + "to_out.mdl.1.weight", (size_t)C * 1024), (size_t)C * 1024);
+        ld.push(w.Wo, ld.get(p + "to_out.mdl.1.weight", (size_t)C * 1024), (size_t)C * 1024);
         const float* go = ld.get(p + "to_out.mdl.0.g", 1);
-        o.go = ld.room(C);
-        if (go) for (int i = 0; i < C; ++i) ld.host[o.go + i] = go[0];
-        o.bo = ld.push(ld.get(p + "to_out.mdl.1.bias", C), C);
-        o.cw_o = ld.push_tapmajor(ld.get(p + "to_out.mdl.3.sequential.1.conv.weight", (size_t)C * 17), C, 17);
+        const size_t go_off = ld.room(w.go, C);
+        if (go) for (int i = 0; i < C; ++i) ld.host[go_off + i] = go[0];
+        ld.push(w.bo, ld.get(p + "to_out.mdl.1.bias", C), C);
+        ld.push_tapmajor(w.cw_o, ld.get(p + "to_out.mdl.3.sequential.1.conv.weight", (size_t)C * 17), C, 17);
         // FSMN
         const std::string q = PFX + "fsmn." + std::to_string(l) + ".";
-        o.W1 = ld.push(ld.get(q + "conv1.0.weight", (size_t)INNER * C), (size_t)INNER * C);
-        o.b1 = ld.push(ld.get(q + "conv1.0.bias", INNER), INNER);
-        o.a1 = ld.push(ld.get(q + "conv1.1.weight", 1), 1);
-        o.ln1g = ld.push(ld.get(q + "norm1.weight", INNER), INNER);
-        o.ln1b = ld.push(ld.get(q + "norm1.bias", INNER), INNER);
+        ld.push(w.W1, ld.get(q + "conv1.0.weight", (size_t)INNER * C), (size_t)INNER * C);
+        ld.push(w.b1, ld.get(q + "conv1.0.bias", INNER), INNER);
+        ld.push(w.a1, ld.get(q + "conv1.1.weight", 1), 1);
+        ld.push(w.ln1g, ld.get(q + "norm1.weight", INNER), INNER);
+        ld.push(w.ln1b, ld.get(q + "norm1.bias", INNER), INNER);
         // fold the FFConvM LayerNorm affine into its Linear:  LN(h)W^T+b = hhat (W diag(g))^T + (b + W beta)
-        o.Wuv = ld.room((size_t)C * INNER);
-        o.buv = ld.room(C);
+        const size_t Wuv = ld.room(w.Wuv, (size_t)C * INNER);
+        const size_t buv = ld.room(w.buv, C);
         for (int br = 0; br < 2 && ld.ok(); ++br) {
             const std::string r = q + "gated_fsmn." + (br == 0 ? "to_u" : "to_v") + ".mdl.";
             const float* lg = ld.get(r + "0.weight", INNER);
@@ -562,83 +567,64 @@ int tdx_mf2_create(const tdx_mf2_config* cfg, const void* blob, size_t blob_byte
             for (int n = 0; n < INNER; ++n) {
                 double acc = bb[n];
                 for (int k = 0; k < INNER; ++k) {
-                    ld.host[o.Wuv + ((size_t)br * INNER + n) * INNER + k] = W[(size_t)n * INNER + k] * lg[k];
+                    ld.host[Wuv + ((size_t)br * INNER + n) * INNER + k] = W[(size_t)n * INNER + k] * lg[k];
                     acc += (double)W[(size_t)n * INNER + k] * (double)lb[k];
                 }
-                ld.host[o.buv + br * INNER + n] = (float)acc;
+                ld.host[buv + br * INNER + n] = (float)acc;
             }
         }
         if (!ld.ok()) break;
         {
             const float* cu = ld.get(q + "gated_fsmn.to_u.mdl.3.sequential.1.conv.weight", (size_t)INNER * 17);
             const float* cv = ld.get(q + "gated_fsmn.to_v.mdl.3.sequential.1.conv.weight", (size_t)INNER * 17);
-            o.cw_uv = ld.room((size_t)17 * C);
+            const size_t cw_uv = ld.room(w.cw_uv, (size_t)17 * C);
             if (cu && cv) for (int c = 0; c < INNER; ++c) for (int t = 0; t < 17; ++t) {
-                ld.host[o.cw_uv + (size_t)t * C + c] = cu[c * 17 + t];
-                ld.host[o.cw_uv + (size_t)t * C + INNER + c] = cv[c * 17 + t];
+                ld.host[cw_uv + (size_t)t * C + c] = cu[c * 17 + t];
+                ld.host[cw_uv + (size_t)t * C + INNER + c] = cv[c * 17 + t];
             }
         }
         const std::string f = q + "gated_fsmn.fsmn.";
-        o.Wl = ld.push(ld.get(f + "linear.weight", (size_t)INNER * INNER), (size_t)INNER * INNER);
-        o.bl = ld.push(ld.get(f + "linear.bias", INNER), INNER);
-        o.Wp = ld.push(ld.get(f + "project.weight", (size_t)INNER * INNER), (size_t)INNER * INNER);
-        o.w1T = ld.push_tapmajor(ld.get(f + "conv.conv1.weight", (size_t)INNER * 39), INNER, 39);
+        ld.push(w.Wl, ld.get(f + "linear.weight", (size_t)INNER * INNER), (size_t)INNER * INNER);
+        ld.push(w.bl, ld.get(f + "linear.bias", INNER), INNER);
+        ld.push(w.Wp, ld.get(f + "project.weight", (size_t)INNER * INNER), (size_t)INNER * INNER);
+        ld.push_tapmajor(w.w1T, ld.get(f + "conv.conv1.weight", (size_t)INNER * 39), INNER, 39);
         {   // conv2.weight [256][2][39] -> [39][2][256]
             const float* w2 = ld.get(f + "conv.conv2.weight", (size_t)INNER * 2 * 39);
-            o.w2T = ld.room((size_t)39 * 2 * INNER);
+            const size_t w2T = ld.room(w.w2T, (size_t)39 * 2 * INNER);
             if (w2) for (int j = 0; j < INNER; ++j) for (int ic = 0; ic < 2; ++ic) for (int t = 0; t < 39; ++t)
-                ld.host[o.w2T + ((size_t)t * 2 + ic) * INNER + j] = w2[((size_t)j * 2 + ic) * 39 + t];
+                ld.host[w2T + ((size_t)t * 2 + ic) * INNER + j] = w2[((size_t)j * 2 + ic) * 39 + t];
         }
-        o.ing = ld.push(ld.get(f + "conv.norm1.weight", INNER), INNER); ld.push(ld.get(f + "conv.norm2.weight", INNER), INNER);
-        o.inb = ld.push(ld.get(f + "conv.norm1.bias", INNER), INNER); ld.push(ld.get(f + "conv.norm2.bias", INNER), INNER);
-        o.pre = ld.push(ld.get(f + "conv.prelu1.weight", INNER), INNER); ld.push(ld.get(f + "conv.prelu2.weight", INNER), INNER);
-        o.ln2g = ld.push(ld.get(q + "norm2.weight", INNER), INNER);
-        o.ln2b = ld.push(ld.get(q + "norm2.bias", INNER), INNER);
-        o.W2 = ld.push(ld.get(q + "conv2.weight", (size_t)C * INNER), (size_t)C * INNER);
-        o.b2 = ld.push(ld.get(q + "conv2.bias", C), C);
+        ld.push(w.ing, ld.get(f + "conv.norm1.weight", INNER), INNER); ld.push(ld.get(f + "conv.norm2.weight", INNER), INNER);
+        ld.push(w.inb, ld.get(f + "conv.norm1.bias", INNER), INNER); ld.push(ld.get(f + "conv.norm2.bias", INNER), INNER);
+        ld.push(w.pre, ld.get(f + "conv.prelu1.weight", INNER), INNER); ld.push(ld.get(f + "conv.prelu2.weight", INNER), INNER);
+        ld.push(w.ln2g, ld.get(q + "norm2.weight", INNER), INNER);
+        ld.push(w.ln2b, ld.get(q + "norm2.bias", INNER), INNER);
+        ld.push(w.W2, ld.get(q + "conv2.weight", (size_t)C * INNER), (size_t)C * INNER);
+        ld.push(w.b2, ld.get(q + "conv2.bias", C), C);
     }
-    size_t encT = 0, gn1g = 0, gn1b = 0, Wenc = 0, pes = 0, invf = 0, rotf = 0, lnfg = 0, lnfb = 0, gn2g = 0, gn2b = 0, prelu = 0,
-           Wout = 0, bout = 0, Wtg = 0, btg = 0, Wdec1 = 0, decT = 0;
     if (ld.ok()) {
-        encT = ld.push_tapmajor(ld.get("enc.conv1d.weight", (size_t)C * 16), C, 16);
-        gn1g = ld.push(ld.get("mask_net.norm.weight", C), C);
-        gn1b = ld.push(ld.get("mask_net.norm.bias", C), C);
-        Wenc = ld.push(ld.get("mask_net.conv1d_encoder.weight", (size_t)C * C), (size_t)C * C);
-        pes = ld.push(ld.get("mask_net.pos_enc.scale", 1), 1);
-        invf = ld.push(ld.get("mask_net.pos_enc.inv_freq", 256), 256);
-        rotf = ld.push(ld.get(PFX + "layers.0.rotary_pos_emb.freqs", 16), 16);
-        lnfg = ld.push(ld.get("mask_net.mdl.intra_mdl.norm.weight", C), C);
-        lnfb = ld.push(ld.get("mask_net.mdl.intra_mdl.norm.bias", C), C);
-        gn2g = ld.push(ld.get("mask_net.mdl.intra_norm.weight", C), C);
-        gn2b = ld.push(ld.get("mask_net.mdl.intra_norm.bias", C), C);
-        prelu = ld.push(ld.get("mask_net.prelu.weight", 1), 1);
-        Wout = ld.push(ld.get("mask_net.conv1d_out.weight", (size_t)2 * C * C), (size_t)2 * C * C);
-        bout = ld.push(ld.get("mask_net.conv1d_out.bias", 2 * C), 2 * C);
-        Wtg = ld.push(ld.get("mask_net.output.0.weight", (size_t)C * C), (size_t)C * C);
+        ld.push_tapmajor(h->encT, ld.get("enc.conv1d.weight", (size_t)C * 16), C, 16);
+        ld.push(h->gn1g, ld.get("mask_net.norm.weight", C), C);
+        ld.push(h->gn1b, ld.get("mask_net.norm.bias", C), C);
+        ld.push(h->Wenc, ld.get("mask_net.conv1d_encoder.weight", (size_t)C * C), (size_t)C * C);
+        ld.push(h->pe_scale, ld.get("mask_net.pos_enc.scale", 1), 1);
+        ld.push(h->inv_freq, ld.get("mask_net.pos_enc.inv_freq", 256), 256);
+        ld.push(h->rot_freqs, ld.get(PFX + "layers.0.rotary_pos_emb.freqs", 16), 16);
+        ld.push(h->lnfg, ld.get("mask_net.mdl.intra_mdl.norm.weight", C), C);
+        ld.push(h->lnfb, ld.get("mask_net.mdl.intra_mdl.norm.bias", C), C);
+        ld.push(h->gn2g, ld.get("mask_net.mdl.intra_norm.weight", C), C);
+        ld.push(h->gn2b, ld.get("mask_net.mdl.intra_norm.bias", C), C);
+        ld.push(h->prelu, ld.get("mask_net.prelu.weight", 1), 1);
+        ld.push(h->Wout, ld.get("mask_net.conv1d_out.weight", (size_t)2 * C * C), (size_t)2 * C * C);
+        ld.push(h->bout, ld.get("mask_net.conv1d_out.bias", 2 * C), 2 * C);
+        ld.push(h->Wtg, ld.get("mask_net.output.0.weight", (size_t)C * C), (size_t)C * C);
         ld.push(ld.get("mask_net.output_gate.0.weight", (size_t)C * C), (size_t)C * C);
-        btg = ld.push(ld.get("mask_net.output.0.bias", C), C);
+        ld.push(h->btg, ld.get("mask_net.output.0.bias", C), C);
         ld.push(ld.get("mask_net.output_gate.0.bias", C), C);
-        Wdec1 = ld.push(ld.get("mask_net.conv1_decoder.weight", (size_t)C * C), (size_t)C * C);
-        decT = ld.push_tapmajor(ld.get("dec.weight", (size_t)C * 16), C, 16);
+        ld.push(h->Wdec1, ld.get("mask_net.conv1_decoder.weight", (size_t)C * C), (size_t)C * C);
+        ld.push_tapmajor(h->decT, ld.get("dec.weight", (size_t)C * 16), C, 16);
     }
-    std::unique_ptr<tdx_mf2> h(new tdx_mf2());
-    h->device = device; h->L = L; h->taps = 0; h->ev_used = 0;
     TRY(ld.finish("tdx_mf2_create", true, device, h->dev_weights));
-    const float* dev = h->dev_weights;
-    h->layers.resize(L);
-    for (int l = 0; l < L; ++l) {
-        const Off& o = offs[l]; LayerW& w = h->layers[l];
-        w.Whq = dev + o.Whq; w.ghq = dev + o.ghq; w.bhq = dev + o.bhq; w.cw_h = dev + o.cw_h; w.cw_qk = dev + o.cw_qk;
-        w.gamma = dev + o.gamma; w.beta = dev + o.beta; w.Wo = dev + o.Wo; w.go = dev + o.go; w.bo = dev + o.bo; w.cw_o = dev + o.cw_o;
-        w.W1 = dev + o.W1; w.b1 = dev + o.b1; w.a1 = dev + o.a1; w.ln1g = dev + o.ln1g; w.ln1b = dev + o.ln1b;
-        w.Wuv = dev + o.Wuv; w.buv = dev + o.buv; w.cw_uv = dev + o.cw_uv; w.Wl = dev + o.Wl; w.bl = dev + o.bl; w.Wp = dev + o.Wp;
-        w.w1T = dev + o.w1T; w.w2T = dev + o.w2T; w.ing = dev + o.ing; w.inb = dev + o.inb; w.pre = dev + o.pre;
-        w.ln2g = dev + o.ln2g; w.ln2b = dev + o.ln2b; w.W2 = dev + o.W2; w.b2 = dev + o.b2;
-    }
-    h->encT = dev + encT; h->gn1g = dev + gn1g; h->gn1b = dev + gn1b; h->Wenc = dev + Wenc; h->pe_scale = dev + pes;
-    h->inv_freq = dev + invf; h->rot_freqs = dev + rotf; h->lnfg = dev + lnfg; h->lnfb = dev + lnfb; h->gn2g = dev + gn2g;
-    h->gn2b = dev + gn2b; h->prelu = dev + prelu; h->Wout = dev + Wout; h->bout = dev + bout; h->Wtg = dev + Wtg; h->btg = dev + btg;
-    h->Wdec1 = dev + Wdec1; h->decT = dev + decT;
     {
         tdx::DeviceGuard guard(device);
         const hipError_t e = guard.err != hipSuccess ? guard.err : h->dev_static.upload(stat_host.data(), stat_host.size() * sizeof(float));

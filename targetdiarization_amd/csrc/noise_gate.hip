@@ -226,7 +226,7 @@ static_assert(2 * BP >= NFFT, "the synthesis frames must fit the A and Y planes"
 
 struct tdx_ngate {
     int device = 0;
-    tdx::DevBuf dev; const float *Wa, *Ws;
+    tdx::DevBuf dev; const float *Wa = nullptr, *Ws = nullptr;
 };
 
 extern "C" {
@@ -239,12 +239,10 @@ int tdx_ngate_create(int device, tdx_ngate** out) {
     // synthesis [1024][2 * 528]: frame[n] = hann[n] / 4 * 1/1024 * sum_k w_k (re_k cos - im_k sin), w = 1 at DC and Nyquist, else 2
     // (the 1/4 and the gather's 1/384 make the overlap-add envelope: four hann^2 at hop 256 sum to 1.5 = 4 * 384 / 1024)
     const std::vector<double> win = tdx::hann_periodic(NFFT);
-    size_t oA, oS;
-    tdx::push_stft_basis(ld, GEO, win.data(), tdx::divided(win, 4.0).data(), oA, oS);
     std::unique_ptr<tdx_ngate> h(new tdx_ngate());
+    h->device = device;
+    tdx::push_stft_basis(ld, GEO, win.data(), tdx::divided(win, 4.0).data(), h->Wa, h->Ws);
     TRY(ld.finish("tdx_ngate_create", false, device, h->dev));
-    const float* dev = h->dev;
-    h->device = device; h->Wa = dev + oA; h->Ws = dev + oS;
     *out = h.release();
     return TDX_OK;
 }

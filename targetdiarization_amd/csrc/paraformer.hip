@@ -337,7 +337,7 @@ int lin3_splitk(const unsigned char* Ap, const float* As, const H3W& W, int M, i
 
 struct tdx_pfenc {
     int device = 0;
-    int L; tdx::DevBuf dev, dev_planes; std::vector<PfLayer> layers; const float *ang, *anb;
+    int L = 0; tdx::DevBuf dev, dev_planes; std::vector<PfLayer> layers; const float *ang = nullptr, *anb = nullptr;
 };
 
 extern "C" {
@@ -346,20 +346,15 @@ int tdx_pfenc_create(int num_blocks, const void* blob, size_t blob_bytes, int de
     if (!blob || !out || num_blocks < 1) return tdx::fail(TDX_E_INVALID, "tdx_pfenc_create: bad argument");
     tdx::Loader ld;       // (not strict: the encoder's tensors are read out of the whole model's checkpoint)
     if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_pfenc_create: malformed TDXW blob");
-    std::vector<PfLayerOff> offs(num_blocks);
-    for (int l = 0; l < num_blocks && ld.ok(); ++l)
-        pf_stage_layer(ld, l == 0 ? std::string("encoder.encoders0.0.") : "encoder.encoders." + std::to_string(l - 1) + ".", l == 0, offs[l]);
-    size_t ang = 0, anb = 0;
-    if (ld.ok()) { ang = ld.push(ld.get("encoder.after_norm.weight", D), D); anb = ld.push(ld.get("encoder.after_norm.bias", D), D); }
     std::unique_ptr<tdx_pfenc> h(new tdx_pfenc());
-    h->device = device;
+    h->device = device; h->L = num_blocks; h->layers.resize(num_blocks);
+    for (int l = 0; l < num_blocks && ld.ok(); ++l)
+        pf_stage_layer(ld, l == 0 ? std::string("encoder.encoders0.0.") : "encoder.encoders." + std::to_string(l - 1) + ".", l == 0, h->layers[l]);
+    if (ld.ok()) { ld.push(h->ang, ld.get("encoder.after_norm.weight", D), D); ld.push(h->anb, ld.get("encoder.after_norm.bias", D), D); }
     TRY(ld.finish("tdx_pfenc_create", false, device, h->dev));
-    const float* dev = h->dev;
-    h->L = num_blocks; h->layers.resize(num_blocks);
-    h->ang = dev + ang; h->anb = dev + anb;
     {   // every nn.Linear weight as split-f16 planes + row scales, once
         std::vector<tdx::PlaneJob> jobs;
-        for (int l = 0; l < num_blocks; ++l) pf_bind_layer(dev, offs[l], l == 0, h->layers[l], jobs);
+        for (int l = 0; l < num_blocks; ++l) pf_queue_planes(l == 0, h->layers[l], jobs);
         TRY(tdx::split_weight_planes(jobs, device, h->dev_planes));
     }
     *out = h.release();
@@ -422,23 +417,21 @@ PfWork pf_carve(float* ws, long M, int B, int T) {
     k.slab = k.hs8 + 8 * al(M);                  // split-K partial sums of the small-row path
     return k;
 }
-void pf_stage_layer(tdx::Loader& ld, const std::string& p, bool wide, PfLayerOff& o) {
+void pf_stage_layer(tdx::Loader& ld, const std::string& p, bool wide, PfLayer& w) {
     const int din = wide ? DIN : D, dinp = wide ? DINP : D;
-    o.Wqkv = ld.push_rows_padded(ld.get(p + "self_attn.linear_q_k_v.weight", (size_t)3 * D * din), 3 * D, din, dinp);       // K padded 560 -> 576 with zeros
-    o.bqkv = ld.push(ld.get(p + "self_attn.linear_q_k_v.bias", 3 * D), 3 * D);
-    o.fsmnT = ld.push_tapmajor(ld.get(p + "self_attn.fsmn_block.weight", (size_t)D * KS), D, KS);
-    o.Wo = ld.push(ld.get(p + "self_attn.linear_out.weight", (size_t)D * D), (size_t)D * D);
-    o.bo = ld.push(ld.get(p + "self_attn.linear_out.bias", D), D);
-    o.W1 = ld.push(ld.get(p + "feed_forward.w_1.weight", (size_t)FFN * D), (size_t)FFN * D);
-    o.b1 = ld.push(ld.get(p + "feed_forward.w_1.bias", FFN), FFN);
-    o.W2 = ld.push(ld.get(p + "feed_forward.w_2.weight", (size_t)D * FFN), (size_t)D * FFN);
-    o.b2 = ld.push(ld.get(p + "feed_forward.w_2.bias", D), D);
-    o.n1g = ld.push(ld.get(p + "norm1.weight", din), din); o.n1b = ld.push(ld.get(p + "norm1.bias", din), din);
-    o.n2g = ld.push(ld.get(p + "norm2.weight", D), D); o.n2b = ld.push(ld.get(p + "norm2.bias", D), D);
+    ld.push_rows_padded(w.Wqkv, ld.get(p + "self_attn.linear_q_k_v.weight", (size_t)3 * D * din), 3 * D, din, dinp);       // K padded 560 -> 576 with zeros
+    ld.push(w.bqkv, ld.get(p + "self_attn.linear_q_k_v.bias", 3 * D), 3 * D);
+    ld.push_tapmajor(w.fsmnT, ld.get(p + "self_attn.fsmn_block.weight", (size_t)D * KS), D, KS);
+    ld.push(w.Wo, ld.get(p + "self_attn.linear_out.weight", (size_t)D * D), (size_t)D * D);
+    ld.push(w.bo, ld.get(p + "self_attn.linear_out.bias", D), D);
+    ld.push(w.W1, ld.get(p + "feed_forward.w_1.weight", (size_t)FFN * D), (size_t)FFN * D);
+    ld.push(w.b1, ld.get(p + "feed_forward.w_1.bias", FFN), FFN);
+    ld.push(w.W2, ld.get(p + "feed_forward.w_2.weight", (size_t)D * FFN), (size_t)D * FFN);
+    ld.push(w.b2, ld.get(p + "feed_forward.w_2.bias", D), D);
+    ld.push(w.n1g, ld.get(p + "norm1.weight", din), din); ld.push(w.n1b, ld.get(p + "norm1.bias", din), din);
+    ld.push(w.n2g, ld.get(p + "norm2.weight", D), D); ld.push(w.n2b, ld.get(p + "norm2.bias", D), D);
 }
-void pf_bind_layer(const float* dev, const PfLayerOff& o, bool wide, PfLayer& w, std::vector<tdx::PlaneJob>& jobs) {
-    w.Wqkv = dev + o.Wqkv; w.bqkv = dev + o.bqkv; w.fsmnT = dev + o.fsmnT; w.Wo = dev + o.Wo; w.bo = dev + o.bo; w.W1 = dev + o.W1;
-    w.b1 = dev + o.b1; w.W2 = dev + o.W2; w.b2 = dev + o.b2; w.n1g = dev + o.n1g; w.n1b = dev + o.n1b; w.n2g = dev + o.n2g; w.n2b = dev + o.n2b;
+void pf_queue_planes(bool wide, PfLayer& w, std::vector<tdx::PlaneJob>& jobs) {
     auto job = [&](const float* m, int N, int K, H3W& dst) { jobs.push_back({m, N, K, &dst.p, &dst.s}); };
     job(w.Wqkv, 3 * D, wide ? DINP : D, w.hqkv); job(w.Wo, D, D, w.ho);
     job(w.W1, FFN, D, w.h1); job(w.W2, D, FFN, w.h2);
@@ -709,7 +702,12 @@ __global__ __launch_bounds__(256) void pf_argmax_kernel(const float* __restrict_
     if (lane == 0) { ids[m] = bi; if (score) score[m] = -logf(s); }
 }
 
-struct PfDecLayer { H3W h1, h2, hq, hkv, ho; const float *W1, *W2, *Wq, *Wkv, *Wo; const float *b1, *fg, *fb, *n1g, *n1b, *n2g, *n2b, *n3g, *n3b, *fsmnT, *bq, *bkv, *bo; };
+struct PfDecLayer {
+    H3W h1, h2, hq, hkv, ho;
+    const float *W1 = nullptr, *W2 = nullptr, *Wq = nullptr, *Wkv = nullptr, *Wo = nullptr;
+    const float *b1 = nullptr, *fg = nullptr, *fb = nullptr, *n1g = nullptr, *n1b = nullptr, *n2g = nullptr, *n2b = nullptr, *n3g = nullptr,
+        *n3b = nullptr, *fsmnT = nullptr, *bq = nullptr, *bkv = nullptr, *bo = nullptr;
+};
 
 }  // namespace
 
@@ -726,7 +724,7 @@ struct tdx_pfdec {
     tdx::DevBuf dev, dev_planes;
     std::vector<PfDecLayer> layers; PfDecLayer d3;
     H3W hcif, hout;
-    const float *cifb, *cifw, *cifob, *ang, *anb, *bout, *Wout;
+    const float *cifb = nullptr, *cifw = nullptr, *cifob = nullptr, *ang = nullptr, *anb = nullptr, *bout = nullptr, *Wout = nullptr;
     PfTsHead ts;                    // the upsampling timestamp predictor (pf_timestamps.hpp), when the blob holds it
     bool cif_residual = true;       // relu(conv(x) + bias + x) (CifPredictorV2) or relu(conv(x) + bias) (V3, the predictor that carries the head)
 };
@@ -738,66 +736,53 @@ int tdx_pfdec_create(int num_blocks, int vocab, const void* blob, size_t blob_by
     tdx::Loader ld;       // (not strict, like the encoder)
     if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_pfdec_create: malformed TDXW blob");
     const int vpad = (vocab + 255) / 256 * 256;
-    struct Off { size_t W1, b1, W2, fg, fb, n1g, n1b, n2g, n2b, n3g, n3b, fsmnT, Wq, bq, Wkv, bkv, Wo, bo; };
-    std::vector<Off> offs(num_blocks + 1);
-    auto ffpart = [&](const std::string& p, Off& o) {
-        o.W1 = ld.push(ld.get(p + "feed_forward.w_1.weight", (size_t)FFN * D), (size_t)FFN * D);
-        o.b1 = ld.push(ld.get(p + "feed_forward.w_1.bias", FFN), FFN);
-        o.W2 = ld.push(ld.get(p + "feed_forward.w_2.weight", (size_t)D * FFN), (size_t)D * FFN);
-        o.fg = ld.push(ld.get(p + "feed_forward.norm.weight", FFN), FFN); o.fb = ld.push(ld.get(p + "feed_forward.norm.bias", FFN), FFN);
-        o.n1g = ld.push(ld.get(p + "norm1.weight", D), D); o.n1b = ld.push(ld.get(p + "norm1.bias", D), D);
+    std::unique_ptr<tdx_pfdec> h(new tdx_pfdec());
+    h->device = device; h->L = num_blocks; h->vocab = vocab; h->vpad = vpad;
+    h->layers.resize(num_blocks);
+    auto ffpart = [&](const std::string& p, PfDecLayer& w) {
+        ld.push(w.W1, ld.get(p + "feed_forward.w_1.weight", (size_t)FFN * D), (size_t)FFN * D);
+        ld.push(w.b1, ld.get(p + "feed_forward.w_1.bias", FFN), FFN);
+        ld.push(w.W2, ld.get(p + "feed_forward.w_2.weight", (size_t)D * FFN), (size_t)D * FFN);
+        ld.push(w.fg, ld.get(p + "feed_forward.norm.weight", FFN), FFN); ld.push(w.fb, ld.get(p + "feed_forward.norm.bias", FFN), FFN);
+        ld.push(w.n1g, ld.get(p + "norm1.weight", D), D); ld.push(w.n1b, ld.get(p + "norm1.bias", D), D);
     };
     for (int l = 0; l < num_blocks && ld.ok(); ++l) {
         const std::string p = "decoder.decoders." + std::to_string(l) + ".";
-        Off& o = offs[l];
-        ffpart(p, o);
-        o.n2g = ld.push(ld.get(p + "norm2.weight", D), D); o.n2b = ld.push(ld.get(p + "norm2.bias", D), D);
-        o.n3g = ld.push(ld.get(p + "norm3.weight", D), D); o.n3b = ld.push(ld.get(p + "norm3.bias", D), D);
-        o.fsmnT = ld.push_tapmajor(ld.get(p + "self_attn.fsmn_block.weight", (size_t)D * KS), D, KS);
-        o.Wq = ld.push(ld.get(p + "src_attn.linear_q.weight", (size_t)D * D), (size_t)D * D); o.bq = ld.push(ld.get(p + "src_attn.linear_q.bias", D), D);
-        o.Wkv = ld.push(ld.get(p + "src_attn.linear_k_v.weight", (size_t)2 * D * D), (size_t)2 * D * D); o.bkv = ld.push(ld.get(p + "src_attn.linear_k_v.bias", 2 * D), 2 * D);
-        o.Wo = ld.push(ld.get(p + "src_attn.linear_out.weight", (size_t)D * D), (size_t)D * D); o.bo = ld.push(ld.get(p + "src_attn.linear_out.bias", D), D);
+        PfDecLayer& w = h->layers[l];
+        ffpart(p, w);
+        ld.push(w.n2g, ld.get(p + "norm2.weight", D), D); ld.push(w.n2b, ld.get(p + "norm2.bias", D), D);
+        ld.push(w.n3g, ld.get(p + "norm3.weight", D), D); ld.push(w.n3b, ld.get(p + "norm3.bias", D), D);
+        ld.push_tapmajor(w.fsmnT, ld.get(p + "self_attn.fsmn_block.weight", (size_t)D * KS), D, KS);
+        ld.push(w.Wq, ld.get(p + "src_attn.linear_q.weight", (size_t)D * D), (size_t)D * D); ld.push(w.bq, ld.get(p + "src_attn.linear_q.bias", D), D);
+        ld.push(w.Wkv, ld.get(p + "src_attn.linear_k_v.weight", (size_t)2 * D * D), (size_t)2 * D * D); ld.push(w.bkv, ld.get(p + "src_attn.linear_k_v.bias", 2 * D), 2 * D);
+        ld.push(w.Wo, ld.get(p + "src_attn.linear_out.weight", (size_t)D * D), (size_t)D * D); ld.push(w.bo, ld.get(p + "src_attn.linear_out.bias", D), D);
     }
-    size_t cifW = 0, cifb = 0, cifw = 0, cifob = 0, ang = 0, anb = 0, Wout = 0, bout = 0;
+    size_t cifW = 0;       // (no field: only its planes are kept)
     if (ld.ok()) {
-        ffpart("decoder.decoders3.0.", offs[num_blocks]);
+        ffpart("decoder.decoders3.0.", h->d3);
         // Conv1d weight [out][in][3] -> [out][tap*512 + in]
         const float* cw = ld.get("predictor.cif_conv1d.weight", (size_t)D * D * 3);
         cifW = ld.room((size_t)D * 3 * D);
         if (cw) for (int o_ = 0; o_ < D; ++o_) for (int c = 0; c < D; ++c) for (int j = 0; j < 3; ++j)
             ld.host[cifW + (size_t)o_ * 3 * D + (size_t)j * D + c] = cw[((size_t)o_ * D + c) * 3 + j];
-        cifb = ld.push(ld.get("predictor.cif_conv1d.bias", D), D);
-        cifw = ld.push(ld.get("predictor.cif_output.weight", D), D);
-        cifob = ld.push(ld.get("predictor.cif_output.bias", 1), 1);
-        ang = ld.push(ld.get("decoder.after_norm.weight", D), D); anb = ld.push(ld.get("decoder.after_norm.bias", D), D);
-        Wout = ld.push(ld.get("decoder.output_layer.weight", (size_t)vocab * D), (size_t)vocab * D, (size_t)vpad * D);     // rows vocab..vpad-1 zero
-        bout = ld.push(ld.get("decoder.output_layer.bias", vocab), vocab, vpad);
+        ld.push(h->cifb, ld.get("predictor.cif_conv1d.bias", D), D);
+        ld.push(h->cifw, ld.get("predictor.cif_output.weight", D), D);
+        ld.push(h->cifob, ld.get("predictor.cif_output.bias", 1), 1);
+        ld.push(h->ang, ld.get("decoder.after_norm.weight", D), D); ld.push(h->anb, ld.get("decoder.after_norm.bias", D), D);
+        ld.push(h->Wout, ld.get("decoder.output_layer.weight", (size_t)vocab * D), (size_t)vocab * D, (size_t)vpad * D);     // rows vocab..vpad-1 zero
+        ld.push(h->bout, ld.get("decoder.output_layer.bias", vocab), vocab, vpad);
     }
-    PfTsOff tsoff{};
-    const bool has_ts = ld.ok() && pfts_stage(ld, tsoff);       // optional as a set: none of its tensors = no head, some = the first missing one is the error
-    std::unique_ptr<tdx_pfdec> h(new tdx_pfdec());
-    h->device = device; h->L = num_blocks; h->vocab = vocab; h->vpad = vpad;
+    const bool has_ts = ld.ok() && pfts_stage(ld, h->ts);       // optional as a set: none of its tensors = no head, some = the first missing one is the error
     TRY(ld.finish("tdx_pfdec_create", false, device, h->dev));
-    const float* dev = h->dev;
-    h->layers.resize(num_blocks);
     std::vector<tdx::PlaneJob> jobs;
     auto job = [&](const float* w, int N, int K, H3W& dst) { jobs.push_back({w, N, K, &dst.p, &dst.s}); };
-    auto bind_ff = [&](const Off& o, PfDecLayer& w) {
-        w.b1 = dev + o.b1; w.fg = dev + o.fg; w.fb = dev + o.fb; w.n1g = dev + o.n1g; w.n1b = dev + o.n1b;
-        w.W1 = dev + o.W1; w.W2 = dev + o.W2;
-        job(dev + o.W1, FFN, D, w.h1); job(dev + o.W2, D, FFN, w.h2);
-    };
-    for (int l = 0; l < num_blocks; ++l) {
-        const Off& o = offs[l]; PfDecLayer& w = h->layers[l];
-        bind_ff(o, w);
-        w.n2g = dev + o.n2g; w.n2b = dev + o.n2b; w.n3g = dev + o.n3g; w.n3b = dev + o.n3b; w.fsmnT = dev + o.fsmnT;
-        w.bq = dev + o.bq; w.bkv = dev + o.bkv; w.bo = dev + o.bo; w.Wq = dev + o.Wq; w.Wkv = dev + o.Wkv; w.Wo = dev + o.Wo;
-        job(dev + o.Wq, D, D, w.hq); job(dev + o.Wkv, 2 * D, D, w.hkv); job(dev + o.Wo, D, D, w.ho);
+    for (int l = 0; l <= num_blocks; ++l) {       // the last one is decoders3: feed-forward only
+        PfDecLayer& w = l < num_blocks ? h->layers[l] : h->d3;
+        job(w.W1, FFN, D, w.h1); job(w.W2, D, FFN, w.h2);
+        if (l < num_blocks) { job(w.Wq, D, D, w.hq); job(w.Wkv, 2 * D, D, w.hkv); job(w.Wo, D, D, w.ho); }
     }
-    bind_ff(offs[num_blocks], h->d3);
-    h->cifb = dev + cifb; h->cifw = dev + cifw; h->cifob = dev + cifob; h->ang = dev + ang; h->anb = dev + anb; h->bout = dev + bout; h->Wout = dev + Wout;
-    job(dev + cifW, D, 3 * D, h->hcif); job(dev + Wout, vpad, D, h->hout);
-    if (has_ts) { pfts_bind(dev, tsoff, h->ts, jobs); h->cif_residual = false; }
+    job(h->dev + cifW, D, 3 * D, h->hcif); job(h->Wout, vpad, D, h->hout);
+    if (has_ts) { pfts_queue_planes(h->ts, jobs); h->cif_residual = false; }
     TRY(tdx::split_weight_planes(jobs, device, h->dev_planes));
     *out = h.release();
     return TDX_OK;

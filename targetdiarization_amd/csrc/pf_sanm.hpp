@@ -1,6 +1,6 @@
 // pf_sanm.hpp — what the two models that stack funasr's SANM encoder layer share: Paraformer (paraformer.hip, where the layer,
 // its kernels and its dispatch thresholds live) and SenseVoiceSmall (sensevoice.hip).  ONE layer loop (pf_run_layers), ONE weight
-// staging (pf_stage_layer / pf_bind_layer), ONE workspace layout (PfWork); the functions are defined in paraformer.hip and are
+// staging (pf_stage_layer / pf_queue_planes), ONE workspace layout (PfWork); the functions are defined in paraformer.hip and are
 // internal to libtdx.so (C++ linkage: not part of the C-ABI).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,12 +13,16 @@
 #include "weight_planes.hpp"
 
 // one layer: d = 512, 4 heads, FFN 2048, FSMN memory of 11 taps, pre-LN (eps 1e-12); fp32 weights and the x3 planes of the Linears
-struct PfLayer { const float *Wqkv, *bqkv, *fsmnT, *Wo, *bo, *W1, *b1, *W2, *b2, *n1g, *n1b, *n2g, *n2b; tdx::H3W hqkv, ho, h1, h2; };
-struct PfLayerOff { size_t Wqkv, bqkv, fsmnT, Wo, bo, W1, b1, W2, b2, n1g, n1b, n2g, n2b; };      // offsets into the Loader's image
-// a layer's tensors under the funasr prefix p ("encoder.encoders.3.") into the Loader's image; wide: the 560 -> 512 layer (K padded to 576)
-void pf_stage_layer(tdx::Loader& ld, const std::string& p, bool wide, PfLayerOff& o);
-// ... bound to the uploaded image, its four Linears queued for split_weight_planes
-void pf_bind_layer(const float* dev, const PfLayerOff& o, bool wide, PfLayer& w, std::vector<tdx::PlaneJob>& jobs);
+struct PfLayer {
+    const float *Wqkv = nullptr, *bqkv = nullptr, *fsmnT = nullptr, *Wo = nullptr, *bo = nullptr, *W1 = nullptr, *b1 = nullptr, *W2 = nullptr,
+        *b2 = nullptr, *n1g = nullptr, *n1b = nullptr, *n2g = nullptr, *n2b = nullptr;
+    tdx::H3W hqkv, ho, h1, h2;
+};
+// a layer's tensors under the funasr prefix p ("encoder.encoders.3.") into the Loader's image, bound to w (an element of the handle's
+// vector at its final size: Loader::bind); wide: the 560 -> 512 layer (K padded to 576)
+void pf_stage_layer(tdx::Loader& ld, const std::string& p, bool wide, PfLayer& w);
+// after finish(): the layer's four Linears queued for split_weight_planes
+void pf_queue_planes(bool wide, PfLayer& w, std::vector<tdx::PlaneJob>& jobs);
 
 // the activations of a layer stack over M = B * T rows
 struct PfWork { float *x, *xin, *qkv, *sc, *ctx, *mem, *ffn; unsigned char* hp; float *hs, *hs8, *slab; };

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void pfts_norm_scan_kernel(const float* __rest
 
 }  // namespace
 
-bool pfts_stage(Loader& ld, PfTsOff& o) {
+bool pfts_stage(Loader& ld, PfTsHead& w) {
     int have = 0;
     for (const char* n : PFTS_TENSORS) have += ld.blob.find(n) ? 1 : 0;
     if (!have) return false;
@@ -156,31 +156,30 @@ bool pfts_stage(Loader& ld, PfTsOff& o) {
     // ConvTranspose1d weight [in][out][3] -> GEMM weight [j*512 + out][in]; the bias three times
     const float* cw = ld.get(PFTS_TENSORS[0], {d, d, (uint32_t)UPS});
     const float* cb = ld.get(PFTS_TENSORS[1], {d});
-    o.Wup = ld.room((size_t)UPS * D * D);
-    o.bup = ld.room((size_t)UPS * D);
+    const size_t Wup = ld.room(w.Wup, (size_t)UPS * D * D);
+    const size_t bup = ld.room(w.bup, (size_t)UPS * D);
     if (cw) for (int ci = 0; ci < D; ++ci) for (int co = 0; co < D; ++co) for (int j = 0; j < UPS; ++j)
-        ld.host[o.Wup + ((size_t)j * D + co) * D + ci] = cw[((size_t)ci * D + co) * UPS + j];
-    if (cb) for (int j = 0; j < UPS; ++j) for (int co = 0; co < D; ++co) ld.host[o.bup + (size_t)j * D + co] = cb[co];
+        ld.host[Wup + ((size_t)j * D + co) * D + ci] = cw[((size_t)ci * D + co) * UPS + j];
+    if (cb) for (int j = 0; j < UPS; ++j) for (int co = 0; co < D; ++co) ld.host[bup + (size_t)j * D + co] = cb[co];
     // both directions' W_ih as one [4096][512] matrix with rows dir*2048 + u*4 + gate, bias b_ih + b_hh; W_hh transposed
-    o.ih.N = XP; o.ih.Npad = XP; o.ih.Kp = D;
-    o.ih.w = ld.room((size_t)XP * D);
-    o.ih.b = ld.room(XP);
-    o.whhT = ld.room((size_t)2 * HID * GATES);
+    GemmW ih; ih.N = XP; ih.Npad = XP; ih.Kp = D;
+    ih.w = ld.room(w.Wih, (size_t)XP * D);
+    ih.b = ld.room(w.bih, XP);
+    const size_t whhT = ld.room(w.whhT, (size_t)2 * HID * GATES);
     for (int dir = 0; dir < 2; ++dir) {
         const float* wih = ld.get(PFTS_TENSORS[2 + 4 * dir], {g, d});
         const float* whh = ld.get(PFTS_TENSORS[3 + 4 * dir], {g, hd});
         const float* bi = ld.get(PFTS_TENSORS[4 + 4 * dir], {g});
         const float* bh = ld.get(PFTS_TENSORS[5 + 4 * dir], {g});
-        push_lstm_gates(ld, wih, whh, bi, bh, HID, D, o.ih, o.whhT, dir * GATES, true);
+        push_lstm_gates(ld, wih, whh, bi, bh, HID, D, ih, whhT, dir * GATES, true);
     }
-    o.w2 = ld.push(ld.get(PFTS_TENSORS[10], {1u, (uint32_t)YW}), YW);
-    o.b2 = ld.push(ld.get(PFTS_TENSORS[11], {1u}), 1);
+    ld.push(w.w2, ld.get(PFTS_TENSORS[10], {1u, (uint32_t)YW}), YW);
+    ld.push(w.b2, ld.get(PFTS_TENSORS[11], {1u}), 1);
     return true;
 }
 
-void pfts_bind(const float* dev, const PfTsOff& o, PfTsHead& w, std::vector<PlaneJob>& jobs) {
+void pfts_queue_planes(PfTsHead& w, std::vector<PlaneJob>& jobs) {
     w.present = true;
-    w.Wup = dev + o.Wup; w.bup = dev + o.bup; w.Wih = dev + o.ih.w; w.bih = dev + o.ih.b; w.whhT = dev + o.whhT; w.w2 = dev + o.w2; w.b2 = dev + o.b2;
     jobs.push_back({w.Wup, UPS * D, D, &w.hup.p, &w.hup.s});
     jobs.push_back({w.Wih, XP, D, &w.hih.p, &w.hih.s});
 }

@@ -13,17 +13,17 @@
 #include "weight_pack.hpp"
 #include "weight_planes.hpp"
 
-struct PfTsOff { size_t Wup, bup; tdx::GemmW ih; size_t whhT, w2, b2; };       // offsets into the Loader's image (ih: the LSTM input projection)
 struct PfTsHead {
     bool present = false;
     float smooth = 0.25f, noise = 0.01f;       // smooth_factor2, noise_threshold2
     tdx::H3W hup, hih;                         // x3 planes of the two GEMM weights
-    const float *Wup, *bup, *Wih, *bih, *whhT, *w2, *b2;
+    const float *Wup = nullptr, *bup = nullptr, *Wih = nullptr, *bih = nullptr, *whhT = nullptr, *w2 = nullptr, *b2 = nullptr;
 };
 // Stages the head's tensors when the blob holds any of them (a partial set leaves the first missing name in the Loader, so that
-// finish() fails with it); returns whether the head is there.
-bool pfts_stage(tdx::Loader& ld, PfTsOff& o);
-void pfts_bind(const float* dev, const PfTsOff& o, PfTsHead& w, std::vector<tdx::PlaneJob>& jobs);
+// finish() fails with it) and binds them to w, which sits in the heap-allocated handle (Loader::bind); returns whether the head is there.
+bool pfts_stage(tdx::Loader& ld, PfTsHead& w);
+// after finish(): marks the head present and queues its two GEMM weights for split_weight_planes
+void pfts_queue_planes(PfTsHead& w, std::vector<tdx::PlaneJob>& jobs);
 size_t pfts_work_floats(size_t B, size_t T);
 // enc [B,T,512], counts int32 [B] -> us_alphas [B,3T], us_peaks [B,3T]; tap (or NULL) [B,3T,1024] = the BLSTM output.
 // The first B*3T floats of ws hold the alphas before the re-normalisation on return.

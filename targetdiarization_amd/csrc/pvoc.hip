@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void resample_sinc_kernel(const float* __restr
     y[ch * n_store + m] = r;
 }
 
-struct Basis { Geo g; tdx::DevBuf dev; const float *Wa, *Ws, *win2; };
+struct Basis { Geo g; tdx::DevBuf dev; const float *Wa = nullptr, *Ws = nullptr, *win2 = nullptr; };
 
 int make_basis(int n_fft, int device, std::unique_ptr<Basis>& out) {
     const Geo g = geo(n_fft, n_fft / 4);
@@ -258,14 +258,12 @@ int make_basis(int n_fft, int device, std::unique_ptr<Basis>& out) {
     // analysis [2 * NPAIR][n_fft]: row k = hann * cos, row NPAIR + k = -hann * sin; rows of the bins nbin.. are zero
     // synthesis [n_fft][KS]: frame[n] = hann[n] / n_fft * sum_k w_k (re_k cos - im_k sin), w = 1 at DC and Nyquist, else 2
     const std::vector<double> win = tdx::hann_periodic(n_fft);
-    size_t oA, oS;
-    tdx::push_stft_basis(ld, g, win.data(), tdx::divided(win, n_fft).data(), oA, oS);
-    const size_t oW = ld.room((size_t)n_fft);
-    for (int n = 0; n < n_fft; ++n) ld.host[oW + n] = (float)(win[n] * win[n]);
     std::unique_ptr<Basis> b(new Basis());
+    b->g = g;
+    tdx::push_stft_basis(ld, g, win.data(), tdx::divided(win, n_fft).data(), b->Wa, b->Ws);
+    const size_t oW = ld.room(b->win2, (size_t)n_fft);
+    for (int n = 0; n < n_fft; ++n) ld.host[oW + n] = (float)(win[n] * win[n]);
     TRY(ld.finish("tdx_pvoc_prepare", false, device, b->dev));
-    const float* dev = b->dev;
-    b->g = g; b->Wa = dev + oA; b->Ws = dev + oS; b->win2 = dev + oW;
     out = std::move(b);
     return TDX_OK;
 }

@@ -172,7 +172,7 @@ struct tdx_sv {
     int L = 0, LT = 0, vocab = 0, vpad = 0, head = 1;
     tdx::DevBuf dev, dev_planes;
     std::vector<PfLayer> layers, tp;
-    const float *embed, *ang, *anb, *tng, *tnb, *Wctc, *bctc;
+    const float *embed = nullptr, *ang = nullptr, *anb = nullptr, *tng = nullptr, *tnb = nullptr, *Wctc = nullptr, *bctc = nullptr;
     H3W hctc;
 };
 
@@ -184,29 +184,26 @@ int tdx_sv_create(int num_blocks, int tp_blocks, int vocab, const void* blob, si
     if (!ld.parse(blob, blob_bytes)) return tdx::fail(TDX_E_BLOB, "tdx_sv_create: malformed TDXW blob");
     const int vpad = tdx::up(vocab, 256);
     const int nl = num_blocks + tp_blocks;
-    std::vector<PfLayerOff> offs(nl);
+    std::unique_ptr<tdx_sv> h(new tdx_sv());
+    h->device = device; h->L = num_blocks; h->LT = tp_blocks; h->vocab = vocab; h->vpad = vpad;
+    h->layers.resize(num_blocks); h->tp.resize(tp_blocks);
+    auto layer = [&](int l) -> PfLayer& { return l < num_blocks ? h->layers[l] : h->tp[l - num_blocks]; };
     for (int l = 0; l < nl && ld.ok(); ++l)
         pf_stage_layer(ld, l == 0 ? std::string("encoder.encoders0.0.")
                            : l < num_blocks ? "encoder.encoders." + std::to_string(l - 1) + "." : "encoder.tp_encoders." + std::to_string(l - num_blocks) + ".",
-                       l == 0, offs[l]);
-    size_t emb = 0, ang = 0, anb = 0, tng = 0, tnb = 0, Wc = 0, bc = 0;
+                       l == 0, layer(l));
     if (ld.ok()) {
-        emb = ld.push(ld.get("embed.weight", {(uint32_t)SV_EMBED_ROWS, (uint32_t)DIN}), (size_t)SV_EMBED_ROWS * DIN);
-        ang = ld.push(ld.get("encoder.after_norm.weight", D), D); anb = ld.push(ld.get("encoder.after_norm.bias", D), D);
-        tng = ld.push(ld.get("encoder.tp_norm.weight", D), D); tnb = ld.push(ld.get("encoder.tp_norm.bias", D), D);
-        Wc = ld.push(ld.get("ctc.ctc_lo.weight", {(uint32_t)vocab, (uint32_t)D}), (size_t)vocab * D, (size_t)vpad * D);     // rows vocab..vpad-1 zero (the x3 Linear's N)
-        bc = ld.push(ld.get("ctc.ctc_lo.bias", vocab), vocab, vpad);
+        ld.push(h->embed, ld.get("embed.weight", {(uint32_t)SV_EMBED_ROWS, (uint32_t)DIN}), (size_t)SV_EMBED_ROWS * DIN);
+        ld.push(h->ang, ld.get("encoder.after_norm.weight", D), D); ld.push(h->anb, ld.get("encoder.after_norm.bias", D), D);
+        ld.push(h->tng, ld.get("encoder.tp_norm.weight", D), D); ld.push(h->tnb, ld.get("encoder.tp_norm.bias", D), D);
+        ld.push(h->Wctc, ld.get("ctc.ctc_lo.weight", {(uint32_t)vocab, (uint32_t)D}), (size_t)vocab * D, (size_t)vpad * D);     // rows vocab..vpad-1 zero (the x3 Linear's N)
+        ld.push(h->bctc, ld.get("ctc.ctc_lo.bias", vocab), vocab, vpad);
     }
-    std::unique_ptr<tdx_sv> h(new tdx_sv());
-    h->device = device; h->L = num_blocks; h->LT = tp_blocks; h->vocab = vocab; h->vpad = vpad;
     const char* e = getenv("TDX_SV_HEAD");                // 1 = fused head kernel, 0 = row chunks through the x3 Linear; unset = the default
     h->head = e && *e ? (atoi(e) != 0) : 1;
     TRY(ld.finish("tdx_sv_create", false, device, h->dev));
-    const float* dev = h->dev;
-    h->layers.resize(num_blocks); h->tp.resize(tp_blocks);
     std::vector<tdx::PlaneJob> jobs;
-    for (int l = 0; l < nl; ++l) pf_bind_layer(dev, offs[l], l == 0, l < num_blocks ? h->layers[l] : h->tp[l - num_blocks], jobs);
-    h->embed = dev + emb; h->ang = dev + ang; h->anb = dev + anb; h->tng = dev + tng; h->tnb = dev + tnb; h->Wctc = dev + Wc; h->bctc = dev + bc;
+    for (int l = 0; l < nl; ++l) pf_queue_planes(l == 0, layer(l), jobs);
     if (!h->head) jobs.push_back({h->Wctc, vpad, D, &h->hctc.p, &h->hctc.s});
     TRY(tdx::split_weight_planes(jobs, device, h->dev_planes));
     if (h->head) {        // the fused head's 129 KB of dynamic LDS: a per-device attribute, set on this handle's device

@@ -198,25 +198,44 @@ struct Loader {
         return o;
     }
 
-    // the checks (a tensor missing; with `strict`, one nobody asked for — load_state_dict(strict=True)), then `device` is
-    // made current for the copy and the image goes to `dev`.  Returns a TDX status; nothing touches the device before the
-    // blob is accepted.
-    int finish(const char* fn, bool strict, int device, DevBuf& dev) {
+    // A handle that keeps pointers binds each `const float*` field to its image offset: the field is null until finish() has
+    // uploaded the image and then points at device base + offset.  The one rule: A BOUND FIELD MUST ALREADY SIT AT ITS FINAL
+    // ADDRESS — a member of the heap-allocated handle, or an element of a vector that already has its final size (resize the
+    // layer vectors before staging).  Never bind into a local that is copied or push_back'd afterwards.  The overloads below
+    // stage like their namesakes and bind what they return.
+    size_t bind(const float*& dst, size_t off) { dst = nullptr; bound_.emplace_back(&dst, off); return off; }
+    size_t room(const float*& dst, size_t n) { return bind(dst, room(n)); }
+    size_t push(const float*& dst, const float* p, size_t n, size_t npad = 0) { return bind(dst, push(p, n, npad)); }
+    size_t push_tapmajor(const float*& dst, const float* w, int C, int k) { return bind(dst, push_tapmajor(w, C, k)); }
+    size_t push_rows_padded(const float*& dst, const float* w, int N, int K, int Kp) { return bind(dst, push_rows_padded(w, N, K, Kp)); }
+
+    // the checks (a tensor missing; with `strict`, one nobody asked for — load_state_dict(strict=True))
+    int check(const char* fn, bool strict) const {
         if (!ok()) return fail(2, std::string(fn) + ": tensor missing or wrong " + (by_shape_ ? "shape: " : "size: ") + missing_);
         if (strict) {
             const std::string extra = blob.first_unused();
             if (!extra.empty()) return fail(2, std::string(fn) + ": unexpected tensor: " + extra);
         }
+        return 0;
+    }
+    // points every bound field at `base` + its offset (host work only: `base` is wherever the image lies)
+    void resolve(const float* base) const { for (const auto& b : bound_) *b.first = base + b.second; }
+    // check(), then `device` is made current for the copy and the image goes to `dev`, then resolve().  Returns a TDX status;
+    // nothing touches the device before the blob is accepted, and on any failure the bound fields stay null.
+    int finish(const char* fn, bool strict, int device, DevBuf& dev) {
+        TRY(check(fn, strict));
         DeviceGuard guard(device);
         if (guard.err != hipSuccess) return fail_hip(guard.err, __FILE__, __LINE__);
         const hipError_t e = dev.upload(host.data(), host.size() * sizeof(float));
         if (e != hipSuccess) return fail_hip(e, __FILE__, __LINE__);
+        resolve(dev);
         return 0;
     }
 
 private:
     std::string missing_;
     bool by_shape_ = false;
+    std::vector<std::pair<const float**, size_t>> bound_;
     const float* miss(const std::string& name, bool by_shape) {
         if (missing_.empty()) { missing_ = name; by_shape_ = by_shape; }
         return nullptr;

@@ -14,6 +14,8 @@ namespace tdx {
 // a packed GEMM B matrix [Npad][Kp] at `w` and its bias [Npad] at `b` (offsets into the image); N real rows.  A convolution's row
 // is `taps` groups of `cinp` channels.
 struct GemmW { size_t w = 0, b = 0; int N = 0, Npad = 0, Kp = 0, taps = 1, cinp = 0; };
+// a handle that keeps pointers binds the pair (Loader::bind) after push_linear / push_conv_gemm
+inline void bind(Loader& ld, const float*& W, const float*& b, const GemmW& g) { ld.bind(W, g.w); ld.bind(b, g.b); }
 
 // eval BatchNorm -> y = x * s + sh, in fp64 (g / be null: no affine part; mu / var null: identity)
 struct BN { std::vector<double> s, sh; };

@@ -788,29 +788,26 @@ AlignWs align_ws(size_t B, size_t nh, size_t max_rows, size_t S) {
     return w;
 }
 
-struct AttnW { const float *ln_g, *ln_b, *Wq, *bq, *Wk, *Wv, *bv, *Wo, *bo; };
-struct EncLayer { AttnW sa; const float *ln2_g, *ln2_b, *W1, *b1, *W2, *b2; };
-struct DecLayer { AttnW sa, ca; const float *ln3_g, *ln3_b, *W1, *b1, *W2, *b2; };
-struct AttnOff { size_t ln_g, ln_b, Wq, bq, Wk, Wv, bv, Wo, bo; };
-struct LayerOff { AttnOff sa, ca; size_t g, b, W1, b1, W2, b2; };
+struct AttnW { const float *ln_g = nullptr, *ln_b = nullptr, *Wq = nullptr, *bq = nullptr, *Wk = nullptr, *Wv = nullptr, *bv = nullptr, *Wo = nullptr, *bo = nullptr; };
+struct EncLayer { AttnW sa; const float *ln2_g = nullptr, *ln2_b = nullptr, *W1 = nullptr, *b1 = nullptr, *W2 = nullptr, *b2 = nullptr; };
+struct DecLayer { AttnW sa, ca; const float *ln3_g = nullptr, *ln3_b = nullptr, *W1 = nullptr, *b1 = nullptr, *W2 = nullptr, *b2 = nullptr; };
 
-size_t push_linear(Loader& ld, const std::string& name, int N, int K) {       // rows padded to the GEMM's 128-column tiles
-    return ld.push(ld.get(name, {(uint32_t)N, (uint32_t)K}), (size_t)N * K, (size_t)up(N, 128) * K);
+// the stage_* functions bind the fields of a layer that already sits in the handle's vector (Loader::bind)
+void push_linear(Loader& ld, const float*& dst, const std::string& name, int N, int K) {       // rows padded to the GEMM's 128-column tiles
+    ld.push(dst, ld.get(name, {(uint32_t)N, (uint32_t)K}), (size_t)N * K, (size_t)up(N, 128) * K);
 }
-void stage_attn(Loader& ld, const std::string& pre, const std::string& ln, int d, AttnOff& o) {
-    o.ln_g = ld.push(ld.get(ln + ".weight", d), d); o.ln_b = ld.push(ld.get(ln + ".bias", d), d);
-    o.Wq = push_linear(ld, pre + ".q_proj.weight", d, d); o.bq = ld.push(ld.get(pre + ".q_proj.bias", d), d);
-    o.Wk = push_linear(ld, pre + ".k_proj.weight", d, d);
-    o.Wv = push_linear(ld, pre + ".v_proj.weight", d, d); o.bv = ld.push(ld.get(pre + ".v_proj.bias", d), d);
-    o.Wo = push_linear(ld, pre + ".out_proj.weight", d, d); o.bo = ld.push(ld.get(pre + ".out_proj.bias", d), d);
+void stage_attn(Loader& ld, const std::string& pre, const std::string& ln, int d, AttnW& w) {
+    ld.push(w.ln_g, ld.get(ln + ".weight", d), d); ld.push(w.ln_b, ld.get(ln + ".bias", d), d);
+    push_linear(ld, w.Wq, pre + ".q_proj.weight", d, d); ld.push(w.bq, ld.get(pre + ".q_proj.bias", d), d);
+    push_linear(ld, w.Wk, pre + ".k_proj.weight", d, d);
+    push_linear(ld, w.Wv, pre + ".v_proj.weight", d, d); ld.push(w.bv, ld.get(pre + ".v_proj.bias", d), d);
+    push_linear(ld, w.Wo, pre + ".out_proj.weight", d, d); ld.push(w.bo, ld.get(pre + ".out_proj.bias", d), d);
 }
-void stage_ffn(Loader& ld, const std::string& pre, int d, int ffn, LayerOff& o) {
-    o.g = ld.push(ld.get(pre + "final_layer_norm.weight", d), d); o.b = ld.push(ld.get(pre + "final_layer_norm.bias", d), d);
-    o.W1 = push_linear(ld, pre + "fc1.weight", ffn, d); o.b1 = ld.push(ld.get(pre + "fc1.bias", ffn), ffn);
-    o.W2 = push_linear(ld, pre + "fc2.weight", d, ffn); o.b2 = ld.push(ld.get(pre + "fc2.bias", d), d);
-}
-AttnW bind_attn(const float* dev, const AttnOff& o) {
-    return AttnW{dev + o.ln_g, dev + o.ln_b, dev + o.Wq, dev + o.bq, dev + o.Wk, dev + o.Wv, dev + o.bv, dev + o.Wo, dev + o.bo};
+template <class Layer>      // EncLayer (final norm ln2_*) or DecLayer (ln3_*)
+void stage_ffn(Loader& ld, const std::string& pre, int d, int ffn, const float*& ln_g, const float*& ln_b, Layer& w) {
+    ld.push(ln_g, ld.get(pre + "final_layer_norm.weight", d), d); ld.push(ln_b, ld.get(pre + "final_layer_norm.bias", d), d);
+    push_linear(ld, w.W1, pre + "fc1.weight", ffn, d); ld.push(w.b1, ld.get(pre + "fc1.bias", ffn), ffn);
+    push_linear(ld, w.W2, pre + "fc2.weight", d, ffn); ld.push(w.b2, ld.get(pre + "fc2.bias", d), d);
 }
 
 double hz_to_mel(double f) { return f < 1000.0 ? 3.0 * f / 200.0 : 15.0 + std::log(f / 1000.0) * (27.0 / std::log(6.4)); }
@@ -866,7 +863,8 @@ struct tdx_whisper {
     int MP = 0;                       // mel channels of the conv1 rows (multiple of 32)
     tdx::DevBuf dev;
     int* pinned = nullptr;            // the host word the decode loop reads
-    const float *dft, *melw, *c1w, *c1b, *c2w, *c2b, *epos, *eln_g, *eln_b, *tok, *dpos, *dln_g, *dln_b;
+    const float *dft = nullptr, *melw = nullptr, *c1w = nullptr, *c1b = nullptr, *c2w = nullptr, *c2b = nullptr, *epos = nullptr,
+        *eln_g = nullptr, *eln_b = nullptr, *tok = nullptr, *dpos = nullptr, *dln_g = nullptr, *dln_b = nullptr;
     std::vector<EncLayer> enc;
     std::vector<DecLayer> dec;
     ~tdx_whisper() { if (pinned) (void)hipHostFree(pinned); }
@@ -936,10 +934,11 @@ int tdx_whisper_create(const tdx_whisper_config* cfg, const void* blob, size_t b
     const int d = c.d_model, MP = up(c.n_mels, 32), dP = up(d, 128);
     std::unique_ptr<tdx_whisper> h(new tdx_whisper());
     h->device = device; h->c = c; h->MP = MP;
+    h->enc.resize(c.enc_layers); h->dec.resize(c.dec_layers);
 
     // window x DFT basis, rows c (re) and NBINP + c (im); the Slaney mel bank [MELP][PWP]
-    size_t o_dft = ld.room((size_t)2 * NBINP * KFR), o_mel = ld.room((size_t)MELP * PWP);
-    tdx::fill_dft_analysis(ld.host.data() + o_dft, NFFT, NBIN, NBINP, KFR, tdx::hann_periodic(NFFT).data());
+    const size_t dft = ld.room(h->dft, (size_t)2 * NBINP * KFR), mel = ld.room(h->melw, (size_t)MELP * PWP);
+    tdx::fill_dft_analysis(ld.host.data() + dft, NFFT, NBIN, NBINP, KFR, tdx::hann_periodic(NFFT).data());
     {
         const int nm = c.n_mels;
         std::vector<double> ff(nm + 2);
@@ -950,50 +949,41 @@ int tdx_whisper_create(const tdx_whisper_config* cfg, const void* blob, size_t b
                 const double f = 8000.0 * b / (NBIN - 1);
                 const double down = (f - ff[j]) / (ff[j + 1] - ff[j]), upw = (ff[j + 2] - f) / (ff[j + 2] - ff[j + 1]);
                 const double v = std::max(0.0, std::min(down, upw)) * (2.0 / (ff[j + 2] - ff[j]));
-                ld.host[o_mel + (size_t)j * PWP + b] = (float)v;
+                ld.host[mel + (size_t)j * PWP + b] = (float)v;
             }
     }
     // conv weights [d][cin][3] -> [dP][3][cin padded]
-    size_t o_c1w = ld.room((size_t)dP * 3 * MP), o_c2w = ld.room((size_t)dP * 3 * d);
+    const size_t c1w = ld.room(h->c1w, (size_t)dP * 3 * MP), c2w = ld.room(h->c2w, (size_t)dP * 3 * d);
     if (const float* w = ld.get("model.encoder.conv1.weight", {(uint32_t)d, (uint32_t)c.n_mels, 3u}))
         for (int n = 0; n < d; ++n) for (int ci = 0; ci < c.n_mels; ++ci) for (int t = 0; t < 3; ++t)
-            ld.host[o_c1w + ((size_t)n * 3 + t) * MP + ci] = w[((size_t)n * c.n_mels + ci) * 3 + t];
+            ld.host[c1w + ((size_t)n * 3 + t) * MP + ci] = w[((size_t)n * c.n_mels + ci) * 3 + t];
     if (const float* w = ld.get("model.encoder.conv2.weight", {(uint32_t)d, (uint32_t)d, 3u}))
         for (int n = 0; n < d; ++n) for (int ci = 0; ci < d; ++ci) for (int t = 0; t < 3; ++t)
-            ld.host[o_c2w + ((size_t)n * 3 + t) * d + ci] = w[((size_t)n * d + ci) * 3 + t];
-    const size_t o_c1b = ld.push(ld.get("model.encoder.conv1.bias", d), d), o_c2b = ld.push(ld.get("model.encoder.conv2.bias", d), d);
-    const size_t o_epos = ld.push(ld.get("model.encoder.embed_positions.weight", {(uint32_t)c.n_audio_ctx, (uint32_t)d}), (size_t)c.n_audio_ctx * d);
-    std::vector<LayerOff> eo(c.enc_layers), dofs(c.dec_layers);
+            ld.host[c2w + ((size_t)n * 3 + t) * d + ci] = w[((size_t)n * d + ci) * 3 + t];
+    ld.push(h->c1b, ld.get("model.encoder.conv1.bias", d), d); ld.push(h->c2b, ld.get("model.encoder.conv2.bias", d), d);
+    ld.push(h->epos, ld.get("model.encoder.embed_positions.weight", {(uint32_t)c.n_audio_ctx, (uint32_t)d}), (size_t)c.n_audio_ctx * d);
     for (int l = 0; l < c.enc_layers; ++l) {
         const std::string p = "model.encoder.layers." + std::to_string(l) + ".";
-        stage_attn(ld, p + "self_attn", p + "self_attn_layer_norm", d, eo[l].sa);
-        stage_ffn(ld, p, d, c.enc_ffn, eo[l]);
+        EncLayer& w = h->enc[l];
+        stage_attn(ld, p + "self_attn", p + "self_attn_layer_norm", d, w.sa);
+        stage_ffn(ld, p, d, c.enc_ffn, w.ln2_g, w.ln2_b, w);
     }
-    const size_t o_elg = ld.push(ld.get("model.encoder.layer_norm.weight", d), d), o_elb = ld.push(ld.get("model.encoder.layer_norm.bias", d), d);
+    ld.push(h->eln_g, ld.get("model.encoder.layer_norm.weight", d), d); ld.push(h->eln_b, ld.get("model.encoder.layer_norm.bias", d), d);
     const float* tokp = ld.get("model.decoder.embed_tokens.weight", {(uint32_t)c.vocab, (uint32_t)d});
-    const size_t o_tok = ld.push(tokp, (size_t)c.vocab * d);
-    const size_t o_dpos = ld.push(ld.get("model.decoder.embed_positions.weight", {(uint32_t)c.n_text_ctx, (uint32_t)d}), (size_t)c.n_text_ctx * d);
+    ld.push(h->tok, tokp, (size_t)c.vocab * d);
+    ld.push(h->dpos, ld.get("model.decoder.embed_positions.weight", {(uint32_t)c.n_text_ctx, (uint32_t)d}), (size_t)c.n_text_ctx * d);
     for (int l = 0; l < c.dec_layers; ++l) {
         const std::string p = "model.decoder.layers." + std::to_string(l) + ".";
-        stage_attn(ld, p + "self_attn", p + "self_attn_layer_norm", d, dofs[l].sa);
-        stage_attn(ld, p + "encoder_attn", p + "encoder_attn_layer_norm", d, dofs[l].ca);
-        stage_ffn(ld, p, d, c.dec_ffn, dofs[l]);
+        DecLayer& w = h->dec[l];
+        stage_attn(ld, p + "self_attn", p + "self_attn_layer_norm", d, w.sa);
+        stage_attn(ld, p + "encoder_attn", p + "encoder_attn_layer_norm", d, w.ca);
+        stage_ffn(ld, p, d, c.dec_ffn, w.ln3_g, w.ln3_b, w);
     }
-    const size_t o_dlg = ld.push(ld.get("model.decoder.layer_norm.weight", d), d), o_dlb = ld.push(ld.get("model.decoder.layer_norm.bias", d), d);
+    ld.push(h->dln_g, ld.get("model.decoder.layer_norm.weight", d), d); ld.push(h->dln_b, ld.get("model.decoder.layer_norm.bias", d), d);
     if (const float* po = ld.get_optional("proj_out.weight", (size_t)c.vocab * d))
         if (tokp && memcmp(po, tokp, (size_t)c.vocab * d * sizeof(float)) != 0)
             return tdx::fail(TDX_E_BLOB, "tdx_whisper_create: proj_out.weight differs from model.decoder.embed_tokens.weight (the head is tied)");
     TRY(ld.finish("tdx_whisper_create", true, device, h->dev));
-    const float* dev = h->dev;
-    h->dft = dev + o_dft; h->melw = dev + o_mel; h->c1w = dev + o_c1w; h->c2w = dev + o_c2w; h->c1b = dev + o_c1b; h->c2b = dev + o_c2b;
-    h->epos = dev + o_epos; h->eln_g = dev + o_elg; h->eln_b = dev + o_elb; h->tok = dev + o_tok; h->dpos = dev + o_dpos;
-    h->dln_g = dev + o_dlg; h->dln_b = dev + o_dlb;
-    h->enc.resize(c.enc_layers); h->dec.resize(c.dec_layers);
-    for (int l = 0; l < c.enc_layers; ++l)
-        h->enc[l] = EncLayer{bind_attn(dev, eo[l].sa), dev + eo[l].g, dev + eo[l].b, dev + eo[l].W1, dev + eo[l].b1, dev + eo[l].W2, dev + eo[l].b2};
-    for (int l = 0; l < c.dec_layers; ++l)
-        h->dec[l] = DecLayer{bind_attn(dev, dofs[l].sa), bind_attn(dev, dofs[l].ca), dev + dofs[l].g, dev + dofs[l].b, dev + dofs[l].W1, dev + dofs[l].b1,
-                             dev + dofs[l].W2, dev + dofs[l].b2};
     {
         tdx::DeviceGuard guard(device);
         if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);

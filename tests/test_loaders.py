@@ -121,3 +121,64 @@ def test_transposed_tensor(lib, model):
     sd[name] = sd[name].t().contiguous()                        # same numel, other shape
     rc, err = _create(lib, model, sd)
     assert rc == 2 and name.encode() in err
+
+
+# ---- the Loader's pointer binding (Loader::bind / resolve), through the host-only hook tdx_diag_loader_bind ----
+BIND = dict(n=70, npad=130, L=2, C=5, k=3, N=6, K=10, Npad=8, Kp=16)
+
+
+@pytest.fixture(scope="module")
+def diag():
+    from targetdiarization_amd.build import build_lib
+    build_lib()
+    return _lib.diag()
+
+
+@lru_cache(maxsize=None)
+def _bind_tensors():
+    g = torch.Generator().manual_seed(0)
+    r = lambda *s: torch.randn(*s, generator=g)
+    b = BIND
+    sd = {"plain": r(b["n"]), "padded": r(b["n"]), "twice": r(b["n"]), "lin.weight": r(b["N"], b["K"]), "lin.bias": r(b["N"])}
+    for l in range(b["L"]):
+        sd[f"layers.{l}.tap"] = r(b["C"], b["k"])
+        sd[f"layers.{l}.rows"] = r(b["N"], b["K"])
+    return sd
+
+
+def _bind(diag, sd):
+    """-> (status, error text, bound fields that are not null, the tensors read back through their bound pointers)"""
+    b = BIND
+    sizes = [b["n"], b["npad"], b["n"], b["Npad"] * b["Kp"], b["Npad"]] + [b["k"] * b["C"], b["N"] * b["Kp"]] * b["L"]
+    blob = W.pack_blob(sd)
+    buf = (C.c_char * len(blob)).from_buffer_copy(blob)
+    out = torch.full((sum(sizes),), float("nan"))
+    nonnull = C.c_int(-1)
+    rc = diag.tdx_diag_loader_bind(buf, len(blob), *[b[k] for k in ("n", "npad", "L", "C", "k", "N", "K", "Npad", "Kp")],
+                                   out.data_ptr(), out.numel(), C.byref(nonnull))
+    return rc, diag.tdx_diag_last_error(), nonnull.value, out.split(sizes)
+
+
+def test_bound_pointers_read_back_what_was_staged(diag):
+    b, sd = BIND, _bind_tensors()
+    rc, err, nonnull, got = _bind(diag, sd)
+    assert rc == 0, err
+    assert nonnull == 5 + 2 * b["L"]
+    pad = torch.nn.functional.pad
+    want = [sd["plain"], pad(sd["padded"], (0, b["npad"] - b["n"])), 2.0 * sd["twice"],
+            pad(sd["lin.weight"], (0, b["Kp"] - b["K"], 0, b["Npad"] - b["N"])), pad(sd["lin.bias"], (0, b["Npad"] - b["N"]))]
+    for l in range(b["L"]):
+        want += [sd[f"layers.{l}.tap"].t(), pad(sd[f"layers.{l}.rows"], (0, b["Kp"] - b["K"]))]
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert torch.equal(g, w.contiguous().reshape(-1))        # bit for bit, the padding exactly zero
+
+
+@pytest.mark.parametrize("name", ["twice", "lin.bias", "layers.1.tap"])
+def test_bound_pointers_stay_null_when_a_tensor_is_missing(diag, name):
+    sd = dict(_bind_tensors())
+    del sd[name]
+    rc, err, nonnull, got = _bind(diag, sd)
+    assert rc == 2 and name.encode() in err
+    assert nonnull == 0
+    assert all(torch.isnan(g).all() for g in got)               # nothing was copied out
