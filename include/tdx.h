@@ -740,6 +740,35 @@ int tdx_pvoc_eq_match(tdx_pvoc* h, const float* src_dev, long n_src, const float
 long tdx_resample_sinc_length(long n_in, double ratio);
 int tdx_resample_sinc(const float* x_dev, int C, long n_in, double ratio, float* y_dev, long n_store, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Spectral clustering, the dense part (clustering.spectral_labels up to the eigenvectors) — DESIGN 8.24.  Stateless, all
+ * arithmetic in fp64, no floating-point atomics and fixed reduction orders: a call returns the same bits every time.
+ *      1 <= n <= 8192 (element indices are int, byte offsets size_t: L alone is 512 MiB at the cap), 1 <= d <= 65536.
+ *
+ *      tdx_spectral_laplacian: emb_dev [n][d] f32 -> L_dev [n][n] f64.  Rows are scaled to unit length, u = x / max(|x|, 1e-12);
+ *      A = U U^T, summed over d in ascending order with fma (A is symmetric to the bit); A_tap_dev (NULL or [n][n] f64) receives
+ *      this unpruned affinity.  Per row the `drop` smallest entries become 0, exactly those that
+ *      np.argsort(A, axis=1, kind="stable")[:, :drop] names: among equal values the lower column index is the smaller one, -0.0
+ *      equals 0.0, and the diagonal (= 1) takes part.  0 <= drop < n.  Then A <- (A + A^T) / 2, diagonal 0, and
+ *      L = diag(row sums) - A, each row sum in a fixed tree order.
+ *
+ *      tdx_symeig_lowest: the m lowest eigenpairs of the symmetric M_dev [n][n] (row-major, full storage, OVERWRITTEN),
+ *      1 <= m <= min(n, 16): w_dev [m] ascending, V_dev [n][m] row-major with orthonormal columns.  The direct route of LAPACK:
+ *      unblocked Householder tridiagonalisation (dsytd2; two launches per column, so about 2 n launches — a column with nothing
+ *      below its subdiagonal is skipped, H = I), bisection on Sturm counts from the Gershgorin interval (dstebz' pivmin rule, at
+ *      most 128 halvings), inverse iteration with partial pivoting (a zero pivot becomes eps |T|; computed eigenvalues closer
+ *      than 10 eps |T| are moved apart; start vectors are a fixed hash of (row, index); 5 iterations, after each one modified
+ *      Gram-Schmidt against all earlier vectors of the m), back-transformation by the stored reflectors.  M = 0 gives w = 0 and
+ *      the first m unit vectors.  Eigenvectors of a multiple eigenvalue are an orthonormal basis of its space, no particular one.
+ *
+ *      tdx_spectral_workspace_bytes(n, d, m): one size for both entries (symeig ignores d: pass 1); 0 for arguments outside
+ *      the limits.  Bad arguments are TDX_E_INVALID, a short workspace TDX_E_WORKSPACE, both before anything is launched.
+ * ---------------------------------------------------------------------------------- */
+size_t tdx_spectral_workspace_bytes(int n, int d, int m);
+int tdx_spectral_laplacian(const float* emb_dev, int n, int d, int drop, double* L_dev, double* A_tap_dev, void* workspace_dev,
+                           size_t workspace_bytes, void* stream);
+int tdx_symeig_lowest(double* M_dev, int n, int m, double* w_dev, double* V_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,9 @@ SIGNATURES = {
     "tdx_pvoc_eq_match": (_i, [_vp, _fp, C.c_long, _fp, C.c_long, _fp, _i, _i, _i, _fp, _fp, _vp, _vp, _fp, _vp, _sz, _vp]),
     "tdx_resample_sinc_length": (C.c_long, [C.c_long, C.c_double]),
     "tdx_resample_sinc": (_i, [_fp, _i, C.c_long, C.c_double, _fp, C.c_long, _vp]),
+    "tdx_spectral_workspace_bytes": (_sz, [_i, _i, _i]),
+    "tdx_spectral_laplacian": (_i, [_fp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "tdx_symeig_lowest": (_i, [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

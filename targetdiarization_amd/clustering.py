@@ -214,25 +214,16 @@ def merge_by_cosine(labels: np.ndarray, X: np.ndarray, threshold: float = 0.78) 
         labels[labels == ids[max(a, b)]] = ids[min(a, b)]
 
 
-def spectral_labels(X: np.ndarray, oracle_num: int | None = None, min_num: int = 20, pval: float = 0.022, min_pnum: int = 6,
-                    max_spks: int = 15, merge_threshold: float = 0.78, seed: int = 0) -> np.ndarray:
-    """X [n,d] embeddings -> labels [n] (0-based, in no particular order).  n < min_num: all zeros."""
-    from scipy.linalg import eigh
-    X = np.asarray(X, dtype=np.float64)
-    n = X.shape[0]
-    if n < min_num:
-        return np.zeros(n, dtype=np.int64)
-    U = _unit(X)
-    A = U @ U.T
-    drop = max(0, min(int((1.0 - pval) * n), n - min_pnum))          # per row: zero the `drop` smallest affinities
-    if drop:
-        idx = np.argsort(A, axis=1, kind="stable")[:, :drop]
-        np.put_along_axis(A, idx, 0.0, axis=1)
-    A = 0.5 * (A + A.T)
-    np.fill_diagonal(A, 0.0)
-    L = np.diag(A.sum(axis=1)) - A
-    m = min(max_spks + 1, n)
-    w, V = eigh(L, subset_by_index=[0, m - 1])
+def spectral_drop(n: int, pval: float = 0.022, min_pnum: int = 6) -> int:
+    """entries zeroed per row of the n x n affinity: all but the largest max(min_pnum, n - int((1 - pval) n))"""
+    return max(0, min(int((1.0 - pval) * n), n - min_pnum))
+
+
+def spectral_tail(w: np.ndarray, V: np.ndarray, X: np.ndarray, oracle_num: int | None = None, max_spks: int = 15,
+                  merge_threshold: float = 0.78, seed: int = 0) -> np.ndarray:
+    """lowest eigenvalues w [m] (ascending) and eigenvectors V [n,m] of the Laplacian, embeddings X [n,d] -> labels [n]: the speaker
+    count from the largest eigengap (or oracle_num), k-means on the first k eigenvectors, then the merge by cosine"""
+    n = V.shape[0]
     if oracle_num is not None:
         k = int(oracle_num)
     else:
@@ -243,3 +234,58 @@ def spectral_labels(X: np.ndarray, oracle_num: int | None = None, min_num: int =
     if oracle_num is None:
         labels = merge_by_cosine(labels, X, merge_threshold)
     return labels
+
+
+def spectral_labels(X: np.ndarray, oracle_num: int | None = None, min_num: int = 20, pval: float = 0.022, min_pnum: int = 6,
+                    max_spks: int = 15, merge_threshold: float = 0.78, seed: int = 0) -> np.ndarray:
+    """X [n,d] embeddings -> labels [n] (0-based, in no particular order).  n < min_num: all zeros."""
+    from scipy.linalg import eigh
+    X = np.asarray(X, dtype=np.float64)
+    n = X.shape[0]
+    if n < min_num:
+        return np.zeros(n, dtype=np.int64)
+    U = _unit(X)
+    A = U @ U.T
+    drop = spectral_drop(n, pval, min_pnum)                          # per row: zero the `drop` smallest affinities
+    if drop:
+        idx = np.argsort(A, axis=1, kind="stable")[:, :drop]
+        np.put_along_axis(A, idx, 0.0, axis=1)
+    A = 0.5 * (A + A.T)
+    np.fill_diagonal(A, 0.0)
+    L = np.diag(A.sum(axis=1)) - A
+    m = min(max_spks + 1, n)
+    w, V = eigh(L, subset_by_index=[0, m - 1])
+    return spectral_tail(w, V, X, oracle_num, max_spks, merge_threshold, seed)
+
+
+SPECTRAL_DEVICE_MAX_N = 8192      # tdx_spectral_laplacian / tdx_symeig_lowest: element indices are int
+
+
+def spectral_labels_device(X_dev, oracle_num: int | None = None, min_num: int = 20, pval: float = 0.022, min_pnum: int = 6,
+                           max_spks: int = 15, merge_threshold: float = 0.78, seed: int = 0) -> np.ndarray:
+    """spectral_labels for embeddings X_dev [n,d] that lie on the device (float32 torch tensor): affinity, pruning, Laplacian and
+    its lowest eigenpairs on the device (ops.spectral_eig, csrc/spectral.hip); eigenvalues, the [n,16] eigenvectors and X come to the
+    host for spectral_tail, the same function the host path ends with.  More than 8192 embeddings, more than 15 speakers or a
+    device error: the reason is printed and the host function runs."""
+    n = int(X_dev.shape[0])
+    if n < min_num:
+        return np.zeros(n, dtype=np.int64)
+    kw = dict(oracle_num=oracle_num, max_spks=max_spks, merge_threshold=merge_threshold, seed=seed)
+    m = min(max_spks + 1, n)
+    why = None
+    if n > SPECTRAL_DEVICE_MAX_N:
+        why = f"{n} embeddings exceed the device limit of {SPECTRAL_DEVICE_MAX_N}"
+    elif m > 16:
+        why = f"max_spks = {max_spks} needs more than the 16 eigenpairs the device returns"
+    else:
+        from . import _lib, ops
+        try:
+            w, V = ops.spectral_eig(X_dev, spectral_drop(n, pval, min_pnum), m=m)
+            w, V = w.cpu().numpy(), V.cpu().numpy()
+        except _lib.TdxError as err:
+            why = str(err)
+    X = X_dev.detach().cpu().numpy().astype(np.float64)
+    if why is not None:
+        print(f"spectral_labels_device: {why}; clustering on the host")
+        return spectral_labels(X, min_num=min_num, pval=pval, min_pnum=min_pnum, **kw)
+    return spectral_tail(w, V, X, **kw)

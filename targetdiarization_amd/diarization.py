@@ -3,7 +3,7 @@
 Restates modelscope's segmentation-clustering pipeline `iic/speech_campplus_speaker-diarization_common`
 [upstream-recall: the package is third-party and absent; DESIGN §8.10 is the governing description]:
     speech ranges (the `vad` plug-in) -> 1.5 s windows at a 0.75 s shift -> CAM++ embeddings (csrc/campplus.hip, ONE bucketed
-    launch sequence for all windows) -> spectral clustering (clustering.spectral_labels) -> time post-processing.
+    launch sequence for all windows) -> spectral clustering (clustering.spectral_labels, or spectral_labels_device) -> time post-processing.
 The host logic is plain functions over an `embed(list_of_windows) -> [n,192]` callable, so that it runs on the CPU against
 an oracle embedder; `CamppDiarizer` binds it to `SpeakerEmbedder.embed_device`.
 """
@@ -92,8 +92,10 @@ def postprocess(windows, labels, min_dur: float = 1.0):
 
 
 def diarize(audio: np.ndarray, embed: Callable, vad: Optional[Callable] = None, oracle_num: Optional[int] = None,
-            return_windows: bool = False, **cluster_kw):
-    """audio: 16 kHz mono float waveform -> {"text": [[start_s, end_s, label], ...]} (intervals.sd_result_parser's input)"""
+            return_windows: bool = False, cluster: Callable = spectral_labels, **cluster_kw):
+    """audio: 16 kHz mono float waveform -> {"text": [[start_s, end_s, label], ...]} (intervals.sd_result_parser's input).
+    `cluster(embeddings, oracle_num=..., **cluster_kw) -> labels` receives the embeddings as a float64 array, or, where `embed`
+    returns a torch tensor, that tensor as it is (clustering.spectral_labels_device takes it on the device)."""
     audio = np.asarray(audio, dtype=np.float32).reshape(-1)
     n = audio.shape[0]
     ranges = vad(audio) if vad is not None else ([[0.0, n / SR]] if n else [])
@@ -101,28 +103,45 @@ def diarize(audio: np.ndarray, embed: Callable, vad: Optional[Callable] = None, 
     if not windows:
         res = {"text": []}
         return (res, [], np.zeros(0, dtype=np.int64)) if return_windows else res
-    emb = np.asarray(embed(cut_windows(audio, windows)), dtype=np.float64)
-    labels = spectral_labels(emb, oracle_num=oracle_num, **cluster_kw)
+    emb = embed(cut_windows(audio, windows))
+    if not hasattr(emb, "data_ptr"):            # a device tensor goes to `cluster` as it is
+        emb = np.asarray(emb, dtype=np.float64)
+    labels = np.asarray(cluster(emb, oracle_num=oracle_num, **cluster_kw))
     res = {"text": postprocess(windows, labels)}
     return (res, windows, labels) if return_windows else res
 
 
 class CamppDiarizer:
-    """`sd_pipeline` on the device: window embeddings from SpeakerEmbedder(arch="campplus").embed_device, clustering on the host."""
+    """`sd_pipeline` on the device: window embeddings from SpeakerEmbedder(arch="campplus").embed_device.  cluster="host" (the default):
+    the embeddings come to the host and clustering.spectral_labels runs there.  cluster="device": they stay on the device, the affinity,
+    the Laplacian and its eigenvectors are computed there (clustering.spectral_labels_device, csrc/spectral.hip) and only the [n,16]
+    eigenvectors and the embeddings come back for the shared k-means / merge tail."""
 
-    def __init__(self, state_dict, cuda_device: int = 0, vad: Optional[Callable] = None, max_batch_frames: int = 40000, **cluster_kw):
+    def __init__(self, state_dict, cuda_device: int = 0, vad: Optional[Callable] = None, max_batch_frames: int = 40000,
+                 cluster: str = "host", **cluster_kw):
         from .speaker import SpeakerEmbedder
+        if cluster not in ("host", "device"):
+            raise ValueError(f"CamppDiarizer: cluster must be \"host\" or \"device\", not {cluster!r}")
+        self.cluster = cluster
         self.embedder = SpeakerEmbedder(state_dict, cuda_device=cuda_device, max_batch_frames=max_batch_frames, arch="campplus")
         self.vad = vad
         self.cluster_kw = cluster_kw
 
     def embed(self, windows):
         """list of equal-length float32 arrays -> [n,192] array: ONE upload, one bucketed launch sequence"""
-        import torch
         if not windows:
             return np.zeros((0, 192), dtype=np.float32)
+        return self.embed_device(windows).cpu().numpy()
+
+    def embed_device(self, windows):
+        """the same, the [n,192] float32 result left on the device (n >= 1)"""
+        import torch
         x = torch.from_numpy(np.stack(windows)).to(self.embedder.device)
-        return self.embedder.embed_device(list(x)).cpu().numpy()
+        return self.embedder.embed_device(list(x))
 
     def __call__(self, audio_16k, oracle_num: Optional[int] = None, return_windows: bool = False):
+        if self.cluster == "device":
+            from .clustering import spectral_labels_device
+            return diarize(audio_16k, self.embed_device, vad=self.vad, oracle_num=oracle_num, return_windows=return_windows,
+                           cluster=spectral_labels_device, **self.cluster_kw)
         return diarize(audio_16k, self.embed, vad=self.vad, oracle_num=oracle_num, return_windows=return_windows, **self.cluster_kw)

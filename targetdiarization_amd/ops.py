@@ -74,6 +74,27 @@ def loudness(wav: torch.Tensor, rate: int = 16000) -> torch.Tensor:
     return out
 
 
+def spectral_eig(emb: torch.Tensor, drop: int, m: int = 16, return_taps: bool = False):
+    """clustering.spectral_labels up to the eigenvectors, on the device (tdx_spectral_laplacian + tdx_symeig_lowest): emb [n,d] fp32 ->
+    (w [m], V [n,m]) float64, the m <= min(n, 16) lowest eigenpairs of the Laplacian of the cosine affinity whose `drop` smallest entries
+    per row were zeroed.  return_taps: also a dict with the unpruned affinity "A" and the Laplacian "L" ([n,n] float64, copies)."""
+    emb = emb.contiguous().float()
+    n, d = emb.shape
+    l = _lib.lib()
+    nb = int(l.tdx_spectral_workspace_bytes(n, d, m))
+    if nb == 0:
+        raise _lib.TdxError(f"spectral_eig: need 1 <= n <= 8192, 1 <= m <= min(n, 16), d >= 1 (n = {n}, d = {d}, m = {m})")
+    ws = torch.empty(nb, dtype=torch.uint8, device=emb.device)
+    L = torch.empty(n, n, dtype=torch.float64, device=emb.device)
+    A = torch.empty(n, n, dtype=torch.float64, device=emb.device) if return_taps else None
+    _lib.check(l.tdx_spectral_laplacian(emb.data_ptr(), n, d, int(drop), L.data_ptr(), A.data_ptr() if return_taps else None, ws.data_ptr(), nb, _st(emb)))
+    taps = {"A": A, "L": L.clone()} if return_taps else None
+    w = torch.empty(m, dtype=torch.float64, device=emb.device)
+    V = torch.empty(n, m, dtype=torch.float64, device=emb.device)
+    _lib.check(l.tdx_symeig_lowest(L.data_ptr(), n, m, w.data_ptr(), V.data_ptr(), ws.data_ptr(), nb, _st(emb)))
+    return (w, V, taps) if return_taps else (w, V)
+
+
 _RESAMPLE_FILTERS = {}
 
 

@@ -24,7 +24,8 @@ order of its steps, with two differences that are the point of the rewrite:
     `asr_engine="whisper_v2"` / `"whisper_v3"` (the same weights, or `whisper_model_dir` = one OpenAI-format .pt file) also asks for word
     timestamps: the words go to the diarization chunks by their start times, as Paraformer's tokens do.
     `sd_state_dict` (CAM++ weights, 3D-Speaker names) or a `diarization_pipeline_dir` holding campplus_cn_common.bin puts the
-    device diarizer (diarization.CamppDiarizer, csrc/campplus.hip) behind sd_pipeline.
+    device diarizer (diarization.CamppDiarizer, csrc/campplus.hip) behind sd_pipeline; `sd_cluster="device"` also moves its spectral
+    clustering up to the eigenvectors onto the device (csrc/spectral.hip; the default "host" clusters on the host as before).
     Defaults: one segment per utterance / no overlap detector / whole clip is speech / the device decoder / text unchanged.
 The MDX denoiser body runs on the device when `mdx_state_dict` is given (mdx.ConvTDFNetBody, or any `mdx_model` callable); the
 Apollo restorer of hot loop B when `restorer_state_dict` is given or `restorer_weights_folder` names a directory holding
@@ -64,7 +65,7 @@ class TargetDiarization:
                  od_state_dict=None, od_embed: Optional[Callable] = None, od_embed_state_dict=None, od_embed_model_dir=None,
                  sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None, sensevoice_model_dir=None,
                  sensevoice_token_file=None, whisper_state_dict=None, whisper_config=None, whisper_model_dir=None, whisper_token_list=None,
-                 whisper_tokenizer=None, whisper_generation_config=None, noise_reduce: bool = False, **kwargs):
+                 whisper_tokenizer=None, whisper_generation_config=None, noise_reduce: bool = False, sd_cluster: str = "host", **kwargs):
         self.target_similarity_threshold = target_similarity_threshold
         self.noise_reduce = bool(noise_reduce)    # noisereduce's spectral gate on the device as denoise_vocal's body when the MDX denoiser is off
         self.asr_engine = asr_engine
@@ -92,7 +93,7 @@ class TargetDiarization:
                     sd_state_dict = torch.load(ckpt, map_location="cpu", weights_only=True)
             if sd_state_dict is not None:
                 from .diarization import CamppDiarizer
-                self.sd_pipeline = CamppDiarizer(sd_state_dict, cuda_device=cuda_device, vad=self.vad)
+                self.sd_pipeline = CamppDiarizer(sd_state_dict, cuda_device=cuda_device, vad=self.vad, cluster=sd_cluster)
         self.hp = HotPath(sep_state_dict, spk_state_dict, asr_state_dict, cuda_device=cuda_device, mdx_model=mdx_model,
                           mdx_weights_file=mdx_weights_file, mdx_state_dict=mdx_state_dict, mdx_args=mdx_args,
                           restorer_state_dict=restorer_state_dict, restorer_weights_folder=restorer_weights_folder,
