@@ -497,7 +497,7 @@ int tdx_ctc_collapse(const int* frame_ids_dev, int B, int S, int blank, int* tok
  * N10  Whisper — replaces `AutoModelForSpeechSeq2Seq.from_pretrained(dir)` + `generate(input_features, task="transcribe",
  *      language="chinese", num_beams=1, prompt_ids=...)` (ASRProcessor.py:244-251, 489-514; Hugging Face transformers'
  *      WhisperForConditionalGeneration, pinned by tests/test_whisper_host.py).  fp32 throughout (the reference runs .half()),
- *      greedy decoding only, one prefix per call.
+ *      greedy decoding only, one prefix per call or, in tdx_whisper_decode_ts, one per row.
  *      create enforces, each with its own message: d_model / heads == 64 (encoder and decoder), gelu != 0 (activation_function
  *      "gelu", the exact erf form), n_mels 80 or 128, 1 <= n_audio_ctx, n_text_ctx <= 32768, vocab >= 2, layers >= 1, the FFN
  *      widths positive multiples of 64.
@@ -530,6 +530,38 @@ int tdx_ctc_collapse(const int* frame_ids_dev, int B, int S, int blank, int* tok
  *      receives no more rows; rows no step reached are left untouched.  step_ids_dev, step_scores_dev and counts_dev are
  *      bit-identical to tdx_whisper_decode's on the same inputs.  Rejected before any device call, each with its own message: nh
  *      outside [1, 64], max_rows < 1, first_row < 0, a NULL heads_host / xattn_dev, a (layer, head) pair outside the decoder.
+ *
+ *      Long-form transcription with timestamp tokens (whisper.transcribe / transformers' long-form generate):
+ *      tdx_whisper_logmel_long: WhisperFeatureExtractor with truncation=False on ONE clip of N samples (1 <= N <= 2^30) on the
+ *      device: no cut or pad to 320 * n_audio_ctx samples, F = N / 160 frames, and the clamp at maximum - 8 is taken over the whole
+ *      clip.  feat_dev [n_mels, F].  N < 160: no frame, nothing is written.  The reflect padding mirrors as often as a short clip
+ *      needs (numpy's "reflect").  The frames go through the same window x DFT and mel GEMMs in blocks of 4096, so the workspace
+ *      (tdx_whisper_logmel_long_workspace_bytes; 0 for a bad argument) does not grow with N beyond one block.
+ *      tdx_whisper_decode_ts: tdx_whisper_decode with per-row prefixes, Whisper's timestamp rules, the no-speech probability and
+ *      an optional capture of the alignment heads.  prefix_host [B][max_prefix], prefix_len_host [B] (1 <= len <= max_prefix, len
+ *      < n_text_ctx): row b feeds its own prefix one id per step and then generates at most min(max_new_host[b], n_text_ctx -
+ *      prefix_len[b]) ids from position prefix_len[b]; outputs at [b][p] as in tdx_whisper_decode.  begin_host NULL or [B], 1 <=
+ *      begin[b] <= prefix_len[b] (NULL: prefix_len): the ids of row b from position begin[b] on are its history `seq` (transformers'
+ *      begin_index); with begin < prefix_len the tail of the prefix counts as already generated.  Per step, after the static
+ *      suppress / begin_suppress masks (begin_suppress at the step that predicts position begin[b]), with tb = no_timestamps_id + 1:
+ *      no_timestamps_id is denied; seq ends in a timestamp and the id before it is one too (or len(seq) < 2): every id >= tb is
+ *      denied; seq ends in a timestamp after a text id: every id < eos is denied; seq holds a timestamp: ids in [tb, last) are
+ *      denied, last = the last timestamp if seq ends in a timestamp that follows a text id, else that id + 1; at the step that
+ *      predicts position begin[b]: every id < tb is denied, and every id > tb + max_initial_timestamp_index when that is >= 0;
+ *      then, over what is still allowed, if the log-sum-exp of the logits >= tb exceeds (strictly) the largest logit < tb, every
+ *      id < tb is denied.  The result is the argmax of what remains (ties: the lowest id) and its log-softmax over what remains
+ *      (WhisperTimeStampLogitsProcessor applied last, as _retrieve_logit_processors orders it).  A max_initial_timestamp_index past
+ *      the last timestamp id is clamped to it (negative: no limit).  If the masks and the rules leave no id at all (a suppress list
+ *      that covers a whole class, say), the row emits eos with score +inf, as tdx_whisper_decode does.  Steps that predict a position
+ *      below begin[b] score the prefix under an empty history.  The head keeps two running (max, argmax, sum exp) triples per row
+ *      and 64-column slice, one per class of ids; the [B, vocab] logits are never stored.  nospeech_dev NULL or float [B]: the
+ *      softmax probability of no_speech_id over the whole vocabulary, no mask, at the step that feeds position sot_pos_host[b]
+ *      (the row's <|startoftranscript|>).  heads_host NULL (no capture) or as in tdx_whisper_decode_xattn, with first_row_host NULL
+ *      or [B] (NULL: prefix_len[b]).  A row's results do not depend on the other rows of its batch.  Rejected before the device
+ *      is touched, each with its own message: a prefix that leaves no room (prefix_len >= n_text_ctx), tb outside the vocabulary,
+ *      eos >= tb, sot_pos outside the prefix, begin outside [1, prefix_len], a negative max_new or first_row, and
+ *      tdx_whisper_decode_xattn's capture checks.  tdx_whisper_decode and tdx_whisper_decode_xattn are unchanged: the three share
+ *      the decoder-layer launches, and each has its own head and step kernels.
  *
  *      tdx_token_align: token times from those rows, as transformers' _extract_token_timestamps (no model handle; the current
  *      device).  xattn_dev [B][nh][max_rows][n_audio_ctx]; per clip on the DEVICE nrows_dev[b] (0 .. max_rows, clamped) and
@@ -564,6 +596,15 @@ int tdx_whisper_decode_xattn(tdx_whisper* h, const float* enc_state_dev, int B, 
                              int n_suppress, const int* begin_suppress_host, int n_begin, int eos, int max_new, const int* heads_host, int nh,
                              int first_row, int max_rows, float* xattn_dev, int* step_ids_dev, float* step_scores_dev, int* counts_dev,
                              void* workspace_dev, size_t workspace_bytes, void* stream);
+size_t tdx_whisper_logmel_long_workspace_bytes(const tdx_whisper* h, long N);
+int tdx_whisper_logmel_long(tdx_whisper* h, const float* wav_dev, long N, float* feat_dev, void* workspace_dev, size_t workspace_bytes,
+                            void* stream);
+int tdx_whisper_decode_ts(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int max_prefix, const int* prefix_len_host,
+                          const int* begin_host, const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int eos,
+                          int no_timestamps_id, int max_initial_timestamp_index, const int* max_new_host, int no_speech_id,
+                          const int* sot_pos_host, float* nospeech_dev, const int* heads_host, int nh, const int* first_row_host, int max_rows,
+                          float* xattn_dev, int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* workspace_dev,
+                          size_t workspace_bytes, void* stream);
 size_t tdx_token_align_workspace_bytes(int B, int nh, int max_rows, int n_audio_ctx);
 int tdx_token_align(const float* xattn_dev, int B, int nh, int max_rows, int n_audio_ctx, const int* nrows_dev, const int* nframes_dev,
                     int median_width, int* frames_dev, float* matrix_dev, void* workspace_dev, size_t workspace_bytes, void* stream);

@@ -155,6 +155,11 @@ SIGNATURES = {
     "tdx_whisper_decode": (_i, [_vp, _fp, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, _i, _i, _vp, _fp, _vp, _vp, _sz, _vp]),
     "tdx_whisper_decode_xattn": (_i, [_vp, _fp, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, _i, _i,
                                       C.POINTER(C.c_int), _i, _i, _i, _fp, _vp, _fp, _vp, _vp, _sz, _vp]),
+    "tdx_whisper_logmel_long_workspace_bytes": (_sz, [_vp, C.c_long]),
+    "tdx_whisper_logmel_long": (_i, [_vp, _fp, C.c_long, _fp, _vp, _sz, _vp]),
+    "tdx_whisper_decode_ts": (_i, [_vp, _fp, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _i,
+                                   C.POINTER(C.c_int), _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _fp, C.POINTER(C.c_int), _i,
+                                   C.POINTER(C.c_int), _i, _fp, _vp, _fp, _vp, _vp, _sz, _vp]),
     "tdx_token_align_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "tdx_token_align": (_i, [_fp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _fp, _vp, _sz, _vp]),
     "tdx_ngate_create": (_i, [_i, C.POINTER(_vp)]),

@@ -14,6 +14,8 @@ import numpy as np
 
 
 class ASRProcessor:
+    whisper_long_form = False                        # (an instance made without __init__ keeps the one-window path)
+
     def __init__(self, is_asr: bool = False, fast_asr: bool = False, asr_model_dir=None, is_vad: bool = False, vad_model_dir: str = "",
                  is_punc: bool = False, punc_model_dir: str = "", is_timestamp: bool = False, timestamp_model_dir: str = "",
                  is_emotion: bool = False, emotion_model_dir: str = "", is_diarization: bool = False, diarization_model_dir: str = "",
@@ -23,8 +25,9 @@ class ASRProcessor:
                  sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None,
                  whisper_state_dict=None, whisper_config=None, whisper_token_list=None, whisper_tokenizer=None, whisper_generation_config=None,
                  whisper_engine: str = "whisper_finetune", whisper_alignment_heads=None,
-                 emotion_state_dict=None, emotion_config=None, emotion_labels=None):
+                 emotion_state_dict=None, emotion_config=None, emotion_labels=None, whisper_long_form: bool = False):
         self.is_asr = is_asr
+        self.whisper_long_form = bool(whisper_long_form)  # whisper_v2 / whisper_v3: clips over 30 s go through WhisperASR.transcribe
         self.verbose_log = verbose_log
         self.ap = ap
         self.cuda_device = cuda_device
@@ -318,13 +321,24 @@ class ASRProcessor:
                 prompt_ids = m.tokenizer.get_prompt_ids(prompt)
             elif prompt:
                 print("Whisper: no tokenizer loaded, the prompt is ignored.")
-            clips = [np.asarray(w, dtype=np.float32).reshape(-1)[:480000] for w in wavs]     # one 30 s segment per clip (no long-form loop)
             auto = language is None or str(language).lower() == "auto"
+            from .whisper import language_code
+            full = [np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
+            if self.whisper_long_form and any(w.shape[0] > 480000 for w in full):
+                # whisper.transcribe's long-form loop (WhisperASR.transcribe): nothing is cut; the whole text and all words are reported
+                res = m.transcribe(full, language=None if auto else str(language).lower(), task="transcribe", prompt_ids=prompt_ids,
+                                   keys=[str(k) for k in range(len(full))])
+                if output_raw_result:
+                    return res
+                for r in res:
+                    result_list.append({"key": r["key"], "language": r["language"], "text": r["text"],
+                                        "timestamp": [(str(w), [float(a), float(b)]) for s in r["segments"] for w, (a, b) in s["words"]]})
+                return join_text_only(result_list) if output_text_only else result_list
+            clips = [w[:480000] for w in full]             # one 30 s segment per clip (the long-form loop is behind whisper_long_form)
             res = m.generate(clips, language=None if auto else str(language).lower(), task="transcribe", prompt_ids=prompt_ids,
                              keys=[str(k) for k in range(len(clips))], return_timestamps=True)
             if output_raw_result:
                 return res
-            from .whisper import language_code
             for r in res:
                 result_list.append({"key": r["key"], "language": r["language"] if auto else language_code(language), "text": r["text"],
                                     "timestamp": [(str(w), [float(a), float(b)]) for w, (a, b) in r["words"]]})

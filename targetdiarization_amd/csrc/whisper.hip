@@ -102,6 +102,50 @@ __global__ __launch_bounds__(1024) void wh_clamp_kernel(float* __restrict__ feat
     const float lo = mx - 8.0f;
     for (long i = tid; i < n; i += 1024) x[i] = (fmaxf(x[i], lo) + 4.0f) / 4.0f;
 }
+// tdx_whisper_logmel_long: `count` samples of the reflect-padded clip from padded index s0 on (padded index q is clip index
+// q - 200, mirrored about 0 and N - 1 as often as it takes, like numpy's reflect); zeros past the padded clip.  N >= 2.
+__global__ __launch_bounds__(256) void wh_pad_long_kernel(const float* __restrict__ wav, long N, long s0, int count, float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const long q = s0 + i;
+    float v = 0.f;
+    if (q < N + NFFT) {
+        const long period = 2 * (N - 1);
+        long j = (q - NFFT / 2) % period;
+        if (j < 0) j += period;
+        if (j >= N) j = period - j;
+        v = wav[j];
+    }
+    out[i] = v;
+}
+// the maximum of a whole clip's map in two launches: WH_MAXPART partial maxima, then every workgroup joins them and clamps its share
+constexpr int WH_MAXPART = 256;
+__global__ __launch_bounds__(1024) void wh_max_part_kernel(const float* __restrict__ x, long n, float* __restrict__ part) {
+    __shared__ float red[16];
+    const int tid = threadIdx.x;
+    float mx = -INFINITY;
+    for (long i = (long)blockIdx.x * 1024 + tid; i < n; i += (long)gridDim.x * 1024) mx = fmaxf(mx, x[i]);
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) red[tid >> 6] = mx;
+    __syncthreads();
+    if (tid == 0) {
+        mx = red[0];
+        for (int w = 1; w < 16; ++w) mx = fmaxf(mx, red[w]);
+        part[blockIdx.x] = mx;
+    }
+}
+__global__ __launch_bounds__(1024) void wh_clamp_long_kernel(float* __restrict__ x, long n, const float* __restrict__ part) {
+    __shared__ float red[16];
+    const int tid = threadIdx.x;
+    float mx = tid < WH_MAXPART ? part[tid] : -INFINITY;
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) red[tid >> 6] = mx;
+    __syncthreads();
+    mx = red[0];
+    for (int w = 1; w < 16; ++w) mx = fmaxf(mx, red[w]);
+    const float lo = mx - 8.0f;
+    for (long i = (long)blockIdx.x * 1024 + tid; i < n; i += (long)gridDim.x * 1024) x[i] = (fmaxf(x[i], lo) + 4.0f) / 4.0f;
+}
 
 // ------------------------------------------------------------------------------------------------ encoder
 // feat [B][n_mels][T] -> channel-last rows [B][T + 2][MP] with a zero frame on either side and zero channels n_mels..MP-1
@@ -486,6 +530,73 @@ __global__ __launch_bounds__(256) void wh_head_kernel(SkArgs a, const unsigned c
         pm[o] = t.m; pi[o] = t.i; ps[o] = t.s;
     }
 }
+__device__ __forceinline__ void wh_top_add(WhTop& top, float v, int n) {
+    if (top.i == INT_MAX) top = WhTop{v, n, 1.f};
+    else if (v > top.m) { top.s = top.s * expf(top.m - v) + 1.f; top.m = v; top.i = n; }
+    else top.s += expf(v - top.m);
+}
+// Vocabulary head of tdx_whisper_decode_ts: wh_head_kernel's sweep with the allowed set of every row read from the device state.
+// bnd [4][WH_MAXB]: text_lo, ts_lo, ts_hi, first.  Id n < tb is allowed when n >= text_lo and n != tb - 1 (<|notimestamps|>); id
+// n >= tb when ts_lo <= n <= ts_hi; the static mask as in wh_head_kernel, its bit 1 counting for the rows whose `first` is set.
+// Two running triples per thread: class 0 over the allowed ids below tb, class 1 over those from tb up (a slice can hold both);
+// out [cls][B][nsl].  want_ns: a third pair (max, sum exp) over every id of the slice, no mask, and the logit of id ns_id.
+template <int BT>
+__global__ __launch_bounds__(256) void wh_head_ts_kernel(SkArgs a, const unsigned char* __restrict__ mask, const int* __restrict__ bnd, int tb, int want_ns,
+                                                          int ns_id, float* __restrict__ pm, int* __restrict__ pi, float* __restrict__ ps,
+                                                          float* __restrict__ nm, float* __restrict__ nsum, float* __restrict__ nlogit, int nsl) {
+    __shared__ float stat[2 * WH_MAXB];
+    __shared__ float red[4][4 * BT];
+    __shared__ float tm[3][4 * BT], tsum[3][4 * BT];
+    __shared__ int ti[3][4 * BT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (a.lng) { sk_stats(a, stat, wave, lane); __syncthreads(); }
+    const int rb = min(tid >> 2, a.B - 1);
+    const int text_lo = bnd[rb], ts_lo = bnd[WH_MAXB + rb], ts_hi = bnd[2 * WH_MAXB + rb];
+    const int deny = bnd[3 * WH_MAXB + rb] ? 3 : 1;
+    WhTop top[3] = {{-INFINITY, INT_MAX, 0.f}, {-INFINITY, INT_MAX, 0.f}, {-INFINITY, INT_MAX, 0.f}};
+    for (int g = 0; g < WH_SLICE / 4; ++g) {
+        const int n0 = blockIdx.x * WH_SLICE + 4 * g;
+        if (n0 >= a.N) break;                                       // (uniform over the workgroup)
+        float acc[4 * BT];
+#pragma unroll
+        for (int i = 0; i < 4 * BT; ++i) acc[i] = 0.f;
+        sk_accumulate<BT>(a, a.job[0].W, n0, stat, wave, lane, acc);
+        sk_reduce_to_lds<BT>(acc, lane, red[wave]);
+        __syncthreads();
+        if (tid < 4 * BT) {
+            const int n = n0 + (tid & 3);
+            if (n < a.N) {
+                const float v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+                if (want_ns) {
+                    wh_top_add(top[2], v, 0);
+                    if (n == ns_id && (tid >> 2) < a.B) nlogit[tid >> 2] = v;
+                }
+                const bool ok = n < tb ? (n >= text_lo && n != tb - 1) : (n >= ts_lo && n <= ts_hi);
+                if (ok && !(mask[n] & deny)) {
+                    if (n < tb) wh_top_add(top[0], v, n); else wh_top_add(top[1], v, n);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < 4 * BT)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { tm[k][tid] = top[k].m; ti[k][tid] = top[k].i; tsum[k][tid] = top[k].s; }
+    __syncthreads();
+    if (tid < BT && tid < a.B) {
+        for (int k = 0; k < (want_ns ? 3 : 2); ++k) {
+            WhTop t{-INFINITY, INT_MAX, 0.f};
+            for (int c = 0; c < 4; ++c) wh_merge(t, WhTop{tm[k][4 * tid + c], ti[k][4 * tid + c], tsum[k][4 * tid + c]});
+            if (k < 2) {
+                const long o = ((long)k * a.B + tid) * nsl + blockIdx.x;
+                pm[o] = t.m; pi[o] = t.i; ps[o] = t.s;
+            } else {
+                const long o = (long)tid * nsl + blockIdx.x;
+                nm[o] = t.m; nsum[o] = t.s;
+            }
+        }
+    }
+}
 
 // decode state on the device
 struct WhState { int* cur; int* pos; int* done; int* ndone; const int* prefix; };
@@ -525,6 +636,99 @@ __global__ __launch_bounds__(1024) void wh_next_kernel(const float* __restrict__
                 nxt = am;
                 if (p < gen_to) { counts[b] += 1; if (nxt == eos) d = 1; }
             }
+            s.cur[b] = nxt;
+            if (d) s.done[b] = 1;
+            else s.pos[b] = min(p + 1, T - 1);
+        }
+        fin[b] = d;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0;
+        for (int i = 0; i < B; ++i) n += fin[i];
+        *s.ndone = n;
+    }
+}
+
+// tdx_whisper_decode_ts: per-row prefixes and Whisper's timestamp rules (transformers' WhisperTimeStampLogitsProcessor).
+// ti [WH_TS_ROWS][WH_MAXB] ints; the host fills the first six rows, the kernels own the rest.
+enum { TS_PLEN = 0, TS_BEGIN, TS_PEND, TS_GENTO, TS_SOT, TS_FIRSTROW, TS_H1, TS_H2, TS_HN, TS_LAST, TS_BND, WH_TS_ROWS = TS_BND + 4 };
+struct WhTsRules { int tb, eos, V, max_init; };
+// the allowed intervals of the step that predicts the id after the history (h1 = its last id, h2 = the one before, hn = its
+// length capped at 2, last = its last timestamp id or -1); first: the history is empty and the id is the first generated one
+__device__ __forceinline__ void wh_ts_bounds(int* __restrict__ ti, int b, bool first, WhTsRules r) {
+    const int hn = ti[TS_HN * WH_MAXB + b], h1 = ti[TS_H1 * WH_MAXB + b], h2 = ti[TS_H2 * WH_MAXB + b], last = ti[TS_LAST * WH_MAXB + b];
+    int text_lo = 0, ts_lo = r.tb, ts_hi = r.V - 1;
+    const bool last_ts = hn >= 1 && h1 >= r.tb, pen_ts = hn < 2 || h2 >= r.tb;
+    if (last_ts) { if (pen_ts) ts_lo = INT_MAX; else text_lo = r.eos; }
+    if (last >= 0) ts_lo = max(ts_lo, (last_ts && !pen_ts) ? last : last + 1);
+    if (first) { text_lo = INT_MAX; if (r.max_init >= 0) ts_hi = min(ts_hi, r.tb + r.max_init); }
+    int* bnd = ti + TS_BND * WH_MAXB;
+    bnd[b] = text_lo; bnd[WH_MAXB + b] = ts_lo; bnd[2 * WH_MAXB + b] = ts_hi; bnd[3 * WH_MAXB + b] = first ? 1 : 0;
+}
+__device__ __forceinline__ void wh_ts_push(int* __restrict__ ti, int b, int id, int tb) {
+    ti[TS_H2 * WH_MAXB + b] = ti[TS_H1 * WH_MAXB + b];
+    ti[TS_H1 * WH_MAXB + b] = id;
+    ti[TS_HN * WH_MAXB + b] = min(ti[TS_HN * WH_MAXB + b] + 1, 2);
+    if (id >= tb) ti[TS_LAST * WH_MAXB + b] = id;
+}
+// prefix [B][T]
+__global__ void wh_init_ts_kernel(WhState s, int* __restrict__ ti, int B, int T, WhTsRules r, int* __restrict__ counts) {
+    const int b = threadIdx.x;
+    if (b < B) {
+        s.cur[b] = s.prefix[(long)b * T]; s.pos[b] = 0; s.done[b] = 0; counts[b] = 0;
+        ti[TS_HN * WH_MAXB + b] = 0; ti[TS_H1 * WH_MAXB + b] = -1; ti[TS_H2 * WH_MAXB + b] = -1; ti[TS_LAST * WH_MAXB + b] = -1;
+        wh_ts_bounds(ti, b, ti[TS_BEGIN * WH_MAXB + b] == 1, r);
+    }
+    if (b == 0) *s.ndone = 0;
+}
+__device__ __forceinline__ WhTop wh_join_slices(const float* __restrict__ pm, const int* __restrict__ pi, const float* __restrict__ ps, long row, int nsl, int l) {
+    WhTop t{-INFINITY, INT_MAX, 0.f};
+    for (int j = l; j < nsl; j += 32) wh_merge(t, WhTop{pm[row * nsl + j], pi ? pi[row * nsl + j] : 0, ps[row * nsl + j]});
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) {
+        WhTop u{__shfl_xor(t.m, o, 64), __shfl_xor(t.i, o, 64), __shfl_xor(t.s, o, 64)};
+        WhTop lo = (l & o) ? u : t, hi = (l & o) ? t : u;           // (lower lane's, upper lane's) on both partners, as in wh_next_kernel
+        wh_merge(lo, hi);
+        t = lo;
+    }
+    return t;
+}
+// wh_next_kernel for tdx_whisper_decode_ts: joins the two classes' slices, applies the mass rule (every id below tb is denied
+// when the log-sum-exp of the allowed timestamp logits exceeds the largest allowed text logit), writes the step's outputs, the
+// no-speech probability at the step that fed sot_pos, the next token of the row's own prefix or the generated one, the history
+// and the allowed intervals of the next step.  A row is done after eos or after its own last step (pend).
+__global__ __launch_bounds__(1024) void wh_next_ts_kernel(const float* __restrict__ pm, const int* __restrict__ pi, const float* __restrict__ ps,
+                                                           const float* __restrict__ nm, const float* __restrict__ nsum, const float* __restrict__ nlogit, int nsl,
+                                                           WhState s, int* __restrict__ ti, int B, int T, WhTsRules r, int* __restrict__ ids,
+                                                           float* __restrict__ score, int* __restrict__ counts, float* __restrict__ nospeech) {
+    __shared__ int fin[WH_MAXB];
+    const int b = threadIdx.x >> 5, l = threadIdx.x & 31;
+    const WhTop text = wh_join_slices(pm, pi, ps, b, nsl, l);
+    const WhTop ts = wh_join_slices(pm, pi, ps, (long)B + b, nsl, l);
+    WhTop ns{-INFINITY, INT_MAX, 0.f};
+    if (nospeech) ns = wh_join_slices(nm, nullptr, nsum, b, nsl, l);
+    if (l == 0) {
+        int d = s.done[b];
+        if (!d) {
+            const int p = s.pos[b];
+            WhTop t = text;
+            if (ts.i != INT_MAX && (text.i == INT_MAX || ts.m + logf(ts.s) > text.m)) t = ts;
+            else wh_merge(t, ts);
+            const int am = t.i == INT_MAX ? r.eos : t.i;
+            ids[(long)b * T + p] = am;
+            score[(long)b * T + p] = -logf(t.s);
+            if (nospeech && p == ti[TS_SOT * WH_MAXB + b]) nospeech[b] = expf(nlogit[b] - ns.m) / ns.s;
+            const int plen = ti[TS_PLEN * WH_MAXB + b], begin = ti[TS_BEGIN * WH_MAXB + b];
+            int nxt;
+            if (p + 1 < plen) nxt = s.prefix[(long)b * T + p + 1];
+            else {
+                nxt = am;
+                if (p < ti[TS_GENTO * WH_MAXB + b]) { counts[b] += 1; if (nxt == r.eos) d = 1; }
+            }
+            if (p + 1 >= ti[TS_PEND * WH_MAXB + b]) d = 1;
+            if (p + 1 >= begin) wh_ts_push(ti, b, nxt, r.tb);
+            wh_ts_bounds(ti, b, p + 2 == begin, r);
             s.cur[b] = nxt;
             if (d) s.done[b] = 1;
             else s.pos[b] = min(p + 1, T - 1);
@@ -618,16 +822,19 @@ __global__ __launch_bounds__(64) void wh_attn_comb_kernel(const float* __restric
 // in LDS up to 4096 positions and in the output row itself beyond.  1024 threads and four key rounds in flight: one workgroup per (head, clip) is a chain of dependent loads, and with 256
 // threads and one round at a time it cost 55 us a launch.  The row is pos[b] - first_row; a finished clip, a head of another layer or a row outside the buffer: nothing is
 // written.  The attention kernels above are not touched, so the decode's own results keep their bits.
+// PR: the first row is per clip (first_rows[b], tdx_whisper_decode_ts); otherwise first_row serves every clip.
+template <bool PR>
 __global__ __launch_bounds__(WH_XROW_NT) void wh_xattn_row_kernel(const float* __restrict__ q, const float* __restrict__ Kc, long clip_stride, int S, int d,
                                                             int layer, const int* __restrict__ heads, const int* __restrict__ pos,
-                                                            const int* __restrict__ done, int first_row, int max_rows, float* __restrict__ out) {
+                                                            const int* __restrict__ done, int first_row, const int* __restrict__ first_rows, int max_rows,
+                                                            float* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) float qs[DK];
     __shared__ float red[WH_XROW_NT / 64];
     __shared__ float slds[WH_XROW_LDS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hi = blockIdx.x, b = blockIdx.y, nh = gridDim.x;
     if (heads[2 * hi] != layer || done[b]) return;                  // (uniform over the workgroup, like the two returns below)
-    const int row = pos[b] - first_row;
+    const int row = pos[b] - (PR ? first_rows[b] : first_row);
     if (row < 0 || row >= max_rows) return;
     const int h = heads[2 * hi + 1];
     float* o = out + (((size_t)b * nh + hi) * max_rows + row) * (size_t)S;
@@ -851,6 +1058,21 @@ int launch_head(const SkArgs& a, const unsigned char* mask, int begin, float* pm
     if (a.B <= 16) return launch_head_t<16>(a, mask, begin, pm, pi, ps, nsl, st);
     return launch_head_t<32>(a, mask, begin, pm, pi, ps, nsl, st);
 }
+struct HeadTsOut { float* pm; int* pi; float* ps; float* nm; float* nsum; float* nlogit; };
+template <int BT>
+int launch_head_ts_t(const SkArgs& a, const unsigned char* mask, const int* bnd, int tb, int want_ns, int ns_id, const HeadTsOut& o, int nsl, hipStream_t st) {
+    hipLaunchKernelGGL(wh_head_ts_kernel<BT>, dim3(nsl), dim3(256), 0, st, a, mask, bnd, tb, want_ns, ns_id, o.pm, o.pi, o.ps, o.nm, o.nsum, o.nlogit, nsl);
+    LAUNCH_CHECK();
+    return TDX_OK;
+}
+int launch_head_ts(const SkArgs& a, const unsigned char* mask, const int* bnd, int tb, int want_ns, int ns_id, const HeadTsOut& o, int nsl, hipStream_t st) {
+    if (a.B <= 1) return launch_head_ts_t<1>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+    if (a.B <= 2) return launch_head_ts_t<2>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+    if (a.B <= 4) return launch_head_ts_t<4>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+    if (a.B <= 8) return launch_head_ts_t<8>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+    if (a.B <= 16) return launch_head_ts_t<16>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+    return launch_head_ts_t<32>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+}
 SkJob sk_job(const float* W, const float* bias, const float* res, float* y, long ld, int brow = 0, int gelu = 0) {
     return SkJob{W, bias, res, y, ld, brow, gelu};
 }
@@ -891,7 +1113,8 @@ EncWs enc_ws(const tdx_whisper* h, int B) {
     w.total = o;
     return w;
 }
-struct DecWs { size_t x, xn, skp, q, ao, hb, part, pm, pi, ps, state, prefix, mask, heads, cache, total; int nsl, nch_self, nch_cross; };
+// tsi .. tsprefix: tdx_whisper_decode_ts only (the rows' state, the second class of head triples, the no-speech pairs, [B][T] prefixes)
+struct DecWs { size_t x, xn, skp, q, ao, hb, part, pm, pi, ps, state, prefix, mask, heads, tsi, pm2, pi2, ps2, nm, nsum, nlogit, tsprefix, cache, total; int nsl, nch_self, nch_cross; };
 DecWs dec_ws(const tdx_whisper* h, int B) {
     const size_t d = h->c.d_model, T = h->c.n_text_ctx, H = h->c.dec_heads;
     DecWs w; size_t o = 0;
@@ -907,6 +1130,10 @@ DecWs dec_ws(const tdx_whisper* h, int B) {
     w.prefix = o; o += al(T);
     w.mask = o; o += al(((size_t)h->c.vocab + 3) / 4);
     w.heads = o; o += al(2 * WH_MAXHEADS);
+    w.tsi = o; o += al((size_t)WH_TS_ROWS * WH_MAXB);
+    w.pm2 = o; o += al((size_t)2 * B * w.nsl); w.pi2 = o; o += al((size_t)2 * B * w.nsl); w.ps2 = o; o += al((size_t)2 * B * w.nsl);
+    w.nm = o; o += al((size_t)B * w.nsl); w.nsum = o; o += al((size_t)B * w.nsl); w.nlogit = o; o += al(WH_MAXB);
+    w.tsprefix = o; o += al((size_t)B * T);
     w.cache = o; o += al((size_t)h->c.dec_layers * 2 * B * T * d);
     w.total = o;
     return w;
@@ -1086,33 +1313,27 @@ int tdx_whisper_encode(tdx_whisper* h, const float* feat_dev, int B, float* enc_
 // the capture of tdx_whisper_decode_xattn: (layer, head) pairs, the first position and the rows of the buffer
 struct WhCapture { const int* heads_host; int nh, first_row, max_rows; float* xattn_dev; };
 
-static int whisper_decode_impl(const std::string& fn, const WhCapture* cap, tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host,
-                               int prefix_len, const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int eos, int max_new,
-                               int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_, size_t ws_bytes, void* stream) {
-    if (cap) {
-        if (cap->nh < 1 || cap->nh > WH_MAXHEADS) return tdx::fail(TDX_E_INVALID, fn + ": nh must be in [1, 64]");
-        if (cap->max_rows < 1) return tdx::fail(TDX_E_INVALID, fn + ": max_rows must be at least 1");
-        if (cap->first_row < 0) return tdx::fail(TDX_E_INVALID, fn + ": first_row must not be negative");
-        if (!cap->heads_host || !cap->xattn_dev) return tdx::fail(TDX_E_INVALID, fn + ": heads_host and xattn_dev must not be NULL");
+// the argument checks the decode entry points share, each with its own message
+static int wh_check_capture(const std::string& fn, const WhCapture& cap) {
+    if (cap.nh < 1 || cap.nh > WH_MAXHEADS) return tdx::fail(TDX_E_INVALID, fn + ": nh must be in [1, 64]");
+    if (cap.max_rows < 1) return tdx::fail(TDX_E_INVALID, fn + ": max_rows must be at least 1");
+    if (cap.first_row < 0) return tdx::fail(TDX_E_INVALID, fn + ": first_row must not be negative");
+    if (!cap.heads_host || !cap.xattn_dev) return tdx::fail(TDX_E_INVALID, fn + ": heads_host and xattn_dev must not be NULL");
+    return TDX_OK;
+}
+static int wh_listed_layers(const std::string& fn, const WhCapture& cap, int Ld, int H, std::vector<char>& listed) {
+    for (int i = 0; i < cap.nh; ++i) {
+        const int l = cap.heads_host[2 * i], hd = cap.heads_host[2 * i + 1];
+        if (l < 0 || l >= Ld || hd < 0 || hd >= H)
+            return tdx::fail(TDX_E_INVALID, fn + ": alignment head (" + std::to_string(l) + ", " + std::to_string(hd) + ") outside the decoder's layers / heads");
+        listed[l] = 1;
     }
-    if (!h || !enc_state_dev || !prefix_host || !step_ids_dev || !step_scores_dev || !counts_dev || !ws_ || B < 1 || B > WH_MAXB || prefix_len < 1 ||
-        n_suppress < 0 || n_begin < 0 || (n_suppress > 0 && !suppress_host) || (n_begin > 0 && !begin_suppress_host) || max_new < 0)
-        return tdx::fail(TDX_E_INVALID, fn + ": bad argument (1 <= B <= 32, prefix_len >= 1, max_new >= 0)");
-    const tdx_whisper_config& c = h->c;
-    const int V = c.vocab, T = c.n_text_ctx, d = c.d_model, H = c.dec_heads, S = c.n_audio_ctx, ffn = c.dec_ffn, Ld = c.dec_layers;
-    if (prefix_len > T) return tdx::fail(TDX_E_INVALID, fn + ": the prefix is longer than n_text_ctx");
-    std::vector<char> listed(Ld, 0);
-    if (cap)
-        for (int i = 0; i < cap->nh; ++i) {
-            const int l = cap->heads_host[2 * i], hd = cap->heads_host[2 * i + 1];
-            if (l < 0 || l >= Ld || hd < 0 || hd >= H)
-                return tdx::fail(TDX_E_INVALID, fn + ": alignment head (" + std::to_string(l) + ", " + std::to_string(hd) + ") outside the decoder's layers / heads");
-            listed[l] = 1;
-        }
-    if (eos < 0 || eos >= V) return tdx::fail(TDX_E_INVALID, fn + ": eos outside the vocabulary");
-    for (int i = 0; i < prefix_len; ++i)
-        if (prefix_host[i] < 0 || prefix_host[i] >= V) return tdx::fail(TDX_E_INVALID, fn + ": prefix id outside the vocabulary");
-    std::vector<unsigned char> mask(((size_t)V + 3) / 4 * 4, 0);
+    return TDX_OK;
+}
+// mask[id] bit 0: suppressed at every step, bit 1: at the first generated step
+static int wh_static_mask(const std::string& fn, int V, const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin,
+                          std::vector<unsigned char>& mask) {
+    mask.assign(((size_t)V + 3) / 4 * 4, 0);
     for (int i = 0; i < n_suppress; ++i) {
         if (suppress_host[i] < 0 || suppress_host[i] >= V) return tdx::fail(TDX_E_INVALID, fn + ": suppressed id outside the vocabulary");
         mask[suppress_host[i]] |= 1;
@@ -1121,6 +1342,98 @@ static int whisper_decode_impl(const std::string& fn, const WhCapture* cap, tdx_
         if (begin_suppress_host[i] < 0 || begin_suppress_host[i] >= V) return tdx::fail(TDX_E_INVALID, fn + ": begin-suppressed id outside the vocabulary");
         mask[begin_suppress_host[i]] |= 2;
     }
+    return TDX_OK;
+}
+
+static SkArgs wh_sk_args(const WhState& s, int B, const float* xin, const float* g, const float* be, int N, int K) {
+    SkArgs a{};
+    a.x = xin; a.lng = g; a.lnb = be; a.pos = s.pos; a.B = B; a.N = N; a.K = K;
+    return a;
+}
+// One decode step up to the vocabulary head, shared by the three decode entry points: the embedding of every row's current token
+// and the decoder layers.  first_rows_dev != NULL: the capture's first row is per clip.
+struct WhStepCtx {
+    tdx_whisper* h; const DecWs* w; float* f; WhState s; int B; const float* enc_state_dev; const WhCapture* cap; const char* listed;
+    const int* heads_dev; const int* first_rows_dev; hipStream_t st;
+};
+static int wh_decoder_step(const WhStepCtx& c) {
+    tdx_whisper* h = c.h;
+    const DecWs& w = *c.w;
+    const WhState& s = c.s;
+    const WhCapture* cap = c.cap;
+    hipStream_t st = c.st;
+    const int B = c.B, T = h->c.n_text_ctx, d = h->c.d_model, H = h->c.dec_heads, S = h->c.n_audio_ctx, ffn = h->c.dec_ffn, Ld = h->c.dec_layers;
+    float* f = c.f;
+    float *x = f + w.x, *xn = f + w.xn, *skp = f + w.skp, *q = f + w.q, *ao = f + w.ao, *hb = f + w.hb, *part = f + w.part, *cache = f + w.cache;
+    const float* enc_state_dev = c.enc_state_dev;
+    const size_t lay = (size_t)B * T * d;                       // one layer's K (or V) cache
+    const size_t clay = (size_t)B * S * d;                      // one layer's cross K (or V)
+    auto sk = [&](const float* xin, const float* g, const float* be, int N, int K) { return wh_sk_args(s, B, xin, g, be, N, K); };
+    hipLaunchKernelGGL(wh_embed_kernel, dim3(B), dim3(256), 0, st, h->tok, h->dpos, s.cur, s.pos, x, d);
+    LAUNCH_CHECK();
+    for (int l = 0; l < Ld; ++l) {
+        const DecLayer& L = h->dec[l];
+        float* Kc = cache + (size_t)(2 * l) * lay;
+        float* Vc = cache + (size_t)(2 * l + 1) * lay;
+        SkArgs a = sk(x, L.sa.ln_g, L.sa.ln_b, d, d);
+        a.job[0] = sk_job(L.sa.Wq, L.sa.bq, nullptr, q, d);
+        a.job[1] = sk_job(L.sa.Wk, nullptr, nullptr, Kc, d, T);
+        a.job[2] = sk_job(L.sa.Wv, L.sa.bv, nullptr, Vc, d, T);
+        TRY(launch_skinny(a, 3, xn, skp, st));
+        hipLaunchKernelGGL(wh_attn_part_kernel, dim3(w.nch_self, H, B), dim3(256), 0, st, q, Kc, Vc, (long)T * d, d, s.pos, 0, part);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL(wh_attn_comb_kernel, dim3(H, B), dim3(64), 0, st, part, w.nch_self, ao, d);
+        LAUNCH_CHECK();
+        a = sk(ao, nullptr, nullptr, d, d);
+        a.job[0] = sk_job(L.sa.Wo, L.sa.bo, x, x, d);
+        TRY(launch_skinny(a, 1, xn, skp, st));
+        a = sk(x, L.ca.ln_g, L.ca.ln_b, d, d);
+        a.job[0] = sk_job(L.ca.Wq, L.ca.bq, nullptr, q, d);
+        TRY(launch_skinny(a, 1, xn, skp, st));
+        if (cap && c.listed[l]) {
+            if (c.first_rows_dev)
+                hipLaunchKernelGGL(wh_xattn_row_kernel<true>, dim3(cap->nh, B), dim3(WH_XROW_NT), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay, (long)S * d, S, d, l,
+                                   c.heads_dev, (const int*)s.pos, (const int*)s.done, 0, c.first_rows_dev, cap->max_rows, cap->xattn_dev);
+            else
+                hipLaunchKernelGGL(wh_xattn_row_kernel<false>, dim3(cap->nh, B), dim3(WH_XROW_NT), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay, (long)S * d, S, d, l,
+                                   c.heads_dev, (const int*)s.pos, (const int*)s.done, cap->first_row, (const int*)nullptr, cap->max_rows, cap->xattn_dev);
+            LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(wh_attn_part_kernel, dim3(w.nch_cross, H, B), dim3(256), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay,
+                           enc_state_dev + (size_t)(2 * l + 1) * clay, (long)S * d, d, (const int*)nullptr, S, part);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL(wh_attn_comb_kernel, dim3(H, B), dim3(64), 0, st, part, w.nch_cross, ao, d);
+        LAUNCH_CHECK();
+        a = sk(ao, nullptr, nullptr, d, d);
+        a.job[0] = sk_job(L.ca.Wo, L.ca.bo, x, x, d);
+        TRY(launch_skinny(a, 1, xn, skp, st));
+        a = sk(x, L.ln3_g, L.ln3_b, ffn, d);
+        a.job[0] = sk_job(L.W1, L.b1, nullptr, hb, ffn, 0, 1);
+        TRY(launch_skinny(a, 1, xn, skp, st));
+        a = sk(hb, nullptr, nullptr, d, ffn);
+        a.job[0] = sk_job(L.W2, L.b2, x, x, d);
+        TRY(launch_skinny(a, 1, xn, skp, st));
+    }
+    return TDX_OK;
+}
+
+static int whisper_decode_impl(const std::string& fn, const WhCapture* cap, tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host,
+                               int prefix_len, const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int eos, int max_new,
+                               int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_, size_t ws_bytes, void* stream) {
+    if (cap) TRY(wh_check_capture(fn, *cap));
+    if (!h || !enc_state_dev || !prefix_host || !step_ids_dev || !step_scores_dev || !counts_dev || !ws_ || B < 1 || B > WH_MAXB || prefix_len < 1 ||
+        n_suppress < 0 || n_begin < 0 || (n_suppress > 0 && !suppress_host) || (n_begin > 0 && !begin_suppress_host) || max_new < 0)
+        return tdx::fail(TDX_E_INVALID, fn + ": bad argument (1 <= B <= 32, prefix_len >= 1, max_new >= 0)");
+    const tdx_whisper_config& c = h->c;
+    const int V = c.vocab, T = c.n_text_ctx, d = c.d_model, H = c.dec_heads, Ld = c.dec_layers;
+    if (prefix_len > T) return tdx::fail(TDX_E_INVALID, fn + ": the prefix is longer than n_text_ctx");
+    std::vector<char> listed(Ld, 0);
+    if (cap) TRY(wh_listed_layers(fn, *cap, Ld, H, listed));
+    if (eos < 0 || eos >= V) return tdx::fail(TDX_E_INVALID, fn + ": eos outside the vocabulary");
+    for (int i = 0; i < prefix_len; ++i)
+        if (prefix_host[i] < 0 || prefix_host[i] >= V) return tdx::fail(TDX_E_INVALID, fn + ": prefix id outside the vocabulary");
+    std::vector<unsigned char> mask;
+    TRY(wh_static_mask(fn, V, suppress_host, n_suppress, begin_suppress_host, n_begin, mask));
     if (ws_bytes < tdx_whisper_workspace_bytes(h, B)) return tdx::fail(TDX_E_WORKSPACE, fn + ": workspace too small");
     tdx::DeviceGuard guard(h->device);
     if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
@@ -1132,7 +1445,7 @@ static int whisper_decode_impl(const std::string& fn, const WhCapture* cap, tdx_
     const int p_end = std::max(prefix_len, gen_to);
     const DecWs w = dec_ws(h, B);
     float* f = (float*)ws_;
-    float *x = f + w.x, *xn = f + w.xn, *skp = f + w.skp, *q = f + w.q, *ao = f + w.ao, *hb = f + w.hb, *part = f + w.part, *pm = f + w.pm, *ps = f + w.ps, *cache = f + w.cache;
+    float *x = f + w.x, *pm = f + w.pm, *ps = f + w.ps;
     int* pi = (int*)(f + w.pi);
     int* sti = (int*)(f + w.state);
     int* prefix_dev = (int*)(f + w.prefix);
@@ -1145,57 +1458,11 @@ static int whisper_decode_impl(const std::string& fn, const WhCapture* cap, tdx_
     if (rc != hipSuccess) return tdx::fail_hip(rc, __FILE__, __LINE__);
     hipLaunchKernelGGL(wh_init_kernel, dim3(1), dim3(64), 0, st, s, B, counts_dev);
     LAUNCH_CHECK();
-    const size_t lay = (size_t)B * T * d;                       // one layer's K (or V) cache
-    const size_t clay = (size_t)B * S * d;                      // one layer's cross K (or V)
-    auto sk = [&](const float* xin, const float* g, const float* be, int N, int K) {
-        SkArgs a{};
-        a.x = xin; a.lng = g; a.lnb = be; a.pos = s.pos; a.B = B; a.N = N; a.K = K;
-        return a;
-    };
+    const WhStepCtx ctx{h, &w, f, s, B, enc_state_dev, cap, listed.data(), (const int*)heads_dev, nullptr, st};
     int status = TDX_OK;
     auto step = [&](int p) -> int {
-        hipLaunchKernelGGL(wh_embed_kernel, dim3(B), dim3(256), 0, st, h->tok, h->dpos, s.cur, s.pos, x, d);
-        LAUNCH_CHECK();
-        for (int l = 0; l < Ld; ++l) {
-            const DecLayer& L = h->dec[l];
-            float* Kc = cache + (size_t)(2 * l) * lay;
-            float* Vc = cache + (size_t)(2 * l + 1) * lay;
-            SkArgs a = sk(x, L.sa.ln_g, L.sa.ln_b, d, d);
-            a.job[0] = sk_job(L.sa.Wq, L.sa.bq, nullptr, q, d);
-            a.job[1] = sk_job(L.sa.Wk, nullptr, nullptr, Kc, d, T);
-            a.job[2] = sk_job(L.sa.Wv, L.sa.bv, nullptr, Vc, d, T);
-            TRY(launch_skinny(a, 3, xn, skp, st));
-            hipLaunchKernelGGL(wh_attn_part_kernel, dim3(w.nch_self, H, B), dim3(256), 0, st, q, Kc, Vc, (long)T * d, d, s.pos, 0, part);
-            LAUNCH_CHECK();
-            hipLaunchKernelGGL(wh_attn_comb_kernel, dim3(H, B), dim3(64), 0, st, part, w.nch_self, ao, d);
-            LAUNCH_CHECK();
-            a = sk(ao, nullptr, nullptr, d, d);
-            a.job[0] = sk_job(L.sa.Wo, L.sa.bo, x, x, d);
-            TRY(launch_skinny(a, 1, xn, skp, st));
-            a = sk(x, L.ca.ln_g, L.ca.ln_b, d, d);
-            a.job[0] = sk_job(L.ca.Wq, L.ca.bq, nullptr, q, d);
-            TRY(launch_skinny(a, 1, xn, skp, st));
-            if (cap && listed[l]) {
-                hipLaunchKernelGGL(wh_xattn_row_kernel, dim3(cap->nh, B), dim3(WH_XROW_NT), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay, (long)S * d, S, d, l,
-                                   (const int*)heads_dev, (const int*)s.pos, (const int*)s.done, cap->first_row, cap->max_rows, cap->xattn_dev);
-                LAUNCH_CHECK();
-            }
-            hipLaunchKernelGGL(wh_attn_part_kernel, dim3(w.nch_cross, H, B), dim3(256), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay,
-                               enc_state_dev + (size_t)(2 * l + 1) * clay, (long)S * d, d, (const int*)nullptr, S, part);
-            LAUNCH_CHECK();
-            hipLaunchKernelGGL(wh_attn_comb_kernel, dim3(H, B), dim3(64), 0, st, part, w.nch_cross, ao, d);
-            LAUNCH_CHECK();
-            a = sk(ao, nullptr, nullptr, d, d);
-            a.job[0] = sk_job(L.ca.Wo, L.ca.bo, x, x, d);
-            TRY(launch_skinny(a, 1, xn, skp, st));
-            a = sk(x, L.ln3_g, L.ln3_b, ffn, d);
-            a.job[0] = sk_job(L.W1, L.b1, nullptr, hb, ffn, 0, 1);
-            TRY(launch_skinny(a, 1, xn, skp, st));
-            a = sk(hb, nullptr, nullptr, d, ffn);
-            a.job[0] = sk_job(L.W2, L.b2, x, x, d);
-            TRY(launch_skinny(a, 1, xn, skp, st));
-        }
-        SkArgs a = sk(x, h->dln_g, h->dln_b, V, d);
+        TRY(wh_decoder_step(ctx));
+        SkArgs a = wh_sk_args(s, B, x, h->dln_g, h->dln_b, V, d);
         a.job[0] = sk_job(h->tok, nullptr, nullptr, nullptr, 0);
         TRY(launch_head(a, mask_dev, p == prefix_len - 1, pm, pi, ps, w.nsl, st));
         hipLaunchKernelGGL(wh_next_kernel, dim3(1), dim3(32 * B), 0, st, pm, pi, ps, w.nsl, s, B, T, prefix_len, gen_to, eos, step_ids_dev, step_scores_dev,
@@ -1230,6 +1497,146 @@ int tdx_whisper_decode_xattn(tdx_whisper* h, const float* enc_state_dev, int B, 
     const WhCapture cap{heads_host, nh, first_row, max_rows, xattn_dev};
     return whisper_decode_impl("tdx_whisper_decode_xattn", &cap, h, enc_state_dev, B, prefix_host, prefix_len, suppress_host, n_suppress,
                                begin_suppress_host, n_begin, eos, max_new, step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
+}
+
+int tdx_whisper_decode_ts(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int max_prefix, const int* prefix_len_host,
+                          const int* begin_host, const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int eos,
+                          int no_timestamps_id, int max_initial_timestamp_index, const int* max_new_host, int no_speech_id, const int* sot_pos_host,
+                          float* nospeech_dev, const int* heads_host, int nh, const int* first_row_host, int max_rows, float* xattn_dev,
+                          int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_, size_t ws_bytes, void* stream) {
+    const std::string fn = "tdx_whisper_decode_ts";
+    if (!h || !enc_state_dev || !prefix_host || !prefix_len_host || !max_new_host || !step_ids_dev || !step_scores_dev || !counts_dev || !ws_ || B < 1 ||
+        B > WH_MAXB || max_prefix < 1 || n_suppress < 0 || n_begin < 0 || (n_suppress > 0 && !suppress_host) || (n_begin > 0 && !begin_suppress_host))
+        return tdx::fail(TDX_E_INVALID, fn + ": bad argument (1 <= B <= 32, max_prefix >= 1)");
+    const tdx_whisper_config& c = h->c;
+    const int V = c.vocab, T = c.n_text_ctx, d = c.d_model, H = c.dec_heads, Ld = c.dec_layers;
+    const int tb = no_timestamps_id + 1;
+    if (no_timestamps_id < 0 || tb >= V) return tdx::fail(TDX_E_INVALID, fn + ": the first timestamp id (no_timestamps_id + 1) is outside the vocabulary");
+    if (eos < 0 || eos >= V) return tdx::fail(TDX_E_INVALID, fn + ": eos outside the vocabulary");
+    if (eos >= tb) return tdx::fail(TDX_E_INVALID, fn + ": eos must be below the first timestamp id");
+    if (nospeech_dev && !sot_pos_host) return tdx::fail(TDX_E_INVALID, fn + ": sot_pos_host must not be NULL when nospeech_dev is given");
+    if (nospeech_dev && (no_speech_id < 0 || no_speech_id >= V)) return tdx::fail(TDX_E_INVALID, fn + ": no_speech_id outside the vocabulary");
+    WhCapture capv{heads_host, nh, 0, max_rows, xattn_dev};
+    const WhCapture* cap = heads_host ? &capv : nullptr;
+    std::vector<char> listed(Ld, 0);
+    if (cap) {
+        TRY(wh_check_capture(fn, *cap));
+        TRY(wh_listed_layers(fn, *cap, Ld, H, listed));
+    }
+    // rows TS_PLEN .. TS_FIRSTROW of the device state, and every row's prefix at pitch T
+    std::vector<int> hst((size_t)(TS_FIRSTROW + 1) * WH_MAXB, 0), pre((size_t)B * T, 0);
+    int p_end = 0;
+    for (int b = 0; b < B; ++b) {
+        const int pl = prefix_len_host[b];
+        const std::string row = "row " + std::to_string(b);
+        if (pl < 1 || pl > max_prefix) return tdx::fail(TDX_E_INVALID, fn + ": prefix_len of " + row + " outside [1, max_prefix]");
+        if (pl >= T) return tdx::fail(TDX_E_INVALID, fn + ": the prefix of " + row + " leaves no room in n_text_ctx");
+        if (max_new_host[b] < 0) return tdx::fail(TDX_E_INVALID, fn + ": max_new of " + row + " is negative");
+        const int bg = begin_host ? begin_host[b] : pl;
+        if (bg < 1 || bg > pl) return tdx::fail(TDX_E_INVALID, fn + ": begin of " + row + " outside [1, prefix_len]");
+        if (nospeech_dev && (sot_pos_host[b] < 0 || sot_pos_host[b] >= pl)) return tdx::fail(TDX_E_INVALID, fn + ": sot_pos of " + row + " outside its prefix");
+        const int fr = first_row_host ? first_row_host[b] : pl;
+        if (cap && fr < 0) return tdx::fail(TDX_E_INVALID, fn + ": first_row of " + row + " is negative");
+        for (int i = 0; i < pl; ++i) {
+            const int id = prefix_host[(size_t)b * max_prefix + i];
+            if (id < 0 || id >= V) return tdx::fail(TDX_E_INVALID, fn + ": prefix id outside the vocabulary");
+            pre[(size_t)b * T + i] = id;
+        }
+        const int gen_to = pl - 1 + std::min(max_new_host[b], T - pl), pend = std::max(pl, gen_to);
+        hst[TS_PLEN * WH_MAXB + b] = pl; hst[TS_BEGIN * WH_MAXB + b] = bg; hst[TS_PEND * WH_MAXB + b] = pend; hst[TS_GENTO * WH_MAXB + b] = gen_to;
+        hst[TS_SOT * WH_MAXB + b] = nospeech_dev ? sot_pos_host[b] : -1; hst[TS_FIRSTROW * WH_MAXB + b] = fr;
+        p_end = std::max(p_end, pend);
+    }
+    std::vector<unsigned char> mask;
+    TRY(wh_static_mask(fn, V, suppress_host, n_suppress, begin_suppress_host, n_begin, mask));
+    if (ws_bytes < tdx_whisper_workspace_bytes(h, B)) return tdx::fail(TDX_E_WORKSPACE, fn + ": workspace too small");
+    tdx::DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
+    hipStream_t st = (hipStream_t)stream;
+    const DecWs w = dec_ws(h, B);
+    float* f = (float*)ws_;
+    float* x = f + w.x;
+    const HeadTsOut ho{f + w.pm2, (int*)(f + w.pi2), f + w.ps2, f + w.nm, f + w.nsum, f + w.nlogit};
+    int* sti = (int*)(f + w.state);
+    int* tsi = (int*)(f + w.tsi);
+    int* prefix_dev = (int*)(f + w.tsprefix);
+    unsigned char* mask_dev = (unsigned char*)(f + w.mask);
+    int* heads_dev = (int*)(f + w.heads);
+    const WhState s{sti, sti + WH_MAXB, sti + 2 * WH_MAXB, sti + 3 * WH_MAXB, prefix_dev};
+    // (an index past the last timestamp id allows every timestamp: clamped, so that tb + index cannot overflow)
+    const WhTsRules rules{tb, eos, V, std::min(max_initial_timestamp_index, V - 1 - tb)};
+    hipError_t rc = hipMemcpyAsync(prefix_dev, pre.data(), sizeof(int) * pre.size(), hipMemcpyHostToDevice, st);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(tsi, hst.data(), sizeof(int) * hst.size(), hipMemcpyHostToDevice, st);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(mask_dev, mask.data(), mask.size(), hipMemcpyHostToDevice, st);
+    if (rc == hipSuccess && cap) rc = hipMemcpyAsync(heads_dev, heads_host, sizeof(int) * 2 * nh, hipMemcpyHostToDevice, st);
+    if (rc != hipSuccess) return tdx::fail_hip(rc, __FILE__, __LINE__);
+    hipLaunchKernelGGL(wh_init_ts_kernel, dim3(1), dim3(64), 0, st, s, tsi, B, T, rules, counts_dev);
+    LAUNCH_CHECK();
+    const WhStepCtx ctx{h, &w, f, s, B, enc_state_dev, cap, listed.data(), (const int*)heads_dev, (const int*)(tsi + TS_FIRSTROW * WH_MAXB), st};
+    int status = TDX_OK;
+    auto step = [&]() -> int {
+        TRY(wh_decoder_step(ctx));
+        SkArgs a = wh_sk_args(s, B, x, h->dln_g, h->dln_b, V, d);
+        a.job[0] = sk_job(h->tok, nullptr, nullptr, nullptr, 0);
+        TRY(launch_head_ts(a, mask_dev, tsi + TS_BND * WH_MAXB, tb, nospeech_dev != nullptr, no_speech_id, ho, w.nsl, st));
+        hipLaunchKernelGGL(wh_next_ts_kernel, dim3(1), dim3(32 * B), 0, st, (const float*)ho.pm, (const int*)ho.pi, (const float*)ho.ps, (const float*)ho.nm,
+                           (const float*)ho.nsum, (const float*)ho.nlogit, w.nsl, s, tsi, B, T, rules, step_ids_dev, step_scores_dev, counts_dev, nospeech_dev);
+        LAUNCH_CHECK();
+        return TDX_OK;
+    };
+    for (int p = 0; p < p_end && status == TDX_OK;) {
+        const int n = std::min(WH_CHUNK, p_end - p);
+        for (int i = 0; i < n && status == TDX_OK; ++i) status = step();
+        p += n;
+        // one host read per chunk, as in tdx_whisper_decode (it also keeps the host copies alive until they have been read)
+        rc = hipMemcpyAsync(h->pinned, s.ndone, sizeof(int), hipMemcpyDeviceToHost, st);
+        if (rc == hipSuccess) rc = hipStreamSynchronize(st);
+        if (rc != hipSuccess) return tdx::fail_hip(rc, __FILE__, __LINE__);
+        if (*h->pinned >= B) break;
+    }
+    return status;
+}
+
+// frames per block of tdx_whisper_logmel_long: the workspace holds one block's padded samples and power rows
+constexpr int WH_LONG_FBLK = 4096;
+constexpr long WH_LONG_MAXN = 1L << 30;
+
+size_t tdx_whisper_logmel_long_workspace_bytes(const tdx_whisper* h, long N) {
+    if (!h || N < 1 || N > WH_LONG_MAXN) return 0;
+    const size_t nb = (size_t)std::max<long>(1, std::min<long>(WH_LONG_FBLK, N / HOP));
+    return (al((nb + 3) * HOP) + al(nb * PWP) + al(WH_MAXPART)) * sizeof(float);
+}
+
+int tdx_whisper_logmel_long(tdx_whisper* h, const float* wav_dev, long N, float* feat_dev, void* ws_, size_t ws_bytes, void* stream) {
+    if (!h || !wav_dev || !ws_) return tdx::fail(TDX_E_INVALID, "tdx_whisper_logmel_long: NULL argument");
+    if (N < 1 || N > WH_LONG_MAXN) return tdx::fail(TDX_E_INVALID, "tdx_whisper_logmel_long: N must be in [1, 2^30]");
+    const long F = N / HOP;
+    if (F == 0) return TDX_OK;                                   // shorter than one hop: no frame, nothing to write
+    if (!feat_dev) return tdx::fail(TDX_E_INVALID, "tdx_whisper_logmel_long: feat_dev must not be NULL");
+    if (ws_bytes < tdx_whisper_logmel_long_workspace_bytes(h, N)) return tdx::fail(TDX_E_WORKSPACE, "tdx_whisper_logmel_long: workspace too small");
+    tdx::DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t nbmax = (size_t)std::min<long>(WH_LONG_FBLK, F);
+    float* pad = (float*)ws_;
+    float* pw = pad + al((nbmax + 3) * HOP);
+    float* part = pw + al(nbmax * PWP);
+    for (long f0 = 0; f0 < F; f0 += WH_LONG_FBLK) {
+        const int nb = (int)std::min<long>(WH_LONG_FBLK, F - f0);
+        // row r of the block is frame f0 + r: KFR floats from pad + HOP r; the last row ends at HOP nb + 256, 224 floats before count
+        const int count = (nb + 3) * HOP;
+        hipLaunchKernelGGL(wh_pad_long_kernel, dim3((count + 255) / 256), dim3(256), 0, st, wav_dev, N, f0 * HOP, count, pad);
+        LAUNCH_CHECK();
+        TRY((linear_f32<true>(pad, HOP, h->dft, nb, NBINP, KFR, EpiPow{pw}, st, 0, NBINP)));
+        // EpiLogMelT with one "clip" whose map starts at frame f0 of the row pitch F
+        TRY(linear_f32(pw, PWP, h->melw, nb, MELP, PWP, EpiLogMelT{feat_dev + f0, INT_MAX, (int)F, h->c.n_mels}, st));
+    }
+    const long n = (long)h->c.n_mels * F;
+    hipLaunchKernelGGL(wh_max_part_kernel, dim3(WH_MAXPART), dim3(1024), 0, st, (const float*)feat_dev, n, part);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(wh_clamp_long_kernel, dim3(WH_MAXPART), dim3(1024), 0, st, feat_dev, n, (const float*)part);
+    LAUNCH_CHECK();
+    return TDX_OK;
 }
 
 size_t tdx_token_align_workspace_bytes(int B, int nh, int max_rows, int n_audio_ctx) {

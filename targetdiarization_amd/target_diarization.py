@@ -49,6 +49,8 @@ def _whole_clip_vad(audio: np.ndarray):
 
 
 class TargetDiarization:
+    whisper_long_form = False                 # (an instance made without __init__ keeps the 30 s cuts)
+
     def __init__(self, diarization_pipeline_dir: str = "iic/speech_campplus_speaker-diarization_common",
                  od_model_dir: str = "pyannote/speaker-diarization-3.1", mdx_weights_file: str = "mdx/weights/UVR-MDX-NET-Inst_HQ_3.onnx",
                  embedding_model_dir: str = "iic/speech_eres2netv2w24s4ep4_sv_zh-cn_16k-common",
@@ -65,8 +67,10 @@ class TargetDiarization:
                  od_state_dict=None, od_embed: Optional[Callable] = None, od_embed_state_dict=None, od_embed_model_dir=None,
                  sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None, sensevoice_model_dir=None,
                  sensevoice_token_file=None, whisper_state_dict=None, whisper_config=None, whisper_model_dir=None, whisper_token_list=None,
-                 whisper_tokenizer=None, whisper_generation_config=None, noise_reduce: bool = False, sd_cluster: str = "host", **kwargs):
+                 whisper_tokenizer=None, whisper_generation_config=None, noise_reduce: bool = False, sd_cluster: str = "host",
+                 whisper_long_form: bool = False, **kwargs):
         self.target_similarity_threshold = target_similarity_threshold
+        self.whisper_long_form = bool(whisper_long_form)   # whisper_v2 / whisper_v3: H3 through WhisperASR.transcribe (long-form) instead of 30 s cuts
         self.noise_reduce = bool(noise_reduce)    # noisereduce's spectral gate on the device as denoise_vocal's body when the MDX denoiser is off
         self.asr_engine = asr_engine
         self.cuda_device = cuda_device
@@ -343,7 +347,8 @@ class TargetDiarization:
             whres = self.hp.recognise_whisper(lines) if lines else []
         elif str(self.asr_engine).lower() in ("whisper_v2", "whisper_v3") and getattr(self.hp, "whisper", None) is not None:
             # the engines with word timestamps (ASRProcessor.py:443-488): the language is detected per segment (language="auto")
-            whtres = self.hp.recognise_whisper(lines, language="auto", timestamps=True) if lines else []
+            # whisper_long_form: each timeline goes whole through WhisperASR.transcribe instead of being cut every 30 s
+            whtres = self.hp.recognise_whisper(lines, language="auto", timestamps=True, long_form=self.whisper_long_form) if lines else []
         elif self.hp.asr is not None and lines:
             if self.decoder is None and self.hp.dec is not None:       # the device CIF + NAR decoder (N2)
                 encs, dres = self.hp.encode_device(lines, decode=True)

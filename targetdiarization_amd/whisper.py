@@ -7,7 +7,9 @@ tests/test_whisper_host.py pins the restatement, the prefix and the language tab
 The device does everything up to the token ids: log-mel features, the encoder, the cross-attention K / V of every decoder layer and
 the greedy decoding loop over a KV cache (one host read per 16 steps).  The host builds the prefix, and turns ids into text through
 the byte-level BPE alphabet when a piece table is given.  Deviations from the reference: fp32 (it runs .half()), one prefix per call,
-greedy decoding only (no beams, temperature fallback, timestamp tokens or long-form), tokenizer files are read when present, never required.
+greedy decoding only (no beams or temperature fallback), tokenizer files are read when present, never required.  generate() is the
+one-window path; transcribe() is the long-form one: features of the whole clip, 30 s windows decoded with timestamp
+tokens under per-row prefixes (decode_ts), segments cut at the timestamp pairs, the next window from the last timestamp.
 
 Word timestamps (the reference's whisper_v2 / whisper_v3 engines, ASRProcessor.py:232-243, 443-488): decode_xattn() also
 captures the cross-attention rows of the alignment heads, token_align() turns them into one encoder frame per token on the device
@@ -274,6 +276,56 @@ def token_align(xattn: torch.Tensor, nrows, nframes, median_width: int = MEDIAN_
     return (frames, matrix) if want_matrix else frames
 
 
+_word_timestamps = word_timestamps                     # transcribe() has a switch of that name
+
+
+def cut_segments(tokens, timestamp_begin: int, seek: int, seek_num_frames: int):
+    """transformers' _retrieve_segment: a window's generated ids (no end-of-text) -> ([{"start", "end", "tokens"}], the seek step in
+    feature frames).  Consecutive timestamp pairs close segments; with a single closing timestamp the last segment runs to the
+    end of the ids and the whole window is consumed, without one the ids after the last pair are dropped and the next window
+    starts at that pair's time; with no pair at all the ids are one segment that ends at the last timestamp (the window's end
+    when there is none, or only <|0.00|>) and the whole window is consumed."""
+    tb = int(timestamp_begin)
+    tokens = [int(t) for t in tokens]
+    t0 = seek * TIME_PRECISION / 2
+    stamp = [t >= tb for t in tokens]
+    single_end = stamp[-2:] == [False, True]
+    slices = [i + 1 for i in range(len(tokens) - 1) if stamp[i] and stamp[i + 1]]
+    if not slices:
+        last = int(seek_num_frames * 0.01 / TIME_PRECISION)
+        marks = [t for t in tokens if t >= tb]
+        if marks and marks[-1] != tb:
+            last = marks[-1] - tb
+        return [{"start": t0, "end": t0 + last * TIME_PRECISION, "tokens": tokens}], int(seek_num_frames)
+    if single_end:
+        slices.append(len(tokens))
+    else:
+        slices[-1] += 1                                    # the pair's second timestamp stays with the last segment
+    segs, lo = [], 0
+    for k, hi in enumerate(slices):
+        sl = tokens[lo:hi]
+        end = sl[-1] if (k < len(slices) - 1 or single_end) else sl[-2]
+        segs.append({"start": t0 + (sl[0] - tb) * TIME_PRECISION, "end": t0 + (end - tb) * TIME_PRECISION, "tokens": sl})
+        lo = hi
+    step = int(seek_num_frames) if single_end else (tokens[lo - 2] - tb) * 2
+    return segs, (step if step > 0 else int(seek_num_frames))      # (the rules keep a pair's time above 0; a step of 0 would never end)
+
+
+def longform_prefix(init, history, condition: bool, first_prompt, timestamp_begin: int, prev_sot: int, n_text_ctx: int):
+    """transformers' _prepare_decoder_input_ids for one clip.  init: [sot, lang, task]; history: the token lists of the clip's
+    segments so far (with conditioning a prompt is the first of them); conditioning: <|startofprev|> + the last n_text_ctx // 2 - 1
+    of those ids, the second timestamp of a closing pair skipped, + init.  first_prompt: the prompt of a first window without
+    conditioning."""
+    if condition and history:
+        ids = []
+        for s in history:
+            ids += list(s[:-1]) if len(s) > 2 and s[-2] >= timestamp_begin else list(s)
+        return [int(prev_sot)] + ids[-(n_text_ctx // 2 - 1):] + list(init)
+    if first_prompt is not None:
+        return [int(prev_sot)] + list(first_prompt) + list(init)
+    return list(init)
+
+
 class WhisperASR:
     def __init__(self, state_dict, config, device="cuda:0", token_list=None, tokenizer=None, generation_config=None, alignment_heads=None):
         self.cfg = c = whisper_config(config)
@@ -492,6 +544,173 @@ class WhisperASR:
                             r["words"] = word_timestamps(tok, r["token_times"], self.token_list, language_code(lg), eos)
                         res[b] = r
             out.extend(res)
+        return out
+
+    # ---- long-form transcription with timestamp tokens
+    def features_long(self, wav) -> torch.Tensor:
+        """one 16 kHz clip of any length N -> log-mel features [n_mels, N // 160], nothing cut or padded, the clamp taken over the
+        whole clip (WhisperFeatureExtractor with truncation=False)"""
+        self._check_open()
+        wav = torch.as_tensor(np.asarray(wav, dtype=np.float32) if not isinstance(wav, torch.Tensor) else wav)
+        wav = wav.reshape(-1).to(self.device, torch.float32).contiguous()
+        N = int(wav.shape[0])
+        if N < 1:
+            raise _lib.TdxError("WhisperASR.features_long: an empty clip")
+        feat = torch.empty(self.cfg["n_mels"], N // 160, device=self.device)
+        with self._guard.call():
+            ws = self._guard.workspace(max(1, int(self._l.tdx_whisper_logmel_long_workspace_bytes(self._h, N))))
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self._l.tdx_whisper_logmel_long(self._h, wav.data_ptr(), N, feat.data_ptr() if feat.numel() else None, ws.data_ptr(),
+                                                       ws.numel(), st))
+        return feat
+
+    def decode_ts(self, state: torch.Tensor, prefixes, max_new, suppress=(), begin_suppress=(), eos=None, no_timestamps_id=None,
+                  max_initial_timestamp_index=None, begin=None, sot_pos=None, no_speech_id=None, heads=None, first_row=None, max_rows=None):
+        """greedy decoding under Whisper's timestamp rules, one prefix per row (tdx_whisper_decode_ts) -> step_ids, step_scores,
+        counts as decode(), nospeech float32 [B] (None without sot_pos) and xattn [B, nh, max_rows, n_audio_ctx] (None without
+        heads).  prefixes: a list of id lists; max_new: an int or one per row; begin: per row, where the row's history starts
+        (default: its prefix length); sot_pos: per row, the position of <|startoftranscript|>; first_row: per row (default: its
+        prefix length)."""
+        self._check_open()
+        c, g = self.cfg, self.gen_cfg
+        B = int(state.shape[2])
+        self._check_batch(B)
+        if tuple(state.shape) != (c["dec_layers"], 2, B, c["n_audio_ctx"], c["d_model"]) or not state.is_contiguous():
+            raise _lib.TdxError("WhisperASR.decode_ts: state is not encode(..., with_state=True)'s")
+        prefixes = [[int(t) for t in p] for p in prefixes]
+        if len(prefixes) != B:
+            raise _lib.TdxError(f"WhisperASR.decode_ts: {B} rows of state, {len(prefixes)} prefixes")
+        per_row = lambda v: [int(v)] * B if isinstance(v, int) else [int(t) for t in v]
+        max_new = per_row(max_new)
+        eos = int(g["eos_token_id"] if eos is None else eos)
+        nots = int(g["no_timestamps_token_id"] if no_timestamps_id is None else no_timestamps_id)
+        mi = g.get("max_initial_timestamp_index") if max_initial_timestamp_index is None else max_initial_timestamp_index
+        mi = -1 if mi is None else int(mi)
+        plen = [len(p) for p in prefixes]
+        mp = max(1, max(plen))
+        arr = lambda v: (C.c_int * max(1, len(v)))(*[int(t) for t in v])
+        opt = lambda v: arr(per_row(v)) if v is not None else None
+        flat_prefix = [t for p in prefixes for t in p + [0] * (mp - len(p))]
+        for name, v in (("max_new", max_new), ("begin", begin), ("sot_pos", sot_pos), ("first_row", first_row)):
+            if v is not None and not isinstance(v, int) and len(v) != B:
+                raise _lib.TdxError(f"WhisperASR.decode_ts: {name} has {len(v)} entries for {B} rows")
+        suppress, begin_suppress = list(suppress), list(begin_suppress)
+        ids = torch.full((B, c["n_text_ctx"]), -1, dtype=torch.int32, device=self.device)
+        scores = torch.zeros(B, c["n_text_ctx"], device=self.device)
+        counts = torch.zeros(B, dtype=torch.int32, device=self.device)
+        nospeech = torch.zeros(B, device=self.device) if sot_pos is not None else None
+        ns_id = int(nots - 1 if no_speech_id is None else no_speech_id)
+        xattn, flat, nh = None, None, 0
+        if heads is not None:
+            heads = [[int(l), int(h)] for l, h in heads]
+            nh = len(heads)
+            flat = arr([t for pair in heads for t in pair])
+            max_rows = max(1, max(max_new) - 1) if max_rows is None else int(max_rows)
+            if 1 <= nh <= MAX_ALIGN_HEADS and max_rows >= 1:
+                xattn = torch.zeros(B, nh, max_rows, c["n_audio_ctx"], device=self.device)
+        with self._guard.call():
+            ws = self._guard.workspace(self.workspace_bytes(B))
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self._l.tdx_whisper_decode_ts(self._h, state.data_ptr(), B, arr(flat_prefix), mp, arr(plen), opt(begin), arr(suppress), len(suppress),
+                                                     arr(begin_suppress), len(begin_suppress), eos, nots, mi, arr(max_new), ns_id, opt(sot_pos),
+                                                     nospeech.data_ptr() if nospeech is not None else None, flat, nh, opt(first_row),
+                                                     int(max_rows or 0), xattn.data_ptr() if xattn is not None else None, ids.data_ptr(),
+                                                     scores.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), st))
+        return ids, scores, counts, nospeech, xattn
+
+    def transcribe(self, wavs, language=None, task: str = "transcribe", prompt_ids=None, condition_on_prev_tokens: bool = True,
+                   no_speech_threshold=0.6, logprob_threshold=-1.0, word_timestamps: bool = True, keys=None):
+        """whisper.transcribe(model, audio, initial_prompt=, word_timestamps=True, language=) at temperature 0, as transformers'
+        long-form generate runs it: clips of any length, decoded in 30 s windows with timestamp tokens, cut into segments at the
+        timestamp pairs, the next window starting at the last timestamp.  Per clip {"key", "language", "text", "segments": [{"id",
+        "seek", "start", "end", "text", "tokens", "avg_logprob", "no_speech_prob", "words"}]}.  All clips still running share one
+        encode and one decode_ts call per round of the loop, whatever their languages and prefix lengths."""
+        self._check_open()
+        if isinstance(wavs, (np.ndarray, torch.Tensor)):
+            wavs = [wavs]
+        g, c = self.gen_cfg, self.cfg
+        T, nseg = c["n_text_ctx"], 2 * c["n_audio_ctx"]
+        if word_timestamps and not 1 <= len(self.alignment_heads) <= MAX_ALIGN_HEADS:
+            raise ValueError(f"{len(self.alignment_heads)} alignment heads: pass 1..{MAX_ALIGN_HEADS} pairs as alignment_heads= or in the generation config")
+        sup, beg, eos = g.get("suppress_tokens") or (), g.get("begin_suppress_tokens") or (), int(g["eos_token_id"])
+        tb, prev = int(g["no_timestamps_token_id"]) + 1, int(g["prev_sot_token_id"])
+        prompt = None
+        if prompt_ids is not None:
+            prompt = [int(t) for t in (prompt_ids.tolist() if hasattr(prompt_ids, "tolist") else prompt_ids)]
+            prompt = prompt[1:] if prompt and prompt[0] == prev else prompt
+        auto = language is None or str(language).strip().lower() == "auto"
+        out = []
+        for c0 in range(0, len(wavs), MAX_BATCH):
+            chunk = wavs[c0:c0 + MAX_BATCH]
+            feats = [self.features_long(w) for w in chunk]
+            n = len(chunk)
+            F = [int(f.shape[1]) for f in feats]
+            seek, langs, inits = [0] * n, [None if auto else language_code(language)] * n, [None] * n
+            history = [[list(prompt)] if prompt is not None and condition_on_prev_tokens else [] for _ in range(n)]
+            first_prompt = [prompt if not condition_on_prev_tokens else None for _ in range(n)]
+            segs = [[] for _ in range(n)]
+            while True:
+                live = [i for i in range(n) if seek[i] < F[i]]
+                if not live:
+                    break
+                nfr = [min(F[i] - seek[i], nseg) for i in live]
+                win = torch.zeros(len(live), c["n_mels"], nseg, device=self.device)
+                for k, i in enumerate(live):
+                    win[k, :, :nfr[k]] = feats[i][:, seek[i]:seek[i] + nfr[k]]
+                _, state = self.encode(win, with_state=True)
+                need = [k for k, i in enumerate(live) if langs[i] is None]
+                if need:                                    # the language of a clip comes from its first window
+                    found = self.detect_language(state if len(need) == len(live) else state[:, :, need].contiguous())
+                    for k, lg in zip(need, found):
+                        langs[live[k]] = lg
+                prefixes = []
+                for i in live:
+                    if inits[i] is None:
+                        inits[i] = decode_prefix(langs[i], task, None, g, T)[:-1]          # no <|notimestamps|>
+                    prefixes.append(longform_prefix(inits[i], history[i], condition_on_prev_tokens, first_prompt[i], tb, prev, T))
+                    first_prompt[i] = None
+                for p in prefixes:
+                    if len(p) >= T:
+                        raise ValueError(f"a prefix of {len(p)} ids leaves no room in a context of {T}")
+                max_new = [new_token_limit(len(p), None, {"max_length": g.get("max_length")}, T) for p in prefixes]
+                heads = self.alignment_heads if word_timestamps else None
+                ids, scores, counts, nosp, xattn = self.decode_ts(state, prefixes, max_new, suppress=sup, begin_suppress=beg, eos=eos, no_timestamps_id=tb - 1,
+                                                                   sot_pos=[len(p) - len(inits[i]) for p, i in zip(prefixes, live)], heads=heads)
+                counts_l, nosp_l = counts.cpu().tolist(), nosp.cpu().tolist()
+                frames = None
+                if word_timestamps:
+                    frames = token_align(xattn, [max(0, m - 1) for m in counts_l], [max(1, f // 2) for f in nfr]).cpu().tolist()
+                    del xattn
+                ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
+                for k, i in enumerate(live):
+                    p0, m = len(prefixes[k]) - 1, counts_l[k]
+                    tok = [int(t) for t in ids[k, p0:p0 + m]]
+                    avg = float(np.sum(scores[k, p0:p0 + m], dtype=np.float64)) / m if m else 0.0
+                    if (no_speech_threshold is not None and logprob_threshold is not None and avg < logprob_threshold
+                            and nosp_l[k] > no_speech_threshold):
+                        seek[i] += nfr[k]                   # a silent window: skipped whole
+                        continue
+                    body = tok[:-1] if tok and tok[-1] == eos else tok
+                    t0 = seek[i] * TIME_PRECISION / 2
+                    times = None
+                    if word_timestamps:
+                        t = [f * TIME_PRECISION for f in frames[k][:max(0, m - 1)]]
+                        times = (t + [t[-1]]) if t else [0.0] * m
+                    cut, step = cut_segments(body, tb, seek[i], nfr[k])
+                    at = 0
+                    for s in cut:
+                        words = []
+                        if word_timestamps:
+                            tt = times[at:at + len(s["tokens"])]
+                            words = [(w, [a + t0, b + t0]) for w, (a, b) in _word_timestamps(s["tokens"], tt, self.token_list, langs[i], eos)]
+                        at += len(s["tokens"])
+                        segs[i].append({"id": len(segs[i]), "seek": seek[i], "start": s["start"], "end": s["end"], "text": self.text_of(s["tokens"]),
+                                        "tokens": s["tokens"], "avg_logprob": avg, "no_speech_prob": float(nosp_l[k]), "words": words})
+                        history[i].append(s["tokens"])
+                    seek[i] += step
+            for i in range(n):
+                out.append({"key": keys[c0 + i] if keys is not None else f"clip_{c0 + i}", "language": langs[i],
+                            "text": "".join(s["text"] for s in segs[i]), "segments": segs[i]})
         return out
 
     def close(self):
