@@ -8,13 +8,17 @@
 //   encoder   conv1 / conv2 as GEMMs over channel-last rows with a zero frame on either side (taps contiguous, conv2 at row pitch
 //             2 d), GELU, + positions; L pre-LN layers: LayerNorm rows, q / k / v / out / fc1 / fc2 through linear_f32, attention
 //             as one streaming-softmax kernel (no score map is ever stored); final LayerNorm; the cross K / V of every decoder layer
-//   decode    one token per clip per step, B <= 32, state on the device (cur_tok, pos, done): embed; per layer a skinny Linear
+//   decode    one loop (wh_decode_run) behind tdx_whisper_decode, tdx_whisper_decode_xattn and tdx_whisper_decode_ts; the first two
+//             are the third with the same prefix in every row, begin = prefix_len and the timestamp rules off.
+//             One token per clip per step, B <= 32, state on the device (cur_tok, pos, done, and per row its prefix, its last
+//             step and the rules' history: WhState): embed; per layer a skinny Linear
 //             launch for q | k | v (k, v land in the cache row `pos`), single-query attention in key chunks of 256 + a combine,
 //             out_proj + residual, the same for the cross attention over the precomputed K / V, fc1 + GELU, fc2 + residual; the
 //             vocabulary head in 64-column slices (max, argmax, sum exp per row and slice, suppression mask applied, logits never
-//             stored) and one combine launch that writes the per-position outputs, the next token, pos + 1 and the done flags.
-//             The host enqueues 16 steps at a time and then reads one pinned word (the number of finished clips).
-//   times     word timestamps: tdx_whisper_decode_xattn is the same loop plus, per layer with a listed alignment head,
+//             stored; wh_head_kernel<BT, TS>: TS = false keeps one running triple per thread, TS = true the rules' two classes
+//             and the no-speech pair) and one combine launch that writes the per-position outputs, the next token, pos + 1 and
+//             the done flags.  The host enqueues 16 steps at a time and then reads one pinned word (the number of finished clips).
+//   times     word timestamps: a capturing call is the same loop plus, per layer with a listed alignment head,
 //             one launch that writes the head's softmax row over the encoder positions; tdx_token_align normalises those rows over
 //             the tokens, median-filters along the frames, averages the heads and runs the dynamic time warping of a clip in one
 //             workgroup along the anti-diagonals (transformers' _extract_token_timestamps).
@@ -487,73 +491,37 @@ __device__ __forceinline__ void wh_merge(WhTop& a, const WhTop& b) {
     if (b.m > a.m || (b.m == a.m && b.i < a.i)) a.i = b.i;
     a.m = mx;
 }
-// Vocabulary head: workgroup s sweeps columns [64 s, 64 s + 64) four at a time through the skinny Linear's loop (W = the token
-// embedding, no bias); thread (b, c) keeps the running triple of row b over its columns; one triple per (row, slice) goes out.
-// mask[n] bit 0: suppressed at every step, bit 1: suppressed when `begin`.
-template <int BT>
-__global__ __launch_bounds__(256) void wh_head_kernel(SkArgs a, const unsigned char* __restrict__ mask, int begin, float* __restrict__ pm,
-                                                       int* __restrict__ pi, float* __restrict__ ps, int nsl) {
-    __shared__ float stat[2 * WH_MAXB];
-    __shared__ float red[4][4 * BT];
-    __shared__ float tm[4 * BT], tsum[4 * BT];
-    __shared__ int ti[4 * BT];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (a.lng) { sk_stats(a, stat, wave, lane); __syncthreads(); }
-    const int deny = begin ? 3 : 1;
-    WhTop top{-INFINITY, INT_MAX, 0.f};
-    for (int g = 0; g < WH_SLICE / 4; ++g) {
-        const int n0 = blockIdx.x * WH_SLICE + 4 * g;
-        if (n0 >= a.N) break;                                       // (uniform over the workgroup)
-        float acc[4 * BT];
-#pragma unroll
-        for (int i = 0; i < 4 * BT; ++i) acc[i] = 0.f;
-        sk_accumulate<BT>(a, a.job[0].W, n0, stat, wave, lane, acc);
-        sk_reduce_to_lds<BT>(acc, lane, red[wave]);
-        __syncthreads();
-        if (tid < 4 * BT) {
-            const int n = n0 + (tid & 3);
-            if (n < a.N && !(mask[n] & deny)) {
-                const float v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-                if (top.i == INT_MAX) top = WhTop{v, n, 1.f};
-                else if (v > top.m) { top.s = top.s * expf(top.m - v) + 1.f; top.m = v; top.i = n; }
-                else top.s += expf(v - top.m);
-            }
-        }
-        __syncthreads();
-    }
-    if (tid < 4 * BT) { tm[tid] = top.m; ti[tid] = top.i; tsum[tid] = top.s; }
-    __syncthreads();
-    if (tid < BT && tid < a.B) {
-        WhTop t{-INFINITY, INT_MAX, 0.f};
-        for (int c = 0; c < 4; ++c) wh_merge(t, WhTop{tm[4 * tid + c], ti[4 * tid + c], tsum[4 * tid + c]});
-        const long o = (long)tid * nsl + blockIdx.x;
-        pm[o] = t.m; pi[o] = t.i; ps[o] = t.s;
-    }
-}
+// what the vocabulary head hands to wh_next_kernel
+struct WhHeadOut { float* pm; int* pi; float* ps; float* nm; float* nsum; float* nlogit; };
 __device__ __forceinline__ void wh_top_add(WhTop& top, float v, int n) {
     if (top.i == INT_MAX) top = WhTop{v, n, 1.f};
     else if (v > top.m) { top.s = top.s * expf(top.m - v) + 1.f; top.m = v; top.i = n; }
     else top.s += expf(v - top.m);
 }
-// Vocabulary head of tdx_whisper_decode_ts: wh_head_kernel's sweep with the allowed set of every row read from the device state.
-// bnd [4][WH_MAXB]: text_lo, ts_lo, ts_hi, first.  Id n < tb is allowed when n >= text_lo and n != tb - 1 (<|notimestamps|>); id
-// n >= tb when ts_lo <= n <= ts_hi; the static mask as in wh_head_kernel, its bit 1 counting for the rows whose `first` is set.
-// Two running triples per thread: class 0 over the allowed ids below tb, class 1 over those from tb up (a slice can hold both);
-// out [cls][B][nsl].  want_ns: a third pair (max, sum exp) over every id of the slice, no mask, and the logit of id ns_id.
-template <int BT>
-__global__ __launch_bounds__(256) void wh_head_ts_kernel(SkArgs a, const unsigned char* __restrict__ mask, const int* __restrict__ bnd, int tb, int want_ns,
-                                                          int ns_id, float* __restrict__ pm, int* __restrict__ pi, float* __restrict__ ps,
-                                                          float* __restrict__ nm, float* __restrict__ nsum, float* __restrict__ nlogit, int nsl) {
+// Vocabulary head: workgroup s sweeps columns [64 s, 64 s + 64) four at a time through the skinny Linear's loop (W = the token
+// embedding, no bias); thread (b, c) keeps the running triples of row b over its columns; one triple per (class, row, slice) goes
+// out, pm / pi / ps [cls][B][nsl].  mask[n] bit 0: suppressed at every step, bit 1: suppressed for the rows whose `first` is set.
+// bnd [4][WH_MAXB] (the device state's TS_BND rows): text_lo, ts_lo, ts_hi, first.
+// TS = false (tdx_whisper_decode, tdx_whisper_decode_xattn: the rules are off): one triple over every id the mask allows, one class.
+// TS = true (tdx_whisper_decode_ts): id n < tb is allowed when n >= text_lo and n != tb - 1 (<|notimestamps|>), id n >= tb when
+// ts_lo <= n <= ts_hi; class 0 over the allowed ids below tb, class 1 over those from tb up (a slice can hold both).  want_ns: a
+// third pair (max, sum exp) over every id of the slice, no mask, and the logit of id ns_id.
+template <int BT, bool TS>
+__global__ __launch_bounds__(256) void wh_head_kernel(SkArgs a, const unsigned char* __restrict__ mask, const int* __restrict__ bnd, int tb, int want_ns,
+                                                       int ns_id, WhHeadOut o, int nsl) {
+    constexpr int NC = TS ? 3 : 1;
     __shared__ float stat[2 * WH_MAXB];
     __shared__ float red[4][4 * BT];
-    __shared__ float tm[3][4 * BT], tsum[3][4 * BT];
-    __shared__ int ti[3][4 * BT];
+    __shared__ float tm[NC][4 * BT], tsum[NC][4 * BT];
+    __shared__ int ti[NC][4 * BT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (a.lng) { sk_stats(a, stat, wave, lane); __syncthreads(); }
     const int rb = min(tid >> 2, a.B - 1);
-    const int text_lo = bnd[rb], ts_lo = bnd[WH_MAXB + rb], ts_hi = bnd[2 * WH_MAXB + rb];
+    const int text_lo = TS ? bnd[rb] : 0, ts_lo = TS ? bnd[WH_MAXB + rb] : 0, ts_hi = TS ? bnd[2 * WH_MAXB + rb] : 0;
     const int deny = bnd[3 * WH_MAXB + rb] ? 3 : 1;
-    WhTop top[3] = {{-INFINITY, INT_MAX, 0.f}, {-INFINITY, INT_MAX, 0.f}, {-INFINITY, INT_MAX, 0.f}};
+    WhTop top[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) top[k] = WhTop{-INFINITY, INT_MAX, 0.f};
     for (int g = 0; g < WH_SLICE / 4; ++g) {
         const int n0 = blockIdx.x * WH_SLICE + 4 * g;
         if (n0 >= a.N) break;                                       // (uniform over the workgroup)
@@ -567,13 +535,15 @@ __global__ __launch_bounds__(256) void wh_head_ts_kernel(SkArgs a, const unsigne
             const int n = n0 + (tid & 3);
             if (n < a.N) {
                 const float v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-                if (want_ns) {
-                    wh_top_add(top[2], v, 0);
-                    if (n == ns_id && (tid >> 2) < a.B) nlogit[tid >> 2] = v;
-                }
-                const bool ok = n < tb ? (n >= text_lo && n != tb - 1) : (n >= ts_lo && n <= ts_hi);
-                if (ok && !(mask[n] & deny)) {
-                    if (n < tb) wh_top_add(top[0], v, n); else wh_top_add(top[1], v, n);
+                if constexpr (TS) {
+                    if (want_ns) {
+                        wh_top_add(top[2], v, 0);
+                        if (n == ns_id && (tid >> 2) < a.B) o.nlogit[tid >> 2] = v;
+                    }
+                    const bool ok = n < tb ? (n >= text_lo && n != tb - 1) : (n >= ts_lo && n <= ts_hi);
+                    if (ok && !(mask[n] & deny)) wh_top_add(top[n < tb ? 0 : 1], v, n);
+                } else {
+                    if (!(mask[n] & deny)) wh_top_add(top[0], v, n);
                 }
             }
         }
@@ -581,88 +551,44 @@ __global__ __launch_bounds__(256) void wh_head_ts_kernel(SkArgs a, const unsigne
     }
     if (tid < 4 * BT)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { tm[k][tid] = top[k].m; ti[k][tid] = top[k].i; tsum[k][tid] = top[k].s; }
+        for (int k = 0; k < NC; ++k) { tm[k][tid] = top[k].m; ti[k][tid] = top[k].i; tsum[k][tid] = top[k].s; }
     __syncthreads();
     if (tid < BT && tid < a.B) {
-        for (int k = 0; k < (want_ns ? 3 : 2); ++k) {
+        for (int k = 0; k < (TS ? (want_ns ? 3 : 2) : 1); ++k) {
             WhTop t{-INFINITY, INT_MAX, 0.f};
             for (int c = 0; c < 4; ++c) wh_merge(t, WhTop{tm[k][4 * tid + c], ti[k][4 * tid + c], tsum[k][4 * tid + c]});
             if (k < 2) {
-                const long o = ((long)k * a.B + tid) * nsl + blockIdx.x;
-                pm[o] = t.m; pi[o] = t.i; ps[o] = t.s;
+                const long q = ((long)k * a.B + tid) * nsl + blockIdx.x;
+                o.pm[q] = t.m; o.pi[q] = t.i; o.ps[q] = t.s;
             } else {
-                const long o = (long)tid * nsl + blockIdx.x;
-                nm[o] = t.m; nsum[o] = t.s;
+                const long q = (long)tid * nsl + blockIdx.x;
+                o.nm[q] = t.m; o.nsum[q] = t.s;
             }
         }
     }
 }
 
-// decode state on the device
-struct WhState { int* cur; int* pos; int* done; int* ndone; const int* prefix; };
-
-__global__ void wh_init_kernel(WhState s, int B, int* __restrict__ counts) {
-    const int b = threadIdx.x;
-    if (b < B) { s.cur[b] = s.prefix[0]; s.pos[b] = 0; s.done[b] = 0; counts[b] = 0; }
-    if (b == 0) *s.ndone = 0;
-}
-// The slices of a row -> (argmax, its log-softmax); then the step: the per-position outputs, the next token (forced while the
-// prefix lasts), pos + 1, the done flag, the count of finished clips.  32 lanes per clip, block = 32 B threads.
-__global__ __launch_bounds__(1024) void wh_next_kernel(const float* __restrict__ pm, const int* __restrict__ pi, const float* __restrict__ ps, int nsl,
-                                                        WhState s, int B, int T, int prefix_len, int gen_to, int eos, int* __restrict__ ids,
-                                                        float* __restrict__ score, int* __restrict__ counts) {
-    __shared__ int fin[WH_MAXB];
-    const int b = threadIdx.x >> 5, l = threadIdx.x & 31;
-    WhTop t{-INFINITY, INT_MAX, 0.f};
-    for (int j = l; j < nsl; j += 32) wh_merge(t, WhTop{pm[(long)b * nsl + j], pi[(long)b * nsl + j], ps[(long)b * nsl + j]});
-#pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) {
-        WhTop u{__shfl_xor(t.m, o, 64), __shfl_xor(t.i, o, 64), __shfl_xor(t.s, o, 64)};
-        // both partners must end with the same triple: merge (lower lane's, upper lane's) in that order on both
-        WhTop lo = (l & o) ? u : t, hi = (l & o) ? t : u;
-        wh_merge(lo, hi);
-        t = lo;
-    }
-    if (l == 0) {
-        int d = s.done[b];
-        if (!d) {
-            const int p = s.pos[b];
-            const int am = t.i == INT_MAX ? eos : t.i;
-            ids[(long)b * T + p] = am;
-            score[(long)b * T + p] = -logf(t.s);
-            int nxt;
-            if (p + 1 < prefix_len) nxt = s.prefix[p + 1];
-            else {
-                nxt = am;
-                if (p < gen_to) { counts[b] += 1; if (nxt == eos) d = 1; }
-            }
-            s.cur[b] = nxt;
-            if (d) s.done[b] = 1;
-            else s.pos[b] = min(p + 1, T - 1);
-        }
-        fin[b] = d;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int n = 0;
-        for (int i = 0; i < B; ++i) n += fin[i];
-        *s.ndone = n;
-    }
-}
-
-// tdx_whisper_decode_ts: per-row prefixes and Whisper's timestamp rules (transformers' WhisperTimeStampLogitsProcessor).
-// ti [WH_TS_ROWS][WH_MAXB] ints; the host fills the first six rows, the kernels own the rest.
+// Decode state on the device.  prefix [B][T]: every row's own prefix.  ti [WH_TS_ROWS][WH_MAXB] ints: the host fills the first six
+// rows (a row's prefix length, where its history starts, its last step, the last position it may generate, the position of
+// <|startoftranscript|> or -1, the first captured position); the kernels own the rest (the history and the allowed intervals of
+// Whisper's timestamp rules, transformers' WhisperTimeStampLogitsProcessor).
+struct WhState { int* cur; int* pos; int* done; int* ndone; const int* prefix; int* ti; };
 enum { TS_PLEN = 0, TS_BEGIN, TS_PEND, TS_GENTO, TS_SOT, TS_FIRSTROW, TS_H1, TS_H2, TS_HN, TS_LAST, TS_BND, WH_TS_ROWS = TS_BND + 4 };
-struct WhTsRules { int tb, eos, V, max_init; };
+// on = 0: no timestamp rules (tdx_whisper_decode, tdx_whisper_decode_xattn); tb, V and max_init are then not read
+struct WhTsRules { int on, tb, eos, V, max_init; };
 // the allowed intervals of the step that predicts the id after the history (h1 = its last id, h2 = the one before, hn = its
-// length capped at 2, last = its last timestamp id or -1); first: the history is empty and the id is the first generated one
+// length capped at 2, last = its last timestamp id or -1); first: the history is empty and the id is the first generated one.
+// Rules off: every text id, no timestamp id.
 __device__ __forceinline__ void wh_ts_bounds(int* __restrict__ ti, int b, bool first, WhTsRules r) {
-    const int hn = ti[TS_HN * WH_MAXB + b], h1 = ti[TS_H1 * WH_MAXB + b], h2 = ti[TS_H2 * WH_MAXB + b], last = ti[TS_LAST * WH_MAXB + b];
-    int text_lo = 0, ts_lo = r.tb, ts_hi = r.V - 1;
-    const bool last_ts = hn >= 1 && h1 >= r.tb, pen_ts = hn < 2 || h2 >= r.tb;
-    if (last_ts) { if (pen_ts) ts_lo = INT_MAX; else text_lo = r.eos; }
-    if (last >= 0) ts_lo = max(ts_lo, (last_ts && !pen_ts) ? last : last + 1);
-    if (first) { text_lo = INT_MAX; if (r.max_init >= 0) ts_hi = min(ts_hi, r.tb + r.max_init); }
+    int text_lo = 0, ts_lo = INT_MAX, ts_hi = -1;
+    if (r.on) {
+        const int hn = ti[TS_HN * WH_MAXB + b], h1 = ti[TS_H1 * WH_MAXB + b], h2 = ti[TS_H2 * WH_MAXB + b], last = ti[TS_LAST * WH_MAXB + b];
+        ts_lo = r.tb; ts_hi = r.V - 1;
+        const bool last_ts = hn >= 1 && h1 >= r.tb, pen_ts = hn < 2 || h2 >= r.tb;
+        if (last_ts) { if (pen_ts) ts_lo = INT_MAX; else text_lo = r.eos; }
+        if (last >= 0) ts_lo = max(ts_lo, (last_ts && !pen_ts) ? last : last + 1);
+        if (first) { text_lo = INT_MAX; if (r.max_init >= 0) ts_hi = min(ts_hi, r.tb + r.max_init); }
+    }
     int* bnd = ti + TS_BND * WH_MAXB;
     bnd[b] = text_lo; bnd[WH_MAXB + b] = ts_lo; bnd[2 * WH_MAXB + b] = ts_hi; bnd[3 * WH_MAXB + b] = first ? 1 : 0;
 }
@@ -672,9 +598,9 @@ __device__ __forceinline__ void wh_ts_push(int* __restrict__ ti, int b, int id, 
     ti[TS_HN * WH_MAXB + b] = min(ti[TS_HN * WH_MAXB + b] + 1, 2);
     if (id >= tb) ti[TS_LAST * WH_MAXB + b] = id;
 }
-// prefix [B][T]
-__global__ void wh_init_ts_kernel(WhState s, int* __restrict__ ti, int B, int T, WhTsRules r, int* __restrict__ counts) {
+__global__ void wh_init_kernel(WhState s, int B, int T, WhTsRules r, int* __restrict__ counts) {
     const int b = threadIdx.x;
+    int* ti = s.ti;
     if (b < B) {
         s.cur[b] = s.prefix[(long)b * T]; s.pos[b] = 0; s.done[b] = 0; counts[b] = 0;
         ti[TS_HN * WH_MAXB + b] = 0; ti[TS_H1 * WH_MAXB + b] = -1; ti[TS_H2 * WH_MAXB + b] = -1; ti[TS_LAST * WH_MAXB + b] = -1;
@@ -682,52 +608,56 @@ __global__ void wh_init_ts_kernel(WhState s, int* __restrict__ ti, int B, int T,
     }
     if (b == 0) *s.ndone = 0;
 }
+// the slices of a row -> one triple; 32 lanes per clip
 __device__ __forceinline__ WhTop wh_join_slices(const float* __restrict__ pm, const int* __restrict__ pi, const float* __restrict__ ps, long row, int nsl, int l) {
     WhTop t{-INFINITY, INT_MAX, 0.f};
     for (int j = l; j < nsl; j += 32) wh_merge(t, WhTop{pm[row * nsl + j], pi ? pi[row * nsl + j] : 0, ps[row * nsl + j]});
 #pragma unroll
     for (int o = 16; o >= 1; o >>= 1) {
         WhTop u{__shfl_xor(t.m, o, 64), __shfl_xor(t.i, o, 64), __shfl_xor(t.s, o, 64)};
-        WhTop lo = (l & o) ? u : t, hi = (l & o) ? t : u;           // (lower lane's, upper lane's) on both partners, as in wh_next_kernel
+        // both partners must end with the same triple: merge (lower lane's, upper lane's) in that order on both
+        WhTop lo = (l & o) ? u : t, hi = (l & o) ? t : u;
         wh_merge(lo, hi);
         t = lo;
     }
     return t;
 }
-// wh_next_kernel for tdx_whisper_decode_ts: joins the two classes' slices, applies the mass rule (every id below tb is denied
-// when the log-sum-exp of the allowed timestamp logits exceeds the largest allowed text logit), writes the step's outputs, the
-// no-speech probability at the step that fed sot_pos, the next token of the row's own prefix or the generated one, the history
-// and the allowed intervals of the next step.  A row is done after eos or after its own last step (pend).
-__global__ __launch_bounds__(1024) void wh_next_ts_kernel(const float* __restrict__ pm, const int* __restrict__ pi, const float* __restrict__ ps,
-                                                           const float* __restrict__ nm, const float* __restrict__ nsum, const float* __restrict__ nlogit, int nsl,
-                                                           WhState s, int* __restrict__ ti, int B, int T, WhTsRules r, int* __restrict__ ids,
-                                                           float* __restrict__ score, int* __restrict__ counts, float* __restrict__ nospeech) {
+// The step after the head, block = 32 B threads: joins the slices of class 0 and, under the rules, of class 1, and applies the mass
+// rule (every id below tb is denied when the log-sum-exp of the allowed timestamp logits exceeds the largest allowed text logit;
+// with class 1 empty the merge leaves class 0's triple as it is); writes the step's outputs (argmax, its log-softmax), the
+// no-speech probability at the step that fed sot_pos, the next token (of the row's own prefix while it lasts, then the generated
+// one), pos + 1, the history and the allowed intervals of the next step, the done flag and the count of finished clips.  A row
+// is done after eos or after its own last step (pend).
+__global__ __launch_bounds__(1024) void wh_next_kernel(WhHeadOut o, int nsl, WhState s, int B, int T, WhTsRules r, int* __restrict__ ids,
+                                                        float* __restrict__ score, int* __restrict__ counts, float* __restrict__ nospeech) {
     __shared__ int fin[WH_MAXB];
     const int b = threadIdx.x >> 5, l = threadIdx.x & 31;
-    const WhTop text = wh_join_slices(pm, pi, ps, b, nsl, l);
-    const WhTop ts = wh_join_slices(pm, pi, ps, (long)B + b, nsl, l);
-    WhTop ns{-INFINITY, INT_MAX, 0.f};
-    if (nospeech) ns = wh_join_slices(nm, nullptr, nsum, b, nsl, l);
+    int* ti = s.ti;
+    // the row's state first: these loads are in flight while the slices are joined, not in the serial tail of lane 0
+    const int p = s.pos[b], plen = ti[TS_PLEN * WH_MAXB + b], begin = ti[TS_BEGIN * WH_MAXB + b], gen_to = ti[TS_GENTO * WH_MAXB + b],
+              pend = ti[TS_PEND * WH_MAXB + b], sot = ti[TS_SOT * WH_MAXB + b], fed = s.prefix[(long)b * T + min(p + 1, T - 1)];
+    int d = s.done[b];
+    const WhTop text = wh_join_slices(o.pm, o.pi, o.ps, b, nsl, l);
+    WhTop ts{-INFINITY, INT_MAX, 0.f}, ns{-INFINITY, INT_MAX, 0.f};
+    if (r.on) ts = wh_join_slices(o.pm, o.pi, o.ps, (long)B + b, nsl, l);
+    if (nospeech) ns = wh_join_slices(o.nm, nullptr, o.nsum, b, nsl, l);
     if (l == 0) {
-        int d = s.done[b];
         if (!d) {
-            const int p = s.pos[b];
             WhTop t = text;
             if (ts.i != INT_MAX && (text.i == INT_MAX || ts.m + logf(ts.s) > text.m)) t = ts;
             else wh_merge(t, ts);
             const int am = t.i == INT_MAX ? r.eos : t.i;
             ids[(long)b * T + p] = am;
             score[(long)b * T + p] = -logf(t.s);
-            if (nospeech && p == ti[TS_SOT * WH_MAXB + b]) nospeech[b] = expf(nlogit[b] - ns.m) / ns.s;
-            const int plen = ti[TS_PLEN * WH_MAXB + b], begin = ti[TS_BEGIN * WH_MAXB + b];
+            if (nospeech && p == sot) nospeech[b] = expf(o.nlogit[b] - ns.m) / ns.s;
             int nxt;
-            if (p + 1 < plen) nxt = s.prefix[(long)b * T + p + 1];
+            if (p + 1 < plen) nxt = fed;
             else {
                 nxt = am;
-                if (p < ti[TS_GENTO * WH_MAXB + b]) { counts[b] += 1; if (nxt == r.eos) d = 1; }
+                if (p < gen_to) { counts[b] += 1; if (nxt == r.eos) d = 1; }
             }
-            if (p + 1 >= ti[TS_PEND * WH_MAXB + b]) d = 1;
-            if (p + 1 >= begin) wh_ts_push(ti, b, nxt, r.tb);
+            if (p + 1 >= pend) d = 1;
+            if (r.on && p + 1 >= begin) wh_ts_push(ti, b, nxt, r.tb);
             wh_ts_bounds(ti, b, p + 2 == begin, r);
             s.cur[b] = nxt;
             if (d) s.done[b] = 1;
@@ -820,13 +750,11 @@ __global__ __launch_bounds__(64) void wh_attn_comb_kernel(const float* __restric
 // projection: workgroup (listed head, clip) recomputes the head's S scores from q and the layer's cross K (16 lanes per key, as
 // above), then a full softmax over S: raw scores, the maximum, exponentials and their sum, the quotient; the intermediate values live
 // in LDS up to 4096 positions and in the output row itself beyond.  1024 threads and four key rounds in flight: one workgroup per (head, clip) is a chain of dependent loads, and with 256
-// threads and one round at a time it cost 55 us a launch.  The row is pos[b] - first_row; a finished clip, a head of another layer or a row outside the buffer: nothing is
+// threads and one round at a time it cost 55 us a launch.  The row is pos[b] - first_rows[b] (the device state's TS_FIRSTROW row); a finished clip, a head of another layer or a row outside the buffer: nothing is
 // written.  The attention kernels above are not touched, so the decode's own results keep their bits.
-// PR: the first row is per clip (first_rows[b], tdx_whisper_decode_ts); otherwise first_row serves every clip.
-template <bool PR>
 __global__ __launch_bounds__(WH_XROW_NT) void wh_xattn_row_kernel(const float* __restrict__ q, const float* __restrict__ Kc, long clip_stride, int S, int d,
                                                             int layer, const int* __restrict__ heads, const int* __restrict__ pos,
-                                                            const int* __restrict__ done, int first_row, const int* __restrict__ first_rows, int max_rows,
+                                                            const int* __restrict__ done, const int* __restrict__ first_rows, int max_rows,
                                                             float* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) float qs[DK];
     __shared__ float red[WH_XROW_NT / 64];
@@ -834,7 +762,7 @@ __global__ __launch_bounds__(WH_XROW_NT) void wh_xattn_row_kernel(const float* _
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hi = blockIdx.x, b = blockIdx.y, nh = gridDim.x;
     if (heads[2 * hi] != layer || done[b]) return;                  // (uniform over the workgroup, like the two returns below)
-    const int row = pos[b] - (PR ? first_rows[b] : first_row);
+    const int row = pos[b] - first_rows[b];
     if (row < 0 || row >= max_rows) return;
     const int h = heads[2 * hi + 1];
     float* o = out + (((size_t)b * nh + hi) * max_rows + row) * (size_t)S;
@@ -1044,34 +972,21 @@ int launch_skinny(SkArgs a, int njobs, float* xn, float* partial, hipStream_t st
     LAUNCH_CHECK();
     return TDX_OK;
 }
-template <int BT>
-int launch_head_t(const SkArgs& a, const unsigned char* mask, int begin, float* pm, int* pi, float* ps, int nsl, hipStream_t st) {
-    hipLaunchKernelGGL(wh_head_kernel<BT>, dim3(nsl), dim3(256), 0, st, a, mask, begin, pm, pi, ps, nsl);
+template <int BT, bool TS>
+int launch_head_t(const SkArgs& a, const unsigned char* mask, const int* bnd, int tb, int want_ns, int ns_id, const WhHeadOut& o, int nsl, hipStream_t st) {
+    hipLaunchKernelGGL((wh_head_kernel<BT, TS>), dim3(nsl), dim3(256), 0, st, a, mask, bnd, tb, want_ns, ns_id, o, nsl);
     LAUNCH_CHECK();
     return TDX_OK;
 }
-int launch_head(const SkArgs& a, const unsigned char* mask, int begin, float* pm, int* pi, float* ps, int nsl, hipStream_t st) {
-    if (a.B <= 1) return launch_head_t<1>(a, mask, begin, pm, pi, ps, nsl, st);
-    if (a.B <= 2) return launch_head_t<2>(a, mask, begin, pm, pi, ps, nsl, st);
-    if (a.B <= 4) return launch_head_t<4>(a, mask, begin, pm, pi, ps, nsl, st);
-    if (a.B <= 8) return launch_head_t<8>(a, mask, begin, pm, pi, ps, nsl, st);
-    if (a.B <= 16) return launch_head_t<16>(a, mask, begin, pm, pi, ps, nsl, st);
-    return launch_head_t<32>(a, mask, begin, pm, pi, ps, nsl, st);
-}
-struct HeadTsOut { float* pm; int* pi; float* ps; float* nm; float* nsum; float* nlogit; };
-template <int BT>
-int launch_head_ts_t(const SkArgs& a, const unsigned char* mask, const int* bnd, int tb, int want_ns, int ns_id, const HeadTsOut& o, int nsl, hipStream_t st) {
-    hipLaunchKernelGGL(wh_head_ts_kernel<BT>, dim3(nsl), dim3(256), 0, st, a, mask, bnd, tb, want_ns, ns_id, o.pm, o.pi, o.ps, o.nm, o.nsum, o.nlogit, nsl);
-    LAUNCH_CHECK();
-    return TDX_OK;
-}
-int launch_head_ts(const SkArgs& a, const unsigned char* mask, const int* bnd, int tb, int want_ns, int ns_id, const HeadTsOut& o, int nsl, hipStream_t st) {
-    if (a.B <= 1) return launch_head_ts_t<1>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
-    if (a.B <= 2) return launch_head_ts_t<2>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
-    if (a.B <= 4) return launch_head_ts_t<4>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
-    if (a.B <= 8) return launch_head_ts_t<8>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
-    if (a.B <= 16) return launch_head_ts_t<16>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
-    return launch_head_ts_t<32>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+// TS: the timestamp rules are on (two classes of triples, the no-speech pair when want_ns)
+template <bool TS>
+int launch_head(const SkArgs& a, const unsigned char* mask, const int* bnd, int tb, int want_ns, int ns_id, const WhHeadOut& o, int nsl, hipStream_t st) {
+    if (a.B <= 1) return launch_head_t<1, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+    if (a.B <= 2) return launch_head_t<2, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+    if (a.B <= 4) return launch_head_t<4, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+    if (a.B <= 8) return launch_head_t<8, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+    if (a.B <= 16) return launch_head_t<16, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+    return launch_head_t<32, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
 }
 SkJob sk_job(const float* W, const float* bias, const float* res, float* y, long ld, int brow = 0, int gelu = 0) {
     return SkJob{W, bias, res, y, ld, brow, gelu};
@@ -1113,8 +1028,8 @@ EncWs enc_ws(const tdx_whisper* h, int B) {
     w.total = o;
     return w;
 }
-// tsi .. tsprefix: tdx_whisper_decode_ts only (the rows' state, the second class of head triples, the no-speech pairs, [B][T] prefixes)
-struct DecWs { size_t x, xn, skp, q, ao, hb, part, pm, pi, ps, state, prefix, mask, heads, tsi, pm2, pi2, ps2, nm, nsum, nlogit, tsprefix, cache, total; int nsl, nch_self, nch_cross; };
+// pm, pi, ps: the head's triples [2][B][nsl] (two classes); nm, nsum, nlogit: the no-speech pairs; ti: the rows' state; prefix [B][T]
+struct DecWs { size_t x, xn, skp, q, ao, hb, part, state, mask, heads, ti, pm, pi, ps, nm, nsum, nlogit, prefix, cache, total; int nsl, nch_self, nch_cross; };
 DecWs dec_ws(const tdx_whisper* h, int B) {
     const size_t d = h->c.d_model, T = h->c.n_text_ctx, H = h->c.dec_heads;
     DecWs w; size_t o = 0;
@@ -1125,15 +1040,13 @@ DecWs dec_ws(const tdx_whisper* h, int B) {
     w.skp = o; o += B > 8 ? al((size_t)3 * SKM_MAXKS * WH_MAXB * std::max<size_t>(d, h->c.dec_ffn)) : 0;
     w.q = o; o += al(B * d); w.ao = o; o += al(B * d); w.hb = o; o += al(B * (size_t)h->c.dec_ffn);
     w.part = o; o += al(B * H * (size_t)std::max(w.nch_self, w.nch_cross) * (DK + 2));
-    w.pm = o; o += al((size_t)B * w.nsl); w.pi = o; o += al((size_t)B * w.nsl); w.ps = o; o += al((size_t)B * w.nsl);
     w.state = o; o += al(4 * WH_MAXB);
-    w.prefix = o; o += al(T);
     w.mask = o; o += al(((size_t)h->c.vocab + 3) / 4);
     w.heads = o; o += al(2 * WH_MAXHEADS);
-    w.tsi = o; o += al((size_t)WH_TS_ROWS * WH_MAXB);
-    w.pm2 = o; o += al((size_t)2 * B * w.nsl); w.pi2 = o; o += al((size_t)2 * B * w.nsl); w.ps2 = o; o += al((size_t)2 * B * w.nsl);
+    w.ti = o; o += al((size_t)WH_TS_ROWS * WH_MAXB);
+    w.pm = o; o += al((size_t)2 * B * w.nsl); w.pi = o; o += al((size_t)2 * B * w.nsl); w.ps = o; o += al((size_t)2 * B * w.nsl);
     w.nm = o; o += al((size_t)B * w.nsl); w.nsum = o; o += al((size_t)B * w.nsl); w.nlogit = o; o += al(WH_MAXB);
-    w.tsprefix = o; o += al((size_t)B * T);
+    w.prefix = o; o += al((size_t)B * T);
     w.cache = o; o += al((size_t)h->c.dec_layers * 2 * B * T * d);
     w.total = o;
     return w;
@@ -1310,7 +1223,8 @@ int tdx_whisper_encode(tdx_whisper* h, const float* feat_dev, int B, float* enc_
     return TDX_OK;
 }
 
-// the capture of tdx_whisper_decode_xattn: (layer, head) pairs, the first position and the rows of the buffer
+// the capture of the alignment heads: (layer, head) pairs and the rows of the buffer; first_row: tdx_whisper_decode_xattn's, for
+// every clip (the clips of tdx_whisper_decode_ts have one each)
 struct WhCapture { const int* heads_host; int nh, first_row, max_rows; float* xattn_dev; };
 
 // the argument checks the decode entry points share, each with its own message
@@ -1351,10 +1265,10 @@ static SkArgs wh_sk_args(const WhState& s, int B, const float* xin, const float*
     return a;
 }
 // One decode step up to the vocabulary head, shared by the three decode entry points: the embedding of every row's current token
-// and the decoder layers.  first_rows_dev != NULL: the capture's first row is per clip.
+// and the decoder layers.
 struct WhStepCtx {
     tdx_whisper* h; const DecWs* w; float* f; WhState s; int B; const float* enc_state_dev; const WhCapture* cap; const char* listed;
-    const int* heads_dev; const int* first_rows_dev; hipStream_t st;
+    const int* heads_dev; hipStream_t st;
 };
 static int wh_decoder_step(const WhStepCtx& c) {
     tdx_whisper* h = c.h;
@@ -1391,12 +1305,8 @@ static int wh_decoder_step(const WhStepCtx& c) {
         a.job[0] = sk_job(L.ca.Wq, L.ca.bq, nullptr, q, d);
         TRY(launch_skinny(a, 1, xn, skp, st));
         if (cap && c.listed[l]) {
-            if (c.first_rows_dev)
-                hipLaunchKernelGGL(wh_xattn_row_kernel<true>, dim3(cap->nh, B), dim3(WH_XROW_NT), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay, (long)S * d, S, d, l,
-                                   c.heads_dev, (const int*)s.pos, (const int*)s.done, 0, c.first_rows_dev, cap->max_rows, cap->xattn_dev);
-            else
-                hipLaunchKernelGGL(wh_xattn_row_kernel<false>, dim3(cap->nh, B), dim3(WH_XROW_NT), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay, (long)S * d, S, d, l,
-                                   c.heads_dev, (const int*)s.pos, (const int*)s.done, cap->first_row, (const int*)nullptr, cap->max_rows, cap->xattn_dev);
+            hipLaunchKernelGGL(wh_xattn_row_kernel, dim3(cap->nh, B), dim3(WH_XROW_NT), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay, (long)S * d, S, d, l,
+                               c.heads_dev, (const int*)s.pos, (const int*)s.done, (const int*)(s.ti + TS_FIRSTROW * WH_MAXB), cap->max_rows, cap->xattn_dev);
             LAUNCH_CHECK();
         }
         hipLaunchKernelGGL(wh_attn_part_kernel, dim3(w.nch_cross, H, B), dim3(256), 0, st, q, enc_state_dev + (size_t)(2 * l) * clay,
@@ -1417,64 +1327,70 @@ static int wh_decoder_step(const WhStepCtx& c) {
     return TDX_OK;
 }
 
-static int whisper_decode_impl(const std::string& fn, const WhCapture* cap, tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host,
-                               int prefix_len, const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int eos, int max_new,
-                               int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_, size_t ws_bytes, void* stream) {
-    if (cap) TRY(wh_check_capture(fn, *cap));
-    if (!h || !enc_state_dev || !prefix_host || !step_ids_dev || !step_scores_dev || !counts_dev || !ws_ || B < 1 || B > WH_MAXB || prefix_len < 1 ||
-        n_suppress < 0 || n_begin < 0 || (n_suppress > 0 && !suppress_host) || (n_begin > 0 && !begin_suppress_host) || max_new < 0)
-        return tdx::fail(TDX_E_INVALID, fn + ": bad argument (1 <= B <= 32, prefix_len >= 1, max_new >= 0)");
-    const tdx_whisper_config& c = h->c;
-    const int V = c.vocab, T = c.n_text_ctx, d = c.d_model, H = c.dec_heads, Ld = c.dec_layers;
-    if (prefix_len > T) return tdx::fail(TDX_E_INVALID, fn + ": the prefix is longer than n_text_ctx");
-    std::vector<char> listed(Ld, 0);
-    if (cap) TRY(wh_listed_layers(fn, *cap, Ld, H, listed));
-    if (eos < 0 || eos >= V) return tdx::fail(TDX_E_INVALID, fn + ": eos outside the vocabulary");
-    for (int i = 0; i < prefix_len; ++i)
-        if (prefix_host[i] < 0 || prefix_host[i] >= V) return tdx::fail(TDX_E_INVALID, fn + ": prefix id outside the vocabulary");
+// The host image of the rows' state (rows TS_PLEN .. TS_FIRSTROW of `ti`) and every row's prefix at pitch T.
+struct WhRows {
+    std::vector<int> st, prefix;
+    int T, p_end = 0;
+    WhRows(int B, int T_) : st((size_t)(TS_FIRSTROW + 1) * WH_MAXB, 0), prefix((size_t)B * T_, 0), T(T_) {}
+    // steps p = 0 .. pend - 1 read the token at position p and write cache row p (< T); the tokens at positions plen .. gen_to are
+    // generated by the steps plen - 1 .. gen_to - 1.  With nothing to generate the prefix is still scored whole.
+    void set(int b, int plen, int begin, int max_new, int sot, int first_row) {
+        const int gen_to = plen - 1 + std::min(max_new, T - plen), pend = std::max(plen, gen_to);
+        st[TS_PLEN * WH_MAXB + b] = plen; st[TS_BEGIN * WH_MAXB + b] = begin; st[TS_PEND * WH_MAXB + b] = pend; st[TS_GENTO * WH_MAXB + b] = gen_to;
+        st[TS_SOT * WH_MAXB + b] = sot; st[TS_FIRSTROW * WH_MAXB + b] = first_row;
+        p_end = std::max(p_end, pend);
+    }
+};
+
+// The decode loop of the three entry points, which have checked their own arguments and filled `rows`: the static mask, the
+// workspace check, the uploads, the init launch, then 16 steps at a time (decoder layers, head, next) and one pinned read.
+// rules.on selects the head's instantiation; nospeech_dev (rules on only) asks for the no-speech pair.
+static int wh_decode_run(const std::string& fn, tdx_whisper* h, const float* enc_state_dev, int B, const WhRows& rows, const WhTsRules& rules,
+                         const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int no_speech_id, float* nospeech_dev,
+                         const WhCapture* cap, const std::vector<char>& listed, int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_,
+                         size_t ws_bytes, void* stream) {
+    const int V = h->c.vocab, T = h->c.n_text_ctx, d = h->c.d_model;
     std::vector<unsigned char> mask;
     TRY(wh_static_mask(fn, V, suppress_host, n_suppress, begin_suppress_host, n_begin, mask));
     if (ws_bytes < tdx_whisper_workspace_bytes(h, B)) return tdx::fail(TDX_E_WORKSPACE, fn + ": workspace too small");
     tdx::DeviceGuard guard(h->device);
     if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
     hipStream_t st = (hipStream_t)stream;
-    // steps p = 0 .. p_end - 1 read the token at position p and write cache row p (< T); the tokens at positions prefix_len ..
-    // gen_to are generated by the steps prefix_len - 1 .. gen_to - 1.  With nothing to generate the prefix is still scored whole.
-    const int new_eff = std::min(max_new, T - prefix_len);
-    const int gen_to = prefix_len - 1 + new_eff;
-    const int p_end = std::max(prefix_len, gen_to);
     const DecWs w = dec_ws(h, B);
     float* f = (float*)ws_;
-    float *x = f + w.x, *pm = f + w.pm, *ps = f + w.ps;
-    int* pi = (int*)(f + w.pi);
+    float* x = f + w.x;
+    const WhHeadOut ho{f + w.pm, (int*)(f + w.pi), f + w.ps, f + w.nm, f + w.nsum, f + w.nlogit};
     int* sti = (int*)(f + w.state);
+    int* ti = (int*)(f + w.ti);
     int* prefix_dev = (int*)(f + w.prefix);
     unsigned char* mask_dev = (unsigned char*)(f + w.mask);
-    const WhState s{sti, sti + WH_MAXB, sti + 2 * WH_MAXB, sti + 3 * WH_MAXB, prefix_dev};
-    hipError_t rc = hipMemcpyAsync(prefix_dev, prefix_host, sizeof(int) * prefix_len, hipMemcpyHostToDevice, st);
-    if (rc == hipSuccess) rc = hipMemcpyAsync(mask_dev, mask.data(), mask.size(), hipMemcpyHostToDevice, st);
     int* heads_dev = (int*)(f + w.heads);
+    const WhState s{sti, sti + WH_MAXB, sti + 2 * WH_MAXB, sti + 3 * WH_MAXB, prefix_dev, ti};
+    hipError_t rc = hipMemcpyAsync(prefix_dev, rows.prefix.data(), sizeof(int) * rows.prefix.size(), hipMemcpyHostToDevice, st);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(ti, rows.st.data(), sizeof(int) * rows.st.size(), hipMemcpyHostToDevice, st);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(mask_dev, mask.data(), mask.size(), hipMemcpyHostToDevice, st);
     if (rc == hipSuccess && cap) rc = hipMemcpyAsync(heads_dev, cap->heads_host, sizeof(int) * 2 * cap->nh, hipMemcpyHostToDevice, st);
     if (rc != hipSuccess) return tdx::fail_hip(rc, __FILE__, __LINE__);
-    hipLaunchKernelGGL(wh_init_kernel, dim3(1), dim3(64), 0, st, s, B, counts_dev);
+    hipLaunchKernelGGL(wh_init_kernel, dim3(1), dim3(64), 0, st, s, B, T, rules, counts_dev);
     LAUNCH_CHECK();
-    const WhStepCtx ctx{h, &w, f, s, B, enc_state_dev, cap, listed.data(), (const int*)heads_dev, nullptr, st};
+    const WhStepCtx ctx{h, &w, f, s, B, enc_state_dev, cap, listed.data(), (const int*)heads_dev, st};
+    const int* bnd = ti + TS_BND * WH_MAXB;
     int status = TDX_OK;
-    auto step = [&](int p) -> int {
+    auto step = [&]() -> int {
         TRY(wh_decoder_step(ctx));
         SkArgs a = wh_sk_args(s, B, x, h->dln_g, h->dln_b, V, d);
         a.job[0] = sk_job(h->tok, nullptr, nullptr, nullptr, 0);
-        TRY(launch_head(a, mask_dev, p == prefix_len - 1, pm, pi, ps, w.nsl, st));
-        hipLaunchKernelGGL(wh_next_kernel, dim3(1), dim3(32 * B), 0, st, pm, pi, ps, w.nsl, s, B, T, prefix_len, gen_to, eos, step_ids_dev, step_scores_dev,
-                           counts_dev);
+        TRY(rules.on ? launch_head<true>(a, mask_dev, bnd, rules.tb, nospeech_dev != nullptr, no_speech_id, ho, w.nsl, st)
+                     : launch_head<false>(a, mask_dev, bnd, 0, 0, 0, ho, w.nsl, st));
+        hipLaunchKernelGGL(wh_next_kernel, dim3(1), dim3(32 * B), 0, st, ho, w.nsl, s, B, T, rules, step_ids_dev, step_scores_dev, counts_dev, nospeech_dev);
         LAUNCH_CHECK();
         return TDX_OK;
     };
-    for (int p = 0; p < p_end && status == TDX_OK;) {
-        const int n = std::min(WH_CHUNK, p_end - p);
-        for (int i = 0; i < n && status == TDX_OK; ++i) status = step(p + i);
+    for (int p = 0; p < rows.p_end && status == TDX_OK;) {
+        const int n = std::min(WH_CHUNK, rows.p_end - p);
+        for (int i = 0; i < n && status == TDX_OK; ++i) status = step();
         p += n;
-        // one host read per chunk: the number of finished clips (also what keeps `mask` alive until its copy has run)
+        // one host read per chunk: the number of finished clips (also what keeps the host copies alive until they have been read)
         rc = hipMemcpyAsync(h->pinned, s.ndone, sizeof(int), hipMemcpyDeviceToHost, st);
         if (rc == hipSuccess) rc = hipStreamSynchronize(st);
         if (rc != hipSuccess) return tdx::fail_hip(rc, __FILE__, __LINE__);
@@ -1483,11 +1399,36 @@ static int whisper_decode_impl(const std::string& fn, const WhCapture* cap, tdx_
     return status;
 }
 
+// tdx_whisper_decode and tdx_whisper_decode_xattn: one prefix for every row, begin = prefix_len, no rules, no no-speech pair
+static int wh_decode_plain(const std::string& fn, const WhCapture* cap, tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host,
+                           int prefix_len, const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int eos, int max_new,
+                           int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_, size_t ws_bytes, void* stream) {
+    if (cap) TRY(wh_check_capture(fn, *cap));
+    if (!h || !enc_state_dev || !prefix_host || !step_ids_dev || !step_scores_dev || !counts_dev || !ws_ || B < 1 || B > WH_MAXB || prefix_len < 1 ||
+        n_suppress < 0 || n_begin < 0 || (n_suppress > 0 && !suppress_host) || (n_begin > 0 && !begin_suppress_host) || max_new < 0)
+        return tdx::fail(TDX_E_INVALID, fn + ": bad argument (1 <= B <= 32, prefix_len >= 1, max_new >= 0)");
+    const tdx_whisper_config& c = h->c;
+    const int V = c.vocab, T = c.n_text_ctx;
+    if (prefix_len > T) return tdx::fail(TDX_E_INVALID, fn + ": the prefix is longer than n_text_ctx");
+    std::vector<char> listed(c.dec_layers, 0);
+    if (cap) TRY(wh_listed_layers(fn, *cap, c.dec_layers, c.dec_heads, listed));
+    if (eos < 0 || eos >= V) return tdx::fail(TDX_E_INVALID, fn + ": eos outside the vocabulary");
+    for (int i = 0; i < prefix_len; ++i)
+        if (prefix_host[i] < 0 || prefix_host[i] >= V) return tdx::fail(TDX_E_INVALID, fn + ": prefix id outside the vocabulary");
+    WhRows rows(B, T);
+    for (int b = 0; b < B; ++b) {
+        std::copy(prefix_host, prefix_host + prefix_len, rows.prefix.begin() + (size_t)b * T);
+        rows.set(b, prefix_len, prefix_len, max_new, -1, cap ? cap->first_row : 0);
+    }
+    return wh_decode_run(fn, h, enc_state_dev, B, rows, WhTsRules{0, 0, eos, V, -1}, suppress_host, n_suppress, begin_suppress_host, n_begin, 0, nullptr, cap,
+                         listed, step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
+}
+
 int tdx_whisper_decode(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int prefix_len, const int* suppress_host, int n_suppress,
                        const int* begin_suppress_host, int n_begin, int eos, int max_new, int* step_ids_dev, float* step_scores_dev, int* counts_dev,
                        void* ws_, size_t ws_bytes, void* stream) {
-    return whisper_decode_impl("tdx_whisper_decode", nullptr, h, enc_state_dev, B, prefix_host, prefix_len, suppress_host, n_suppress, begin_suppress_host,
-                               n_begin, eos, max_new, step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
+    return wh_decode_plain("tdx_whisper_decode", nullptr, h, enc_state_dev, B, prefix_host, prefix_len, suppress_host, n_suppress, begin_suppress_host,
+                           n_begin, eos, max_new, step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
 }
 
 int tdx_whisper_decode_xattn(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int prefix_len, const int* suppress_host,
@@ -1495,8 +1436,8 @@ int tdx_whisper_decode_xattn(tdx_whisper* h, const float* enc_state_dev, int B, 
                              int first_row, int max_rows, float* xattn_dev, int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_,
                              size_t ws_bytes, void* stream) {
     const WhCapture cap{heads_host, nh, first_row, max_rows, xattn_dev};
-    return whisper_decode_impl("tdx_whisper_decode_xattn", &cap, h, enc_state_dev, B, prefix_host, prefix_len, suppress_host, n_suppress,
-                               begin_suppress_host, n_begin, eos, max_new, step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
+    return wh_decode_plain("tdx_whisper_decode_xattn", &cap, h, enc_state_dev, B, prefix_host, prefix_len, suppress_host, n_suppress,
+                           begin_suppress_host, n_begin, eos, max_new, step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
 }
 
 int tdx_whisper_decode_ts(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int max_prefix, const int* prefix_len_host,
@@ -1509,23 +1450,21 @@ int tdx_whisper_decode_ts(tdx_whisper* h, const float* enc_state_dev, int B, con
         B > WH_MAXB || max_prefix < 1 || n_suppress < 0 || n_begin < 0 || (n_suppress > 0 && !suppress_host) || (n_begin > 0 && !begin_suppress_host))
         return tdx::fail(TDX_E_INVALID, fn + ": bad argument (1 <= B <= 32, max_prefix >= 1)");
     const tdx_whisper_config& c = h->c;
-    const int V = c.vocab, T = c.n_text_ctx, d = c.d_model, H = c.dec_heads, Ld = c.dec_layers;
+    const int V = c.vocab, T = c.n_text_ctx;
     const int tb = no_timestamps_id + 1;
     if (no_timestamps_id < 0 || tb >= V) return tdx::fail(TDX_E_INVALID, fn + ": the first timestamp id (no_timestamps_id + 1) is outside the vocabulary");
     if (eos < 0 || eos >= V) return tdx::fail(TDX_E_INVALID, fn + ": eos outside the vocabulary");
     if (eos >= tb) return tdx::fail(TDX_E_INVALID, fn + ": eos must be below the first timestamp id");
     if (nospeech_dev && !sot_pos_host) return tdx::fail(TDX_E_INVALID, fn + ": sot_pos_host must not be NULL when nospeech_dev is given");
     if (nospeech_dev && (no_speech_id < 0 || no_speech_id >= V)) return tdx::fail(TDX_E_INVALID, fn + ": no_speech_id outside the vocabulary");
-    WhCapture capv{heads_host, nh, 0, max_rows, xattn_dev};
+    const WhCapture capv{heads_host, nh, 0, max_rows, xattn_dev};
     const WhCapture* cap = heads_host ? &capv : nullptr;
-    std::vector<char> listed(Ld, 0);
+    std::vector<char> listed(c.dec_layers, 0);
     if (cap) {
         TRY(wh_check_capture(fn, *cap));
-        TRY(wh_listed_layers(fn, *cap, Ld, H, listed));
+        TRY(wh_listed_layers(fn, *cap, c.dec_layers, c.dec_heads, listed));
     }
-    // rows TS_PLEN .. TS_FIRSTROW of the device state, and every row's prefix at pitch T
-    std::vector<int> hst((size_t)(TS_FIRSTROW + 1) * WH_MAXB, 0), pre((size_t)B * T, 0);
-    int p_end = 0;
+    WhRows rows(B, T);
     for (int b = 0; b < B; ++b) {
         const int pl = prefix_len_host[b];
         const std::string row = "row " + std::to_string(b);
@@ -1540,64 +1479,16 @@ int tdx_whisper_decode_ts(tdx_whisper* h, const float* enc_state_dev, int B, con
         for (int i = 0; i < pl; ++i) {
             const int id = prefix_host[(size_t)b * max_prefix + i];
             if (id < 0 || id >= V) return tdx::fail(TDX_E_INVALID, fn + ": prefix id outside the vocabulary");
-            pre[(size_t)b * T + i] = id;
+            rows.prefix[(size_t)b * T + i] = id;
         }
-        const int gen_to = pl - 1 + std::min(max_new_host[b], T - pl), pend = std::max(pl, gen_to);
-        hst[TS_PLEN * WH_MAXB + b] = pl; hst[TS_BEGIN * WH_MAXB + b] = bg; hst[TS_PEND * WH_MAXB + b] = pend; hst[TS_GENTO * WH_MAXB + b] = gen_to;
-        hst[TS_SOT * WH_MAXB + b] = nospeech_dev ? sot_pos_host[b] : -1; hst[TS_FIRSTROW * WH_MAXB + b] = fr;
-        p_end = std::max(p_end, pend);
+        rows.set(b, pl, bg, max_new_host[b], nospeech_dev ? sot_pos_host[b] : -1, fr);
     }
-    std::vector<unsigned char> mask;
-    TRY(wh_static_mask(fn, V, suppress_host, n_suppress, begin_suppress_host, n_begin, mask));
-    if (ws_bytes < tdx_whisper_workspace_bytes(h, B)) return tdx::fail(TDX_E_WORKSPACE, fn + ": workspace too small");
-    tdx::DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
-    hipStream_t st = (hipStream_t)stream;
-    const DecWs w = dec_ws(h, B);
-    float* f = (float*)ws_;
-    float* x = f + w.x;
-    const HeadTsOut ho{f + w.pm2, (int*)(f + w.pi2), f + w.ps2, f + w.nm, f + w.nsum, f + w.nlogit};
-    int* sti = (int*)(f + w.state);
-    int* tsi = (int*)(f + w.tsi);
-    int* prefix_dev = (int*)(f + w.tsprefix);
-    unsigned char* mask_dev = (unsigned char*)(f + w.mask);
-    int* heads_dev = (int*)(f + w.heads);
-    const WhState s{sti, sti + WH_MAXB, sti + 2 * WH_MAXB, sti + 3 * WH_MAXB, prefix_dev};
     // (an index past the last timestamp id allows every timestamp: clamped, so that tb + index cannot overflow)
-    const WhTsRules rules{tb, eos, V, std::min(max_initial_timestamp_index, V - 1 - tb)};
-    hipError_t rc = hipMemcpyAsync(prefix_dev, pre.data(), sizeof(int) * pre.size(), hipMemcpyHostToDevice, st);
-    if (rc == hipSuccess) rc = hipMemcpyAsync(tsi, hst.data(), sizeof(int) * hst.size(), hipMemcpyHostToDevice, st);
-    if (rc == hipSuccess) rc = hipMemcpyAsync(mask_dev, mask.data(), mask.size(), hipMemcpyHostToDevice, st);
-    if (rc == hipSuccess && cap) rc = hipMemcpyAsync(heads_dev, heads_host, sizeof(int) * 2 * nh, hipMemcpyHostToDevice, st);
-    if (rc != hipSuccess) return tdx::fail_hip(rc, __FILE__, __LINE__);
-    hipLaunchKernelGGL(wh_init_ts_kernel, dim3(1), dim3(64), 0, st, s, tsi, B, T, rules, counts_dev);
-    LAUNCH_CHECK();
-    const WhStepCtx ctx{h, &w, f, s, B, enc_state_dev, cap, listed.data(), (const int*)heads_dev, (const int*)(tsi + TS_FIRSTROW * WH_MAXB), st};
-    int status = TDX_OK;
-    auto step = [&]() -> int {
-        TRY(wh_decoder_step(ctx));
-        SkArgs a = wh_sk_args(s, B, x, h->dln_g, h->dln_b, V, d);
-        a.job[0] = sk_job(h->tok, nullptr, nullptr, nullptr, 0);
-        TRY(launch_head_ts(a, mask_dev, tsi + TS_BND * WH_MAXB, tb, nospeech_dev != nullptr, no_speech_id, ho, w.nsl, st));
-        hipLaunchKernelGGL(wh_next_ts_kernel, dim3(1), dim3(32 * B), 0, st, (const float*)ho.pm, (const int*)ho.pi, (const float*)ho.ps, (const float*)ho.nm,
-                           (const float*)ho.nsum, (const float*)ho.nlogit, w.nsl, s, tsi, B, T, rules, step_ids_dev, step_scores_dev, counts_dev, nospeech_dev);
-        LAUNCH_CHECK();
-        return TDX_OK;
-    };
-    for (int p = 0; p < p_end && status == TDX_OK;) {
-        const int n = std::min(WH_CHUNK, p_end - p);
-        for (int i = 0; i < n && status == TDX_OK; ++i) status = step();
-        p += n;
-        // one host read per chunk, as in tdx_whisper_decode (it also keeps the host copies alive until they have been read)
-        rc = hipMemcpyAsync(h->pinned, s.ndone, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (rc == hipSuccess) rc = hipStreamSynchronize(st);
-        if (rc != hipSuccess) return tdx::fail_hip(rc, __FILE__, __LINE__);
-        if (*h->pinned >= B) break;
-    }
-    return status;
+    const WhTsRules rules{1, tb, eos, V, std::min(max_initial_timestamp_index, V - 1 - tb)};
+    return wh_decode_run(fn, h, enc_state_dev, B, rows, rules, suppress_host, n_suppress, begin_suppress_host, n_begin, no_speech_id, nospeech_dev, cap, listed,
+                         step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
 }
 
-// frames per block of tdx_whisper_logmel_long: the workspace holds one block's padded samples and power rows
 constexpr int WH_LONG_FBLK = 4096;
 constexpr long WH_LONG_MAXN = 1L << 30;
 

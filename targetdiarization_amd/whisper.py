@@ -326,6 +326,10 @@ def longform_prefix(init, history, condition: bool, first_prompt, timestamp_begi
     return list(init)
 
 
+def _int_array(v):                                      # (one element for an empty list: never a NULL pointer)
+    return (C.c_int * max(1, len(v)))(*[int(t) for t in v])
+
+
 class WhisperASR:
     def __init__(self, state_dict, config, device="cuda:0", token_list=None, tokenizer=None, generation_config=None, alignment_heads=None):
         self.cfg = c = whisper_config(config)
@@ -354,6 +358,29 @@ class WhisperASR:
         if not 1 <= B <= MAX_BATCH:
             raise _lib.TdxError(f"WhisperASR: {B} clips in one call (1..{MAX_BATCH})")
 
+    def _check_state(self, who, state) -> int:
+        c = self.cfg
+        B = int(state.shape[2])
+        self._check_batch(B)
+        if tuple(state.shape) != (c["dec_layers"], 2, B, c["n_audio_ctx"], c["d_model"]) or not state.is_contiguous():
+            raise _lib.TdxError(f"WhisperASR.{who}: state is not encode(..., with_state=True)'s")
+        return B
+
+    def _decode_buffers(self, B):                       # step_ids, step_scores, counts
+        T = self.cfg["n_text_ctx"]
+        return (torch.full((B, T), -1, dtype=torch.int32, device=self.device), torch.zeros(B, T, device=self.device),
+                torch.zeros(B, dtype=torch.int32, device=self.device))
+
+    def _alloc_xattn(self, B, nh, max_rows):            # None: a shape the C-ABI call rejects with its own message
+        ok = 1 <= nh <= MAX_ALIGN_HEADS and max_rows >= 1
+        return torch.zeros(B, nh, max_rows, self.cfg["n_audio_ctx"], device=self.device) if ok else None
+
+    def _call(self, fn, B, *args):
+        """fn(handle, *args, workspace, its bytes, the current stream) under the model's guard"""
+        with self._guard.call():
+            ws = self._guard.workspace(self.workspace_bytes(B))
+            _lib.check(fn(self._h, *args, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream))
+
     def workspace_bytes(self, B):
         return int(self._l.tdx_whisper_workspace_bytes(self._h, B))
 
@@ -379,11 +406,7 @@ class WhisperASR:
         self._check_batch(B)
         lens_dev = torch.as_tensor(lens, dtype=torch.int32).to(self.device) if lens is not None else None
         feat = torch.empty(B, self.cfg["n_mels"], 2 * self.cfg["n_audio_ctx"], device=self.device)
-        with self._guard.call():
-            ws = self._guard.workspace(self.workspace_bytes(B))
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._l.tdx_whisper_logmel(self._h, wav.data_ptr(), lens_dev.data_ptr() if lens_dev is not None else None, B, N,
-                                                  feat.data_ptr(), ws.data_ptr(), ws.numel(), st))
+        self._call(self._l.tdx_whisper_logmel, B, wav.data_ptr(), lens_dev.data_ptr() if lens_dev is not None else None, B, N, feat.data_ptr())
         return feat
 
     def encode(self, feats: torch.Tensor, with_state: bool = False):
@@ -398,34 +421,19 @@ class WhisperASR:
             raise _lib.TdxError(f"WhisperASR.encode: features of shape {tuple(feats.shape)}, expected [B, {c['n_mels']}, {2 * c['n_audio_ctx']}]")
         enc = torch.empty(B, c["n_audio_ctx"], c["d_model"], device=self.device)
         state = torch.empty(c["dec_layers"], 2, B, c["n_audio_ctx"], c["d_model"], device=self.device) if with_state else None
-        with self._guard.call():
-            ws = self._guard.workspace(self.workspace_bytes(B))
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._l.tdx_whisper_encode(self._h, feats.data_ptr(), B, enc.data_ptr(), state.data_ptr() if with_state else None,
-                                                  ws.data_ptr(), ws.numel(), st))
+        self._call(self._l.tdx_whisper_encode, B, feats.data_ptr(), B, enc.data_ptr(), state.data_ptr() if with_state else None)
         return (enc, state) if with_state else enc
 
     def decode(self, state: torch.Tensor, prefix, max_new: int, suppress=(), begin_suppress=(), eos=None):
         """greedy decoding from encode()'s state under one prefix -> device tensors step_ids int32 [B, n_text_ctx], step_scores
         [B, n_text_ctx] (step p at column p; columns no step reached hold -1 / 0) and counts int32 [B]"""
         self._check_open()
-        c = self.cfg
-        B = int(state.shape[2])
-        self._check_batch(B)
-        if tuple(state.shape) != (c["dec_layers"], 2, B, c["n_audio_ctx"], c["d_model"]) or not state.is_contiguous():
-            raise _lib.TdxError("WhisperASR.decode: state is not encode(..., with_state=True)'s")
+        B = self._check_state("decode", state)
         eos = int(self.gen_cfg["eos_token_id"] if eos is None else eos)
-        ids = torch.full((B, c["n_text_ctx"]), -1, dtype=torch.int32, device=self.device)
-        scores = torch.zeros(B, c["n_text_ctx"], device=self.device)
-        counts = torch.zeros(B, dtype=torch.int32, device=self.device)
-        arr = lambda v: (C.c_int * max(1, len(v)))(*[int(t) for t in v])
+        ids, scores, counts = self._decode_buffers(B)
         prefix, suppress, begin_suppress = list(prefix), list(suppress), list(begin_suppress)
-        with self._guard.call():
-            ws = self._guard.workspace(self.workspace_bytes(B))
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._l.tdx_whisper_decode(self._h, state.data_ptr(), B, arr(prefix), len(prefix), arr(suppress), len(suppress),
-                                                  arr(begin_suppress), len(begin_suppress), eos, int(max_new), ids.data_ptr(), scores.data_ptr(),
-                                                  counts.data_ptr(), ws.data_ptr(), ws.numel(), st))
+        self._call(self._l.tdx_whisper_decode, B, state.data_ptr(), B, _int_array(prefix), len(prefix), _int_array(suppress), len(suppress),
+                   _int_array(begin_suppress), len(begin_suppress), eos, int(max_new), ids.data_ptr(), scores.data_ptr(), counts.data_ptr())
         return ids, scores, counts
 
     def decode_xattn(self, state: torch.Tensor, prefix, max_new: int, suppress=(), begin_suppress=(), eos=None, first_row=None, max_rows=None,
@@ -436,33 +444,23 @@ class WhisperASR:
         max_rows = max(1, max_new - 1).  Rows no step reached keep what `xattn` held (zeros when it is allocated here)."""
         self._check_open()
         c = self.cfg
-        B = int(state.shape[2])
-        self._check_batch(B)
-        if tuple(state.shape) != (c["dec_layers"], 2, B, c["n_audio_ctx"], c["d_model"]) or not state.is_contiguous():
-            raise _lib.TdxError("WhisperASR.decode_xattn: state is not encode(..., with_state=True)'s")
+        B = self._check_state("decode_xattn", state)
         eos = int(self.gen_cfg["eos_token_id"] if eos is None else eos)
         prefix, suppress, begin_suppress = list(prefix), list(suppress), list(begin_suppress)
         heads = [[int(l), int(h)] for l, h in (self.alignment_heads if heads is None else heads)]
         first_row = len(prefix) if first_row is None else int(first_row)
         max_rows = max(1, int(max_new) - 1) if max_rows is None else int(max_rows)
         nh = len(heads)
-        if xattn is None and 1 <= nh <= MAX_ALIGN_HEADS and max_rows >= 1:
-            xattn = torch.zeros(B, nh, max_rows, c["n_audio_ctx"], device=self.device)
-        elif xattn is not None and (tuple(xattn.shape) != (B, nh, max_rows, c["n_audio_ctx"]) or xattn.dtype != torch.float32
-                                    or not xattn.is_contiguous() or xattn.device != torch.device(self.device)):
+        if xattn is None:
+            xattn = self._alloc_xattn(B, nh, max_rows)
+        elif (tuple(xattn.shape) != (B, nh, max_rows, c["n_audio_ctx"]) or xattn.dtype != torch.float32 or not xattn.is_contiguous()
+              or xattn.device != torch.device(self.device)):
             raise _lib.TdxError(f"WhisperASR.decode_xattn: xattn must be contiguous float32 [{B}, {nh}, {max_rows}, {c['n_audio_ctx']}] on {self.device}")
-        ids = torch.full((B, c["n_text_ctx"]), -1, dtype=torch.int32, device=self.device)
-        scores = torch.zeros(B, c["n_text_ctx"], device=self.device)
-        counts = torch.zeros(B, dtype=torch.int32, device=self.device)
-        arr = lambda v: (C.c_int * max(1, len(v)))(*[int(t) for t in v])
+        ids, scores, counts = self._decode_buffers(B)
         flat = [t for pair in heads for t in pair]
-        with self._guard.call():
-            ws = self._guard.workspace(self.workspace_bytes(B))
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._l.tdx_whisper_decode_xattn(self._h, state.data_ptr(), B, arr(prefix), len(prefix), arr(suppress), len(suppress),
-                                                        arr(begin_suppress), len(begin_suppress), eos, int(max_new), arr(flat), nh, first_row, max_rows,
-                                                        xattn.data_ptr() if xattn is not None else None, ids.data_ptr(), scores.data_ptr(),
-                                                        counts.data_ptr(), ws.data_ptr(), ws.numel(), st))
+        self._call(self._l.tdx_whisper_decode_xattn, B, state.data_ptr(), B, _int_array(prefix), len(prefix), _int_array(suppress), len(suppress),
+                   _int_array(begin_suppress), len(begin_suppress), eos, int(max_new), _int_array(flat), nh, first_row, max_rows,
+                   xattn.data_ptr() if xattn is not None else None, ids.data_ptr(), scores.data_ptr(), counts.data_ptr())
         return ids, scores, counts, xattn
 
     def detect_language(self, state: torch.Tensor) -> list:
@@ -572,11 +570,8 @@ class WhisperASR:
         (default: its prefix length); sot_pos: per row, the position of <|startoftranscript|>; first_row: per row (default: its
         prefix length)."""
         self._check_open()
-        c, g = self.cfg, self.gen_cfg
-        B = int(state.shape[2])
-        self._check_batch(B)
-        if tuple(state.shape) != (c["dec_layers"], 2, B, c["n_audio_ctx"], c["d_model"]) or not state.is_contiguous():
-            raise _lib.TdxError("WhisperASR.decode_ts: state is not encode(..., with_state=True)'s")
+        g = self.gen_cfg
+        B = self._check_state("decode_ts", state)
         prefixes = [[int(t) for t in p] for p in prefixes]
         if len(prefixes) != B:
             raise _lib.TdxError(f"WhisperASR.decode_ts: {B} rows of state, {len(prefixes)} prefixes")
@@ -588,34 +583,26 @@ class WhisperASR:
         mi = -1 if mi is None else int(mi)
         plen = [len(p) for p in prefixes]
         mp = max(1, max(plen))
-        arr = lambda v: (C.c_int * max(1, len(v)))(*[int(t) for t in v])
-        opt = lambda v: arr(per_row(v)) if v is not None else None
+        opt = lambda v: _int_array(per_row(v)) if v is not None else None
         flat_prefix = [t for p in prefixes for t in p + [0] * (mp - len(p))]
         for name, v in (("max_new", max_new), ("begin", begin), ("sot_pos", sot_pos), ("first_row", first_row)):
             if v is not None and not isinstance(v, int) and len(v) != B:
                 raise _lib.TdxError(f"WhisperASR.decode_ts: {name} has {len(v)} entries for {B} rows")
         suppress, begin_suppress = list(suppress), list(begin_suppress)
-        ids = torch.full((B, c["n_text_ctx"]), -1, dtype=torch.int32, device=self.device)
-        scores = torch.zeros(B, c["n_text_ctx"], device=self.device)
-        counts = torch.zeros(B, dtype=torch.int32, device=self.device)
+        ids, scores, counts = self._decode_buffers(B)
         nospeech = torch.zeros(B, device=self.device) if sot_pos is not None else None
         ns_id = int(nots - 1 if no_speech_id is None else no_speech_id)
         xattn, flat, nh = None, None, 0
         if heads is not None:
             heads = [[int(l), int(h)] for l, h in heads]
             nh = len(heads)
-            flat = arr([t for pair in heads for t in pair])
+            flat = _int_array([t for pair in heads for t in pair])
             max_rows = max(1, max(max_new) - 1) if max_rows is None else int(max_rows)
-            if 1 <= nh <= MAX_ALIGN_HEADS and max_rows >= 1:
-                xattn = torch.zeros(B, nh, max_rows, c["n_audio_ctx"], device=self.device)
-        with self._guard.call():
-            ws = self._guard.workspace(self.workspace_bytes(B))
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._l.tdx_whisper_decode_ts(self._h, state.data_ptr(), B, arr(flat_prefix), mp, arr(plen), opt(begin), arr(suppress), len(suppress),
-                                                     arr(begin_suppress), len(begin_suppress), eos, nots, mi, arr(max_new), ns_id, opt(sot_pos),
-                                                     nospeech.data_ptr() if nospeech is not None else None, flat, nh, opt(first_row),
-                                                     int(max_rows or 0), xattn.data_ptr() if xattn is not None else None, ids.data_ptr(),
-                                                     scores.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), st))
+            xattn = self._alloc_xattn(B, nh, max_rows)
+        self._call(self._l.tdx_whisper_decode_ts, B, state.data_ptr(), B, _int_array(flat_prefix), mp, _int_array(plen), opt(begin), _int_array(suppress),
+                   len(suppress), _int_array(begin_suppress), len(begin_suppress), eos, nots, mi, _int_array(max_new), ns_id, opt(sot_pos),
+                   nospeech.data_ptr() if nospeech is not None else None, flat, nh, opt(first_row), int(max_rows or 0),
+                   xattn.data_ptr() if xattn is not None else None, ids.data_ptr(), scores.data_ptr(), counts.data_ptr())
         return ids, scores, counts, nospeech, xattn
 
     def transcribe(self, wavs, language=None, task: str = "transcribe", prompt_ids=None, condition_on_prev_tokens: bool = True,

@@ -304,3 +304,14 @@ def test_old_decode_is_unchanged(gold, nb):
     ids, sc, cnt = lc.old_decode_run(W, nb)
     assert cnt.tolist() == z[f"counts{nb}"].tolist() and int(cnt.min()) >= 1
     assert np.array_equal(ids.numpy(), z[f"ids{nb}"]) and np.array_equal(sc.numpy(), z[f"scores{nb}"])          # bit for bit
+
+
+# ---- 9. tdx_whisper_decode_ts gives what it gave before the three decode entry points shared one loop: every kernel path of the
+# smallest shapes that reach them (the B <= 8 and B > 8 Linear, tb inside the first and the second head slice, a partial last slice,
+# every rule branch, the mass-rule flip, the no-speech pair, the per-clip capture row)
+def test_decode_ts_is_unchanged(gold):
+    z = np.load(os.path.join(gold, "whisper_decode_ts_golden.npz"))
+    got = lc.decode_ts_golden_run(lambda name: model(name)[0])
+    assert sorted(got) == sorted(k for k in z.files if k != "commit") and len(got) == 17 and len(str(z["commit"])) == 40
+    for k, v in got.items():
+        assert v.dtype == z[k].dtype and np.array_equal(v, z[k]), k                                              # bit for bit

@@ -130,6 +130,29 @@ def old_decode_run(W, nb):
     return out
 
 
+GOLDEN_TS_CAPTURE = [[1, 0], [0, 0]]
+
+
+def decode_ts_golden_run(model_of):
+    """tdx_whisper_decode_ts on decode_case S / 3, S / 9, M / 3 (sot_pos given; S / 3 with the capture of GOLDEN_TS_CAPTURE) and on
+    branch_case M with max_initial_timestamp_index 5 -> {key: numpy array}.  model_of(name): the WhisperASR of weights(name, 1, SCALE)
+    under gen_config(name).  tests/golden/whisper_decode_ts_golden.npz holds what the commit before the three decode entry points
+    shared one loop gave (tools/make_goldens_whisper_decode_ts.py)."""
+    out = {}
+    cases = [(f"{n}{B}", n, decode_case(n, B), -1, GOLDEN_TS_CAPTURE if (n, B) == ("S", 3) else None) for n, B in (("S", 3), ("S", 9), ("M", 3))]
+    cases.append(("branchM", "M", branch_case("M"), 5, None))
+    for tag, name, (feats, rows), max_initial, heads in cases:
+        m, g = model_of(name), gen_config(name)
+        _, state = m.encode(feats, with_state=True)
+        ids, sc, cnt, nosp, xattn = m.decode_ts(state, [r["prefix"] for r in rows], [r["max_new"] for r in rows], suppress=g["suppress_tokens"],
+                                                begin_suppress=g["begin_suppress_tokens"], max_initial_timestamp_index=max_initial,
+                                                begin=[r.get("begin", len(r["prefix"])) for r in rows], sot_pos=[r["sot_pos"] for r in rows], heads=heads)
+        out.update({f"ids_{tag}": ids.cpu().numpy(), f"scores_{tag}": sc.cpu().numpy(), f"counts_{tag}": cnt.cpu().numpy(), f"nospeech_{tag}": nosp.cpu().numpy()})
+        if heads is not None:
+            out[f"xattn_{tag}"] = xattn.cpu().numpy()
+    return out
+
+
 def oracle_rows(name, sd64, cfg, enc, rows, max_initial=None, eos=None):
     """the fp64 oracle's greedy_ts for every row, enc [B, S, d] in fp64"""
     import whisper_longform_oracle as lo
