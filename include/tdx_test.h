@@ -2,7 +2,8 @@
  *
  * NOT part of the product boundary (include/tdx.h / libtdx.so).  libtdx_diag.so is a separate library built
  * from csrc/diag.hip over the same kernel headers; tests/test_gpu_h3.py checks the numerics of the split-f16 x3
- * core through it, tests/test_gpu_gemm_f32.py the operand modes and tile maps of the fp32 MFMA core,
+ * core through it, tests/test_gpu_h3_forms.py and tests/test_h3_tile_map.py its operand forms, producers and tile map,
+ * tests/test_gpu_gemm_f32.py the operand modes and tile maps of the fp32 MFMA core,
  * tests/test_gpu_epilogues.py the shared epilogues, tests/test_gpu_attention_gate.py the gated attention launch,
  * and tools/ time its variants.  Same conventions as tdx.h (device pointers, void* stream, 0 = ok). */
 #ifndef TDX_TEST_H
@@ -67,6 +68,63 @@ int tdx_gemm_f32(int a_kmajor, int b_kmajor, int paired, const tdx_gemm_seg* seg
 int tdx_gemm_f32_conv(const float* a_dev, long lda, const float* w_dev, int B, int Hin, int Win, int Hout, int Wout, int stride,
                       int stride_w, int ntaps, int cin, int N, int n_valid, float* out_dev, long ldo, int nreal, int* plan_or_null,
                       void* stream);
+
+/* the split-f16 x3 core (csrc/gemm_h3.hpp gemm_h3_kernel / launch_gemm_h3x) in every operand form the product issues, with a plain
+ * store: tests/test_gpu_h3_forms.py.
+ *   out[z*strideO + m*ldo + n] = sum over segments of sa[m] * sb[n] * sum over k of A'[z][m][k] * B'[z][n][k]      for n < nreal.
+ * One K segment, field for field the H3Seg of gemm_h3.hpp (strides of the planes in BYTES, of the scales in floats): A row-major planes
+ * (pitch lda); B row-major planes [N][..] (a weight) or, with b_kmajor, K-major planes [k][N/32][2][32] (ldb = pitch of a k row).  Batch
+ * z = z1 * zdiv + z2 reads A + z1*strideA + z2*strideA2, sa + z1*strideSA + z2*strideSA2 (B, sb likewise).  kchunk > 0: batch z2 covers
+ * min(K, ktotal - z2*kchunk) k.  segk > 0: one row scale per K segment of segk values, segment j's at sa + j*strideSeg.  a_shift /
+ * a_period / a_zero: the token shift (operand row m - 1; a_zero, >= 4*K zero bytes, for m % a_period == 0). */
+typedef struct tdx_h3_seg {
+    const void* A;
+    const void* B;
+    const float* sa;
+    const float* sb;
+    long lda, ldb;
+    long strideA, strideB, strideA2, strideB2;
+    long strideSA, strideSB, strideSA2, strideSB2;
+    int sa_mul, sb_mul;
+    int K;
+    int zdiv;
+    int kchunk, ktotal;
+    int segk;
+    long strideSeg;
+    int a_shift, a_period;
+    const void* a_zero;
+} tdx_h3_seg;
+/* b_kmajor / paired / twoseg / a_conv pick the template instance <A_TR = false, B_TR, PAIRED, TWOSEG, ., 0, A_CONV>: <F,F,F,F>, <F,T,F,F>,
+ * <F,F,T,F>, <F,F,F,T>, <F,T,T,T> and <F,F,F,F> with A_CONV; anything else is refused (K-major A stays with tdx_h3_gemm_x).  PAIRED: N pair
+ * columns; column c pairs B column c with B column pair_off + c and stores them to out columns c and pair_off + c (c < nreal).  A_CONV
+ * (implicit GEMM over NHWC pixel rows, M = B*Hout*Wout): K = ntaps*cin, tap (dy, dx) reads pixel (b, h*stride + dy, w*stride + dx) or
+ * zero_row (>= 4*cin zero bytes) outside the image; taps_total > 0 splits the taps over `batches` = taps_total / ntaps slabs (the
+ * caller sets strideB = 4*ntaps*cin).  The other forms ignore the A_CONV arguments.  plan_or_null (host, 6 ints) receives what
+ * launch_gemm_h3x planned: map_mode, mp, gw, mc, tiles_m, tiles_n.
+ * Refused (TDX_E_INVALID): a null pointer, M < 1, batches < 1, K % 16, K < 64 in a TWOSEG segment, N % 128 with a K-major B or PAIRED,
+ * lda / ldb / operand strides % 16, a K-major ldb < 4*(pair_off + N), zdiv < 1, sa_mul / sb_mul outside {0, 1}, kchunk anywhere but
+ * <F,T,F,F>, segk anywhere but <F,F,F,F> (where the product sets them), kchunk % 16, ktotal % 16, a z2 of the launch left without a k-tile, segk % 64, K % segk, K / segk > 8,
+ * a_shift / a_period anywhere but the first segment of <F,F,F,T>, a_shift != -1, a_period without a_zero, and for A_CONV: cin < 64,
+ * cin % 16, K != ntaps*cin, no zero_row, taps in all not 1 or 9, batches != taps_total / ntaps, M % (Hout*Wout).  The caller owns the
+ * extents: every row the kernel can address after its clamps (rows < M, B rows < N or < pair_off + N, k rows < ktotal) must exist. */
+int tdx_h3_gemm_ex(int b_kmajor, int paired, int twoseg, int a_conv, const tdx_h3_seg* seg0, const tdx_h3_seg* seg1_or_null, int M, int N,
+                   int pair_off, int batches, int Hin, int Win, int Hout, int Wout, int stride, int ntaps, int cin, int taps_total,
+                   const void* zero_row, float* out_dev, long ldo, long strideO, int nreal, int* plan_or_null, void* stream);
+/* the plan of launch_gemm_h3x (plan_gemm_h3) and its block -> tile map (h3_tile_of_block) on the HOST, no device touched:
+ * tests/test_h3_tile_map.py.  tdx_h3_plan: plan[6] as above and grid[2] = (gridDim.x, gridDim.y) for one launch of M x N (PAIRED: N pair
+ * columns) over ktot = the sum of the segments' K.  tdx_h3_tile_of_block: 1 and (*z, *bm, *bn) if block (bx, by) of that launch
+ * computes a tile, 0 if it returns at once, -1 on a bad argument. */
+int tdx_h3_plan(int M, int N, int ktot, int batches, int paired, int* plan, int* grid);
+int tdx_h3_tile_of_block(const int* plan, int batches, int bx, int by, int* z, int* bm, int* bn);
+/* the split producers no other hook reaches.  static: row-major planes [R][Kp/8][2][8] (Kp = K rounded up to 16, tail zero) with the
+ * caller's scale s.  long: rows of any length (K % 16 == 0; the product uses it beyond 2048), one power-of-two scale per row.
+ * kmajor_ex: tdx_h3_split_kmajor with the exact scale (mx_dev / inv_dev given: the exponent-aligned scale of the float whose bits are
+ * mx_dev[0], its inverse to inv_dev[0]; absmax != 0 first computes mx_dev[0] = max |x| over the source rows, which needs ld == N) and
+ * with group padding (Sp > 0: k rows are [K/Sp][Sp], row (b, t) reads source row b*S + t, zero for t >= S). */
+int tdx_h3_split_rows_static(const float* x_dev, long ld, void* planes_dev, long R, int K, float s, void* stream);
+int tdx_h3_split_rows_long(const float* x_dev, long ld, void* planes_dev, float* scale_dev, long R, int K, void* stream);
+int tdx_h3_split_kmajor_ex(const float* x_dev, long ld, void* planes_dev, long K, int N, float s, int absmax, unsigned* mx_dev,
+                           float* inv_dev, int S, int Sp, void* stream);
 
 /* the gated attention launch of a FLASH layer exactly as tdx_mf2_forward issues it (csrc/mf2_attention.hpp attention_core_h3 with the
  * planes-out gate): o = (att_u*v) * sigmoid(att_v*u) as row-major split-f16 planes oP [B*S][4E bytes] with one scale os and one sum of

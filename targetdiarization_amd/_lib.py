@@ -230,8 +230,23 @@ class GemmSeg(C.Structure):
                 ("K", _i), ("zdiv", _i), ("kchunk", _i), ("ktotal", _i)]
 
 
+class H3Seg(C.Structure):
+    """tdx_h3_seg of include/tdx_test.h: one K segment of a tdx_h3_gemm_ex launch (the H3Seg of csrc/gemm_h3.hpp)."""
+    _fields_ = [("A", _vp), ("B", _vp), ("sa", _vp), ("sb", _vp), ("lda", _l), ("ldb", _l),
+                ("strideA", _l), ("strideB", _l), ("strideA2", _l), ("strideB2", _l),
+                ("strideSA", _l), ("strideSB", _l), ("strideSA2", _l), ("strideSB2", _l),
+                ("sa_mul", _i), ("sb_mul", _i), ("K", _i), ("zdiv", _i), ("kchunk", _i), ("ktotal", _i), ("segk", _i),
+                ("strideSeg", _l), ("a_shift", _i), ("a_period", _i), ("a_zero", _vp)]
+
+
 DIAG_SIGNATURES = {
     "tdx_diag_last_error": (C.c_char_p, []),
+    "tdx_h3_gemm_ex": (_i, [_i] * 4 + [C.POINTER(H3Seg)] * 2 + [_i] * 12 + [_vp, _vp, _l, _l, _i, C.POINTER(_i), _vp]),
+    "tdx_h3_plan": (_i, [_i] * 5 + [C.POINTER(_i)] * 2),
+    "tdx_h3_tile_of_block": (_i, [C.POINTER(_i), _i, _i, _i] + [C.POINTER(_i)] * 3),
+    "tdx_h3_split_rows_static": (_i, [_vp, _l, _vp, _l, _i, C.c_float, _vp]),
+    "tdx_h3_split_rows_long": (_i, [_vp, _l, _vp, _vp, _l, _i, _vp]),
+    "tdx_h3_split_kmajor_ex": (_i, [_vp, _l, _vp, _l, _i, C.c_float, _i, _vp, _vp, _i, _i, _vp]),
     "tdx_h3_split_rows": (_i, [_vp, _l, _vp, _vp, _l, _i, _vp]),
     "tdx_h3_split_kmajor": (_i, [_vp, _l, _vp, _l, _i, C.c_float, _vp]),
     "tdx_h3_gemm_x": (_i, [_i] + [_vp] * 5 + [_i] * 3 + [_vp]),

@@ -1,7 +1,8 @@
 // diag.hip — libtdx_diag.so: test hooks and timing diagnostics of the GEMM cores (declared in include/tdx_test.h).
 // NOT part of the product library: libtdx.so exports only what include/tdx.h declares.  Used by tests/test_gpu_h3.py
-// (numerics of the split-f16 x3 core in all operand modes), tests/test_gpu_gemm_f32.py (the fp32 MFMA core in every operand mode and
-// on both tile maps), tests/test_gpu_epilogues.py (the shared epilogue family), tests/test_gpu_attention_gate.py (the gated attention
+// (numerics of the split-f16 x3 core in all operand modes), tests/test_gpu_h3_forms.py (every operand form and tile map of that core,
+// the split producers), tests/test_h3_tile_map.py (its block -> tile map on the host, no device), tests/test_gpu_gemm_f32.py (the fp32
+// MFMA core in every operand mode and on both tile maps), tests/test_gpu_epilogues.py (the shared epilogue family), tests/test_gpu_attention_gate.py (the gated attention
 // launch exactly as the model issues it), tests/test_dft_basis_host.py (the host-built DFT bases, no device), tests/test_loaders.py
 // (the Loader's pointer binding, no device) and by tools/ (timing variants, operand fill rates).
 #include <hip/hip_runtime.h>
@@ -80,6 +81,61 @@ template <bool A_KMAJOR, bool B_KMAJOR, bool PAIRED, bool CONV, class Epi>
 int run_gemm_f32(const GemmArgs& g, int batches, Epi e, int* plan, hipStream_t st) {
     plan_of<PAIRED, CONV>(g, batches, plan);
     const hipError_t r = launch_gemm<A_KMAJOR, B_KMAJOR, PAIRED, false, Epi, 0, CONV>(g, batches, e, st);
+    return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
+}
+
+// ---- the x3 core's operand-form hook (tdx_h3_gemm_ex)
+H3Seg h3_seg_of(const tdx_h3_seg& s) {
+    H3Seg r{};
+    r.A = (const unsigned char*)s.A; r.B = (const unsigned char*)s.B; r.sa = s.sa; r.sb = s.sb; r.lda = s.lda; r.ldb = s.ldb;
+    r.strideA = s.strideA; r.strideB = s.strideB; r.strideA2 = s.strideA2; r.strideB2 = s.strideB2;
+    r.strideSA = s.strideSA; r.strideSB = s.strideSB; r.strideSA2 = s.strideSA2; r.strideSB2 = s.strideSB2;
+    r.sa_mul = s.sa_mul; r.sb_mul = s.sb_mul; r.K = s.K; r.zdiv = s.zdiv; r.kchunk = s.kchunk; r.ktotal = s.ktotal;
+    r.segk = s.segk; r.strideSeg = s.strideSeg; r.a_shift = s.a_shift; r.a_period = s.a_period; r.a_zero = (const unsigned char*)s.a_zero;
+    return r;
+}
+// form: bit 0 K-major B, bit 1 PAIRED, bit 2 TWOSEG, bit 3 A_CONV.  The optional fields are accepted where the product sets them and nowhere
+// else: kchunk / ktotal on <F,T,F,F>, segk on <F,F,F,F>, a_shift / a_period on the first segment of <F,F,F,T> (the only place where the
+// kernel also shifts the row scale)
+const char* h3_seg_error(const tdx_h3_seg& s, int form, bool first, int batches) {
+    const bool twoseg = form & 4, shift_ok = first && form == 4;
+    if (!s.A || !s.B || !s.sa || !s.sb) return "null operand or scale";
+    if (s.K < 16 || s.K % 16) return "need K >= 16, K % 16 == 0";
+    if (twoseg && s.K < 64) return "TWOSEG needs K >= 64 in both segments";
+    if (s.lda < 64 || s.ldb < 64 || s.lda % 16 || s.ldb % 16) return "need lda, ldb >= 64 bytes and % 16 == 0 (16-byte loads)";
+    for (long v : {s.strideA, s.strideB, s.strideA2, s.strideB2})
+        if (v < 0 || v % 16) return "need operand strides >= 0 and % 16 == 0 (16-byte loads)";
+    for (long v : {s.strideSA, s.strideSB, s.strideSA2, s.strideSB2, s.strideSeg})
+        if (v < 0) return "need scale strides >= 0";
+    if (s.zdiv < 1) return "need zdiv >= 1";
+    if ((s.sa_mul != 0 && s.sa_mul != 1) || (s.sb_mul != 0 && s.sb_mul != 1)) return "need sa_mul, sb_mul in {0, 1}";
+    if (s.kchunk < 0 || s.ktotal < 0) return "need kchunk >= 0, ktotal >= 0";
+    if (s.kchunk) {
+        if (form != 1) return "kchunk: the one segment of <F,T,F,F> only";
+        if (s.kchunk % 16 || s.ktotal % 16) return "need kchunk % 16 == 0, ktotal % 16 == 0";
+        // batch z2 covers min(K, ktotal - z2 * kchunk) k rows: at least one k-tile for the largest z2 of the launch
+        if ((long)s.ktotal - (long)(std::min(s.zdiv, batches) - 1) * s.kchunk < 16) return "kchunk / ktotal leave a z2 of the launch without a k-tile";
+    }
+    if (s.segk) {
+        if (form != 0) return "segk: the one segment of <F,F,F,F> only";
+        if (s.segk < 64 || s.segk % 64 || s.K % s.segk || s.K / s.segk > 8) return "need segk % 64 == 0, K % segk == 0, K / segk <= 8";
+    }
+    if (s.a_shift || s.a_period) {
+        if (!shift_ok) return "a_shift / a_period: the first segment of a row-major TWOSEG launch only";
+        if (s.a_shift != -1 || s.a_period < 1) return "need a_shift == -1 with a_period >= 1 (row -1 would be read otherwise)";
+        if (!s.a_zero) return "a_period without a_zero";
+    }
+    return nullptr;
+}
+void h3_plan_out(const H3Args& g, int* plan) {
+    if (plan) { plan[0] = g.map_mode; plan[1] = g.mp; plan[2] = g.gw; plan[3] = g.mc; plan[4] = g.tiles_m; plan[5] = g.tiles_n; }
+}
+template <bool B_TR, bool PAIRED, bool TWOSEG, bool A_CONV, class Epi>
+int run_gemm_h3(const H3Args& g, int batches, Epi e, int* plan, hipStream_t st) {
+    H3Args p = g;                       // what launch_gemm_h3x is about to compute for g
+    plan_gemm_h3<PAIRED, Epi>(p, batches);
+    h3_plan_out(p, plan);
+    const hipError_t r = launch_gemm_h3x<false, B_TR, PAIRED, TWOSEG, Epi, 0, A_CONV>(g, batches, e, st);
     return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
 }
 }  // namespace
@@ -285,6 +341,122 @@ int tdx_h3_gemm(const void* pa, const float* sa, const void* pb, const float* sb
     g.seg[0] = tdx::h3_seg(pa, sa, 4L * K, pb, sb, 4L * K, K);
     g.nseg = 1; g.M = M; g.N = N;
     hipError_t r = tdx::launch_gemm_h3<false>(g, 1, EpiBiasAct<>{bias, c, N}, (hipStream_t)stream);
+    return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
+}
+
+// ---- the x3 core in every operand form the product issues, with a plain store: tests/test_gpu_h3_forms.py -----------------------------
+// tdx_h3_gemm_ex builds an H3Args from its arguments and calls launch_gemm_h3x itself (EpiPlainN / EpiPlainPair above).  It refuses
+// whatever the kernel cannot run safely; the buffers' extents are the caller's business (see include/tdx_test.h).
+int tdx_h3_gemm_ex(int b_kmajor, int paired, int twoseg, int a_conv, const tdx_h3_seg* seg0, const tdx_h3_seg* seg1_or_null, int M, int N,
+                   int pair_off, int batches, int Hin, int Win, int Hout, int Wout, int stride, int ntaps, int cin, int taps_total,
+                   const void* zero_row, float* out, long ldo, long strideO, int nreal, int* plan_or_null, void* stream) {
+    const auto bad = [](const char* m) { return tdx::fail(TDX_E_INVALID, std::string("tdx_h3_gemm_ex: ") + m); };
+    if (!seg0 || !out) return bad("null argument");
+    const int form = (b_kmajor ? 1 : 0) | (paired ? 2 : 0) | (twoseg ? 4 : 0) | (a_conv ? 8 : 0);
+    if (form != 0 && form != 1 && form != 2 && form != 4 && form != 7 && form != 8)
+        return bad("no product instance: <F,F,F,F>, <F,T,F,F>, <F,F,T,F>, <F,F,F,T>, <F,T,T,T> and A_CONV on <F,F,F,F> only");
+    if ((twoseg != 0) != (seg1_or_null != nullptr)) return bad("TWOSEG needs seg1, one segment needs seg1 == NULL");
+    if (M < 1 || batches < 1) return bad("need M >= 1, batches >= 1");
+    if (N < 1 || ((b_kmajor || paired) && N % 128)) return bad("need N >= 1; N % 128 == 0 with a K-major B or PAIRED");
+    if (nreal < 1 || nreal > N || pair_off < 0 || (!paired && pair_off)) return bad("need 1 <= nreal <= N, pair_off >= 0 (PAIRED only)");
+    if (paired && b_kmajor && pair_off % 128) return bad("need pair_off % 128 == 0 with a K-major B");
+    if (ldo < 1 || strideO < 0) return bad("need ldo >= 1, strideO >= 0");
+    if (const char* m = h3_seg_error(*seg0, form, true, batches)) return bad(m);
+    if (seg1_or_null)
+        if (const char* m = h3_seg_error(*seg1_or_null, form, false, batches)) return bad(m);
+    if (b_kmajor)
+        for (const tdx_h3_seg* s : {seg0, seg1_or_null})
+            if (s && s->ldb < 4L * (pair_off + N)) return bad("need ldb >= 4 * (pair_off + N) bytes with a K-major B");
+    H3Args g{};
+    g.seg[0] = h3_seg_of(*seg0);
+    if (seg1_or_null) g.seg[1] = h3_seg_of(*seg1_or_null);
+    g.nseg = seg1_or_null ? 2 : 1; g.M = M; g.N = N; g.pair_off = pair_off;
+    if (a_conv) {
+        const int nt = taps_total ? taps_total : ntaps;
+        if (!zero_row) return bad("A_CONV without zero_row");
+        if (nt != 1 && nt != 9) return bad("need 1 or 9 taps in all");
+        if (ntaps < 1 || taps_total < 0 || (taps_total && taps_total % ntaps)) return bad("need ntaps >= 1, taps_total % ntaps == 0");
+        if (batches != (taps_total ? taps_total / ntaps : 1)) return bad("need batches == taps_total / ntaps (1 without taps_total)");
+        if (cin < 64 || cin % 16) return bad("need cin >= 64, cin % 16 == 0");
+        if (seg0->K != ntaps * cin) return bad("need K == ntaps * cin");
+        if (seg0->lda < 4L * cin) return bad("need lda >= 4 * cin bytes");
+        if (Hin < 1 || Win < 1 || Hout < 1 || Wout < 1 || stride < 1) return bad("need positive extents, stride >= 1");
+        if ((long)Hout * Wout > 0x7fffffffL || M % (Hout * Wout)) return bad("need M == B * Hout * Wout");
+        if ((long)(M / (Hout * Wout)) * Hin * Win > 0x7fffffffL) return bad("rows beyond int");
+        g.cv_Hin = Hin; g.cv_Win = Win; g.cv_Hout = Hout; g.cv_Wout = Wout; g.cv_stride = stride; g.cv_ntaps = ntaps; g.cv_cin = cin;
+        g.cv_taps_total = taps_total; g.zero_row = (const unsigned char*)zero_row;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (paired) {
+        const EpiPlainPair e{out, ldo, strideO, nreal, pair_off};
+        return b_kmajor ? run_gemm_h3<true, true, true, false>(g, batches, e, plan_or_null, st)
+                        : run_gemm_h3<false, true, false, false>(g, batches, e, plan_or_null, st);
+    }
+    const EpiPlainN e{out, ldo, strideO, nreal};
+    if (a_conv) return run_gemm_h3<false, false, false, true>(g, batches, e, plan_or_null, st);
+    if (twoseg) return run_gemm_h3<false, false, true, false>(g, batches, e, plan_or_null, st);
+    if (b_kmajor) return run_gemm_h3<true, false, false, false>(g, batches, e, plan_or_null, st);
+    return run_gemm_h3<false, false, false, false>(g, batches, e, plan_or_null, st);
+}
+
+// the plan and the block -> tile map of the x3 core on the host (gemm_h3.hpp plan_gemm_h3 / h3_tile_of_block): tests/test_h3_tile_map.py.
+// No device call.
+int tdx_h3_plan(int M, int N, int ktot, int batches, int paired, int* plan, int* grid) {
+    if (!plan || !grid || M < 1 || N < 1 || ktot < 16 || batches < 1 || (paired && N % 128)) return tdx::fail(TDX_E_INVALID, "tdx_h3_plan: bad argument");
+    H3Args g{};
+    g.nseg = 1; g.seg[0].K = ktot; g.M = M; g.N = N;
+    const dim3 gr = paired ? plan_gemm_h3<true, EpiPlainPair>(g, batches) : plan_gemm_h3<false, EpiPlainN>(g, batches);
+    h3_plan_out(g, plan);
+    grid[0] = (int)gr.x; grid[1] = (int)gr.y;
+    return TDX_OK;
+}
+// returns 1 if block (bx, by) computes tile (*bm, *bn) of batch *z, 0 if it returns at once, < 0 on a bad argument
+int tdx_h3_tile_of_block(const int* plan, int batches, int bx, int by, int* z, int* bm, int* bn) {
+    if (!plan || !z || !bm || !bn || bx < 0 || by < 0 || batches < 1 || plan[2] < 1 || plan[4] < 1 || plan[5] < 1 || plan[3] < 0 ||
+        (plan[0] == 0 && plan[1] < 1)) {
+        tdx::fail(TDX_E_INVALID, "tdx_h3_tile_of_block: bad argument");
+        return -1;
+    }
+    H3Args g{};
+    g.map_mode = plan[0]; g.mp = plan[1]; g.gw = plan[2]; g.mc = plan[3]; g.tiles_m = plan[4]; g.tiles_n = plan[5]; g.batches = batches;
+    *z = *bm = *bn = -1;
+    return h3_tile_of_block(g, (unsigned)bx, (unsigned)by, *z, *bm, *bn) ? 1 : 0;
+}
+
+// the split producers that no other hook reaches
+int tdx_h3_split_rows_static(const float* x, long ld, void* planes, long R, int K, float s, void* stream) {
+    if (!x || !planes || R < 1 || K < 8 || K % 8 || ld < K || ld % 4 || !(s > 0.f) || !(s < 3e38f))
+        return tdx::fail(TDX_E_INVALID, "tdx_h3_split_rows_static: need R >= 1, K % 8 == 0, ld >= K, ld % 4 == 0, 0 < s < inf");
+    hipError_t r = tdx::launch_h3_split_rows_static(x, ld, planes, R, K, s, (hipStream_t)stream);
+    return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
+}
+int tdx_h3_split_rows_long(const float* x, long ld, void* planes, float* scale, long R, int K, void* stream) {
+    if (!x || !planes || !scale || R < 1 || K < 16 || K % 16 || ld < K || ld % 4)
+        return tdx::fail(TDX_E_INVALID, "tdx_h3_split_rows_long: need R >= 1, K % 16 == 0, ld >= K, ld % 4 == 0");
+    hipError_t r = tdx::launch_h3_split_rows_long(x, ld, planes, scale, R, K, (hipStream_t)stream);
+    return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
+}
+int tdx_h3_split_kmajor_ex(const float* x, long ld, void* planes, long K, int N, float s, int absmax, unsigned* mx, float* inv, int S, int Sp,
+                           void* stream) {
+    const auto bad = [](const char* m) { return tdx::fail(TDX_E_INVALID, std::string("tdx_h3_split_kmajor_ex: ") + m); };
+    if (!x || !planes || K < 1 || N < 128 || N % 128 || ld < N || ld % 4) return bad("need K >= 1, N % 128 == 0, ld >= N, ld % 4 == 0");
+    if ((mx != nullptr) != (inv != nullptr)) return bad("mx and inv come together");
+    if (!mx && (!(s > 0.f) || !(s < 3e38f))) return bad("need 0 < s < inf without mx");
+    if (absmax && (!mx || ld != N)) return bad("absmax needs mx and a dense source (ld == N)");
+    if (Sp < 0 || (Sp > 0 && (S < 1 || S > Sp || K % Sp))) return bad("need 1 <= S <= Sp, K % Sp == 0 with group padding");
+    if (Sp == 0 && S != 0) return bad("S without Sp");
+    hipStream_t st = (hipStream_t)stream;
+    if (absmax) {       // as attn_make_planes (mf2_attention.hpp) does: max |x| over the source rows into mx[0], zeroed first
+        const long rows = Sp > 0 ? (K / Sp) * S : K;
+        if (hipMemsetAsync(mx, 0, sizeof(unsigned), st) != hipSuccess) return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
+        hipLaunchKernelGGL(tdx::h3_absmax_kernel<0>, dim3(1024), dim3(256), 0, st, x, rows * ld, mx);
+        const hipError_t ra = hipGetLastError();
+        if (ra != hipSuccess) return tdx::fail_hip(ra, __FILE__, __LINE__);
+    }
+    const long n = K * (N / 8);
+    hipLaunchKernelGGL(tdx::h3_split_kmajor_kernel<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, ld, (unsigned char*)planes, K, N,
+                       mx ? 1.0f : s, (const unsigned*)mx, inv, S, Sp);
+    hipError_t r = hipGetLastError();
     return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
 }
 

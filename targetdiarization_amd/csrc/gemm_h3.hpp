@@ -51,6 +51,7 @@
 // In both cases the swizzle is applied on the per-lane SOURCE address of the DMA (its LDS
 // destination is lane-linear) and on the fragment read.
 #pragma once
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <typeinfo>
@@ -426,6 +427,39 @@ constexpr int H3_CONV_STEP = 240, H3_CONV_HALO = 8;
 template <class T> __device__ __forceinline__ void h3_assume_row(const T&) {}
 __device__ __forceinline__ void h3_assume_row(long rw) { __builtin_assume(rw >= 0); }
 
+// block -> tile map of a launch planned by plan_gemm_h3: block (BX, BY) computes tile (bm, bn) of batch z, or nothing (FAIL runs).
+// BX & 7 is the XCD the block lands on.  One text for the kernel and for the host copy h3_tile_of_block below, which
+// tests/test_h3_tile_map.py enumerates (a shared function changed the kernels' register allocation: profiles/h3_tile_map_isa.txt).
+#define H3_TILE_OF_BLOCK(g, BX, BY, z, bm, bn, FAIL)                                                                    \
+    {                                                                                                                  \
+        const int x = (BX) & 7, i = (BX) >> 3;                                                                         \
+        if (g.map_mode == 0) {                                                                                         \
+            z = (BY);                                                                                                  \
+            /* the XCD's M range in chunks of g.mc M tiles (0: one chunk): all N groups sweep a chunk before the next chunk starts, so */ \
+            /* that the A rows a later group re-reads are still in the Infinity Cache (one sweep of the whole range evicts them)       */ \
+            int i2 = i, mbase = 0, mcur = g.mp;                                                                        \
+            if (g.mc > 0) { const int tpc = g.mc * g.tiles_n, c = i / tpc; i2 = i - c * tpc; mbase = c * g.mc; mcur = min(g.mc, g.mp - mbase); } \
+            const int per = mcur * g.gw, ngf = g.tiles_n / g.gw;                                                       \
+            const int p = i2 / per;                                                                                    \
+            int lm, n;                                                                                                 \
+            if (p < ngf) { const int j = i2 - p * per; lm = j / g.gw; n = p * g.gw + (j - lm * g.gw); }                \
+            else { const int rem = g.tiles_n - ngf * g.gw; const int j = i2 - ngf * per; lm = j / rem; n = ngf * g.gw + (j - lm * rem); } \
+            bm = x * g.mp + mbase + lm; bn = n;                                                                        \
+            if (bm >= g.tiles_m) FAIL;                                                                                 \
+        } else {                                                                                                       \
+            const int tpb = g.tiles_m * g.tiles_n;                                                                     \
+            const int zb = i / tpb, tt = i - zb * tpb;                                                                 \
+            z = zb * 8 + x;                                                                                            \
+            if (z >= g.batches) FAIL;                                                                                  \
+            bm = tt / g.tiles_n; bn = tt - bm * g.tiles_n;                                                             \
+        }                                                                                                              \
+    }
+inline bool h3_tile_of_block(const H3Args& g, unsigned bx, unsigned by, int& z, int& bm, int& bn) {
+    using std::min;
+    H3_TILE_OF_BLOCK(g, bx, by, z, bm, bn, return false)
+    return true;
+}
+
 template <bool A_TR, bool B_TR, bool PAIRED, bool TWOSEG, class Epi, int VARIANT = 0, bool A_CONV = false>
 __global__ __launch_bounds__(H3_THREADS, 2) void gemm_h3_kernel(H3Args g, Epi epi) {
     static_assert(!A_CONV || (!A_TR && !TWOSEG), "A_CONV: row-major A planes, one weight segment");
@@ -437,29 +471,10 @@ __global__ __launch_bounds__(H3_THREADS, 2) void gemm_h3_kernel(H3Args g, Epi ep
     const int wm = wave >> 2, wn = wave & 3;
 
     int z, bm, bn;
-    {
-        const int x = blockIdx.x & 7, i = blockIdx.x >> 3;
-        if (g.map_mode == 0) {
-            z = blockIdx.y;
-            // the XCD's M range in chunks of g.mc M tiles (0: one chunk): all N groups sweep a chunk before the next chunk starts, so
-            // that the A rows a later group re-reads are still in the Infinity Cache (one sweep of the whole range evicts them)
-            int i2 = i, mbase = 0, mcur = g.mp;
-            if (g.mc > 0) { const int tpc = g.mc * g.tiles_n, c = i / tpc; i2 = i - c * tpc; mbase = c * g.mc; mcur = min(g.mc, g.mp - mbase); }
-            const int per = mcur * g.gw, ngf = g.tiles_n / g.gw;
-            const int p = i2 / per;
-            int lm, n;
-            if (p < ngf) { const int j = i2 - p * per; lm = j / g.gw; n = p * g.gw + (j - lm * g.gw); }
-            else { const int rem = g.tiles_n - ngf * g.gw; const int j = i2 - ngf * per; lm = j / rem; n = ngf * g.gw + (j - lm * rem); }
-            bm = x * g.mp + mbase + lm; bn = n;
-            if (bm >= g.tiles_m) return;
-        } else {
-            const int tpb = g.tiles_m * g.tiles_n;
-            const int zb = i / tpb, tt = i - zb * tpb;
-            z = zb * 8 + x;
-            if (z >= g.batches) return;
-            bm = tt / g.tiles_n; bn = tt - bm * g.tiles_n;
-        }
-    }
+    // (the macro's text is the map this kernel has always had, token for token — its own block scope, the device `min` — and the host
+    //  copy above expands the same text: change the map there, in one place, and re-check profiles/h3_tile_map_isa.txt)
+    H3_TILE_OF_BLOCK(g, blockIdx.x, blockIdx.y, z, bm, bn, return)
+#undef H3_TILE_OF_BLOCK
     constexpr bool CONV = epi_has_conv<Epi>::value;
     static_assert(!CONV || (!PAIRED && !A_TR && !B_TR && !A_CONV && epi_has_ptr<Epi>::value && epi_has_rowmul<Epi>::value), "CONV: row-major Linear with a put_scaled() functor");
     const int m0 = CONV ? bm * H3_CONV_STEP - H3_CONV_HALO : bm * H3_BM;      // (CONV: overlapping tiles, m0 = -8 for the first)
@@ -1324,17 +1339,16 @@ __global__ __launch_bounds__(H3_THREADS, 2) void gemm_h3_kernel(H3Args g, Epi ep
     H3_STAMP(4);
 }
 
-template <bool A_TR, bool B_TR, bool PAIRED, bool TWOSEG, class Epi, int VARIANT = 0, bool A_CONV = false>
-inline hipError_t launch_gemm_h3x(H3Args g, int batches, Epi epi, hipStream_t st) {
-    // (function-local static: set once, thread-safe — forwards may be issued from several host threads)
-    static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_h3_kernel<A_TR, B_TR, PAIRED, TWOSEG, Epi, VARIANT, A_CONV>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            H3_LDS + H3_LDS_EXTRA);
-    (void)attr_rc;
+// the plan knobs of the environment, read once per process
+inline long h3_env_gw_kb() { static const long v = [] { const char* e = getenv("TDX_H3_GW_KB"); return e ? atol(e) : 1536L; }(); return v; }
+inline int h3_env_mc() { static const int v = [] { const char* e = getenv("TDX_H3_MC"); return e ? atoi(e) : -1; }(); return v; }
+
+// the tiling and the block -> tile map of a launch (h3_tile_of_block reads them back): fills g.tiles_m / tiles_n / batches / map_mode /
+// mp / gw / mc and returns the grid.  Host only; launch_gemm_h3x and the test hook tdx_h3_gemm_ex (diag.hip) both call it.
+template <bool PAIRED, class Epi>
+inline dim3 plan_gemm_h3(H3Args& g, int batches) {
     g.tiles_m = (g.M + H3_BM - 1) / H3_BM;
-    if constexpr (epi_has_conv<Epi>::value) {        // overlapping M tiles: 240 output rows each (see H3Conv)
-        g.tiles_m = (g.M + H3_CONV_STEP - 1) / H3_CONV_STEP;
-        if (batches != 1 || g.seg[0].segk || g.seg[0].kchunk) return hipErrorInvalidValue;
-    }
+    if constexpr (epi_has_conv<Epi>::value) g.tiles_m = (g.M + H3_CONV_STEP - 1) / H3_CONV_STEP;      // overlapping M tiles: 240 output rows each (see H3Conv)
     g.tiles_n = PAIRED ? g.N / (H3_BN / 2) : (g.N + H3_BN - 1) / H3_BN;
     g.batches = batches;
     dim3 grid;
@@ -1343,13 +1357,13 @@ inline hipError_t launch_gemm_h3x(H3Args g, int batches, Epi epi, hipStream_t st
         g.mp = (g.tiles_m + 7) / 8;
         long ktot = 0;
         for (int i = 0; i < g.nseg; ++i) ktot += g.seg[i].K;
-        static const long gw_kb = [] { const char* e = getenv("TDX_H3_GW_KB"); return e ? atol(e) : 1536L; }();
+        const long gw_kb = h3_env_gw_kb();
         long gw = (gw_kb * 1024) / (256L * ktot * 4);      // weight slice of a group stays in the XCD's L2
         if (gw < 1) gw = 1;
         if (gw > g.tiles_n) gw = g.tiles_n;
         g.gw = (int)gw;
         // several N groups re-read the A rows: keep a chunk's rows (per XCD <= ~6 MB, 48 MB on the chip) inside the 256 MB Infinity Cache
-        static const int mc_env = [] { const char* e = getenv("TDX_H3_MC"); return e ? atoi(e) : -1; }();
+        const int mc_env = h3_env_mc();
         g.mc = 0;
         if (g.gw < g.tiles_n) {
             long mc = mc_env >= 0 ? mc_env : (6L * 1024 * 1024) / (256L * ktot * 4);
@@ -1361,6 +1375,17 @@ inline hipError_t launch_gemm_h3x(H3Args g, int batches, Epi epi, hipStream_t st
         g.mp = 0; g.gw = 1;
         grid = dim3(8 * ((batches + 7) / 8) * g.tiles_m * g.tiles_n, 1, 1);
     }
+    return grid;
+}
+
+template <bool A_TR, bool B_TR, bool PAIRED, bool TWOSEG, class Epi, int VARIANT = 0, bool A_CONV = false>
+inline hipError_t launch_gemm_h3x(H3Args g, int batches, Epi epi, hipStream_t st) {
+    // (function-local static: set once, thread-safe — forwards may be issued from several host threads)
+    static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_h3_kernel<A_TR, B_TR, PAIRED, TWOSEG, Epi, VARIANT, A_CONV>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            H3_LDS + H3_LDS_EXTRA);
+    (void)attr_rc;
+    if (epi_has_conv<Epi>::value && (batches != 1 || g.seg[0].segk || g.seg[0].kchunk)) return hipErrorInvalidValue;
+    const dim3 grid = plan_gemm_h3<PAIRED, Epi>(g, batches);
     if (TWOSEG && (g.seg[0].K < 64 || g.seg[1].K < 64 || g.seg[0].kchunk || g.seg[1].kchunk)) return hipErrorInvalidValue;
     for (int i = 0; i < g.nseg; ++i) {
         const H3Seg& sg = g.seg[i];
