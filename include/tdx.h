@@ -497,13 +497,15 @@ int tdx_ctc_collapse(const int* frame_ids_dev, int B, int S, int blank, int* tok
  * N10  Whisper — replaces `AutoModelForSpeechSeq2Seq.from_pretrained(dir)` + `generate(input_features, task="transcribe",
  *      language="chinese", num_beams=1, prompt_ids=...)` (ASRProcessor.py:244-251, 489-514; Hugging Face transformers'
  *      WhisperForConditionalGeneration, pinned by tests/test_whisper_host.py).  fp32 throughout (the reference runs .half()),
- *      greedy decoding only, one prefix per call or, in tdx_whisper_decode_ts, one per row.
+ *      greedy decoding, one prefix per call or, in tdx_whisper_decode_ts, one per row; sampled decoding
+ *      in tdx_whisper_decode_ts_sample.  No beam search.
  *      create enforces, each with its own message: d_model / heads == 64 (encoder and decoder), gelu != 0 (activation_function
  *      "gelu", the exact erf form), n_mels 80 or 128, 1 <= n_audio_ctx, n_text_ctx <= 32768, vocab >= 2, layers >= 1, the FFN
  *      widths positive multiples of 64.
  *      blob: TDXW container with transformers' names (model.encoder.*, model.decoder.*; proj_out.weight optional and then equal
  *      to model.decoder.embed_tokens.weight); strict both ways, by shape, before any device work.
- *      1 <= B <= 32 in every call (workspace_bytes returns 0 outside); one workspace size serves the three entry points.
+ *      1 <= B <= 32 in every call (workspace_bytes returns 0 outside); one workspace size serves the three entry points
+ *      (tdx_whisper_decode_ts_sample asks for tdx_whisper_decode_sample_workspace_bytes).
  *
  *      tdx_whisper_logmel: WhisperFeatureExtractor.  wav_dev [B,N] 16 kHz in [-1,1]; lens_dev NULL or int32 [B] on the DEVICE,
  *      the valid samples of each row (clamped to [0,N]).  Each clip is cut or zero-padded to 320 * n_audio_ctx samples, reflect-
@@ -562,6 +564,18 @@ int tdx_ctc_collapse(const int* frame_ids_dev, int B, int S, int blank, int* tok
  *      eos >= tb, sot_pos outside the prefix, begin outside [1, prefix_len], a negative max_new or first_row, and
  *      tdx_whisper_decode_xattn's capture checks.  tdx_whisper_decode and tdx_whisper_decode_xattn are unchanged: the three share
  *      the decoder-layer launches, and each has its own head and step kernels.
+ *      tdx_whisper_decode_ts_sample: tdx_whisper_decode_ts with a draw from softmax(logits / T) per row (whisper.transcribe's
+ *      temperature fallback).  temperature_host float [B] (0: the row decodes greedily and gives tdx_whisper_decode_ts's
+ *      bits; all 0: the call launches tdx_whisper_decode_ts's kernels), stream_host uint64 [B] (a row's own noise stream), seed.  The draw is the Gumbel-max trick inside the head, so the
+ *      logits are still never stored: id n at context position p gets g = -logf(-logf(u)), u = ((w >> 9) + 0.5) 2^-23, w = word
+ *      n & 3 of Philox4x32-10 under the key (seed & 0xffffffff, seed >> 32) and the counter (n >> 2, p, stream & 0xffffffff,
+ *      stream >> 32); the head keeps, per class, the largest z = v / T + g over the ids the rules admit (ties: the lowest id).
+ *      The mass rule is decided on the untempered logits as in tdx_whisper_decode_ts; if the timestamps win the id is the timestamp
+ *      class's winner, otherwise the larger z of the two classes; the score is the id's untempered log-softmax over the allowed set.
+ *      A row's results depend on (seed, stream, its inputs) alone.  The workspace is tdx_whisper_decode_sample_workspace_bytes(h, B):
+ *      the common workspace (tdx_whisper_workspace_bytes, unchanged) with the rows' records behind it; 0 for a bad argument.
+ *      Rejected, each with its own message: a NULL temperature_host or stream_host, a temperature that is negative, NaN or
+ *      infinite (the row is named), and everything tdx_whisper_decode_ts rejects.
  *
  *      tdx_token_align: token times from those rows, as transformers' _extract_token_timestamps (no model handle; the current
  *      device).  xattn_dev [B][nh][max_rows][n_audio_ctx]; per clip on the DEVICE nrows_dev[b] (0 .. max_rows, clamped) and
@@ -605,6 +619,14 @@ int tdx_whisper_decode_ts(tdx_whisper* h, const float* enc_state_dev, int B, con
                           const int* sot_pos_host, float* nospeech_dev, const int* heads_host, int nh, const int* first_row_host, int max_rows,
                           float* xattn_dev, int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* workspace_dev,
                           size_t workspace_bytes, void* stream);
+size_t tdx_whisper_decode_sample_workspace_bytes(const tdx_whisper* h, int B);
+int tdx_whisper_decode_ts_sample(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int max_prefix,
+                                 const int* prefix_len_host, const int* begin_host, const int* suppress_host, int n_suppress,
+                                 const int* begin_suppress_host, int n_begin, int eos, int no_timestamps_id, int max_initial_timestamp_index,
+                                 const int* max_new_host, int no_speech_id, const int* sot_pos_host, float* nospeech_dev, const int* heads_host,
+                                 int nh, const int* first_row_host, int max_rows, float* xattn_dev, int* step_ids_dev, float* step_scores_dev,
+                                 int* counts_dev, const float* temperature_host, const unsigned long long* stream_host, unsigned long long seed,
+                                 void* workspace_dev, size_t workspace_bytes, void* stream);
 size_t tdx_token_align_workspace_bytes(int B, int nh, int max_rows, int n_audio_ctx);
 int tdx_token_align(const float* xattn_dev, int B, int nh, int max_rows, int n_audio_ctx, const int* nrows_dev, const int* nframes_dev,
                     int median_width, int* frames_dev, float* matrix_dev, void* workspace_dev, size_t workspace_bytes, void* stream);

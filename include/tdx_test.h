@@ -155,6 +155,12 @@ int tdx_diag_dft_synthesis(int N, int nbin, long im_off, long ld, int gain_kind,
 int tdx_diag_loader_bind(const void* blob, size_t blob_bytes, int n, int npad, int L, int C, int k, int N, int K, int Npad, int Kp,
                          float* out_host, size_t out_floats, int* nonnull);
 
+/* the noise of Whisper's sampled decoding (csrc/whisper_noise.hpp) for the ids n0 .. n0 + count - 1 at context position
+ * p of the row stream `row_stream` under `seed`: word_dev [count] the raw Philox4x32-10 words, g_dev [count] the Gumbel values the
+ * vocabulary head adds.  tests/test_gpu_whisper_fallback.py.  Refused: a null pointer, n0 < 0, p < 0, count < 1. */
+int tdx_test_whisper_noise(unsigned long long seed, unsigned long long row_stream, int p, int n0, int count, float* g_dev, unsigned* word_dev,
+                           void* stream);
+
 /* per-CU operand fill rates (tools/fill_bench*.py) */
 int tdx_fill_bench(int mode, const void* src_dev, long bytes_per_block, int blocks, int iters, float* sink_dev, void* stream);
 int tdx_fill_bench2(int mode, const void* src_dev, int stride, int blocks, int iters, float* sink_dev, void* stream);

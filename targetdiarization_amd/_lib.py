@@ -160,6 +160,11 @@ SIGNATURES = {
     "tdx_whisper_decode_ts": (_i, [_vp, _fp, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _i,
                                    C.POINTER(C.c_int), _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _fp, C.POINTER(C.c_int), _i,
                                    C.POINTER(C.c_int), _i, _fp, _vp, _fp, _vp, _vp, _sz, _vp]),
+    "tdx_whisper_decode_sample_workspace_bytes": (_sz, [_vp, _i]),
+    "tdx_whisper_decode_ts_sample": (_i, [_vp, _fp, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _i,
+                                          C.POINTER(C.c_int), _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _fp, C.POINTER(C.c_int), _i,
+                                          C.POINTER(C.c_int), _i, _fp, _vp, _fp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_ulonglong), C.c_ulonglong,
+                                          _vp, _sz, _vp]),
     "tdx_token_align_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "tdx_token_align": (_i, [_fp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _fp, _vp, _sz, _vp]),
     "tdx_ngate_create": (_i, [_i, C.POINTER(_vp)]),
@@ -261,6 +266,7 @@ DIAG_SIGNATURES = {
     "tdx_diag_dft_analysis": (_i, [_i, _i, _l, _l, _l, _i, _vp]),
     "tdx_diag_dft_synthesis": (_i, [_i, _i, _l, _l, _i, _vp]),
     "tdx_diag_loader_bind": (_i, [_vp, _sz] + [_i] * 9 + [_vp, _sz, C.POINTER(_i)]),
+    "tdx_test_whisper_noise": (_i, [C.c_ulonglong, C.c_ulonglong, _i, _i, _i, _vp, _vp, _vp]),
     "tdx_fill_bench": (_i, [_i, _vp, _l, _i, _i, _vp, _vp]),
     "tdx_fill_bench2": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
     "tdx_fill_bench3": (_i, [_vp, _l, _i, _l, _i, _i, _i, _vp, _vp]),

@@ -15,6 +15,7 @@ import numpy as np
 
 class ASRProcessor:
     whisper_long_form = False                        # (an instance made without __init__ keeps the one-window path)
+    whisper_fallback = False                         # (... and greedy decoding)
 
     def __init__(self, is_asr: bool = False, fast_asr: bool = False, asr_model_dir=None, is_vad: bool = False, vad_model_dir: str = "",
                  is_punc: bool = False, punc_model_dir: str = "", is_timestamp: bool = False, timestamp_model_dir: str = "",
@@ -25,9 +26,11 @@ class ASRProcessor:
                  sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None,
                  whisper_state_dict=None, whisper_config=None, whisper_token_list=None, whisper_tokenizer=None, whisper_generation_config=None,
                  whisper_engine: str = "whisper_finetune", whisper_alignment_heads=None,
-                 emotion_state_dict=None, emotion_config=None, emotion_labels=None, whisper_long_form: bool = False):
+                 emotion_state_dict=None, emotion_config=None, emotion_labels=None, whisper_long_form: bool = False,
+                 whisper_fallback: bool = False):
         self.is_asr = is_asr
         self.whisper_long_form = bool(whisper_long_form)  # whisper_v2 / whisper_v3: clips over 30 s go through WhisperASR.transcribe
+        self.whisper_fallback = bool(whisper_fallback)    # ... and transcribe runs whisper.transcribe's temperature fallback (its defaults)
         self.verbose_log = verbose_log
         self.ap = ap
         self.cuda_device = cuda_device
@@ -322,12 +325,12 @@ class ASRProcessor:
             elif prompt:
                 print("Whisper: no tokenizer loaded, the prompt is ignored.")
             auto = language is None or str(language).lower() == "auto"
-            from .whisper import language_code
+            from .whisper import fallback_options, language_code
             full = [np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
             if self.whisper_long_form and any(w.shape[0] > 480000 for w in full):
                 # whisper.transcribe's long-form loop (WhisperASR.transcribe): nothing is cut; the whole text and all words are reported
                 res = m.transcribe(full, language=None if auto else str(language).lower(), task="transcribe", prompt_ids=prompt_ids,
-                                   keys=[str(k) for k in range(len(full))])
+                                   keys=[str(k) for k in range(len(full))], **fallback_options(self.whisper_fallback))
                 if output_raw_result:
                     return res
                 for r in res:

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <initializer_list>
 #include <string>
 
@@ -17,6 +18,7 @@
 #include "epilogues.hpp"
 #include "mf2_attention.hpp"
 #include "weight_pack.hpp"
+#include "whisper_noise.hpp"
 
 using namespace tdx;
 
@@ -612,5 +614,25 @@ extern "C" int tdx_fill_bench(int mode, const void* src, long bytes_per_block, i
     }
     if (mode == 0) hipLaunchKernelGGL(fill_bench_kernel<0>, dim3(blocks), dim3(512), 131072, (hipStream_t)stream, (const unsigned char*)src, bytes_per_block, iters, sink);
     else hipLaunchKernelGGL(fill_bench_kernel<1>, dim3(blocks), dim3(512), 131072, (hipStream_t)stream, (const unsigned char*)src, bytes_per_block, iters, sink);
+    return hipGetLastError() == hipSuccess ? TDX_OK : TDX_E_HIP;
+}
+
+// the noise of Whisper's sampled decoding as the vocabulary head computes it (whisper_noise.hpp): tests/test_gpu_whisper_fallback.py
+namespace {
+__global__ __launch_bounds__(256) void whisper_noise_kernel(unsigned long long seed, unsigned long long row_stream, int p, int n0, int count,
+                                                             float* __restrict__ g, unsigned* __restrict__ word) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int n = n0 + i;
+    const unsigned w = tdx::wh_noise_words(seed, row_stream, p, n >> 2).w[n & 3];
+    word[i] = w;
+    g[i] = tdx::wh_gumbel(w);
+}
+}  // namespace
+extern "C" int tdx_test_whisper_noise(unsigned long long seed, unsigned long long row_stream, int p, int n0, int count, float* g_dev, unsigned* word_dev,
+                                      void* stream) {
+    if (!g_dev || !word_dev || n0 < 0 || p < 0 || count < 1 || n0 > INT_MAX - count)
+        return tdx::fail(TDX_E_INVALID, "tdx_test_whisper_noise: need g_dev, word_dev, n0 >= 0, p >= 0, count >= 1");
+    hipLaunchKernelGGL(whisper_noise_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, seed, row_stream, p, n0, count, g_dev, word_dev);
     return hipGetLastError() == hipSuccess ? TDX_OK : TDX_E_HIP;
 }

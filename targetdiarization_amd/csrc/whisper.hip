@@ -16,8 +16,9 @@
 //             out_proj + residual, the same for the cross attention over the precomputed K / V, fc1 + GELU, fc2 + residual; the
 //             vocabulary head in 64-column slices (max, argmax, sum exp per row and slice, suppression mask applied, logits never
 //             stored; wh_head_kernel<BT, TS>: TS = false keeps one running triple per thread, TS = true the rules' two classes
-//             and the no-speech pair) and one combine launch that writes the per-position outputs, the next token, pos + 1 and
-//             the done flags.  The host enqueues 16 steps at a time and then reads one pinned word (the number of finished clips).
+//             and the no-speech pair; SAMPLE = true, tdx_whisper_decode_ts_sample, also a draw from softmax(logits / T) per row by
+//             the Gumbel-max trick) and one combine launch that writes the per-position outputs, the next token, pos + 1
+//             and the done flags.  The host enqueues 16 steps at a time and then reads one pinned word (the number of finished clips).
 //   times     word timestamps: a capturing call is the same loop plus, per layer with a listed alignment head,
 //             one launch that writes the head's softmax row over the encoder positions; tdx_token_align normalises those rows over
 //             the tokens, median-filters along the frames, averages the heads and runs the dynamic time warping of a clip in one
@@ -34,6 +35,7 @@
 
 #include "dft_basis.hpp"
 #include "epilogues.hpp"
+#include "whisper_noise.hpp"
 
 using namespace tdx;
 
@@ -493,6 +495,16 @@ __device__ __forceinline__ void wh_merge(WhTop& a, const WhTop& b) {
 }
 // what the vocabulary head hands to wh_next_kernel
 struct WhHeadOut { float* pm; int* pi; float* ps; float* nm; float* nsum; float* nlogit; };
+// Sampled decoding (tdx_whisper_decode_ts_sample).  temp [B] (0: the row decodes greedily), stream [B] on the device;
+// zm / zi / zv [cls][B][nsl]: per class, row and slice the record of the perturbed maximum.  The sampling instantiations are launched
+// only when some row has temp > 0: a call whose temperatures are all 0 runs the greedy kernels.
+struct WhSample { const float* temp; const unsigned long long* stream; unsigned long long seed; float* zm; int* zi; float* zv; };
+// (max z, its id, the raw logit of that id) over a set of ids; the empty set is (-inf, INT_MAX, 0).  Ties in z: the lowest id.  Only
+// comparisons: joining records gives the same result in any order.
+struct WhDraw { float z; int i; float v; };
+__device__ __forceinline__ void wh_draw_add(WhDraw& a, const WhDraw& b) {
+    if (b.i != INT_MAX && (a.i == INT_MAX || b.z > a.z || (b.z == a.z && b.i < a.i))) a = b;
+}
 __device__ __forceinline__ void wh_top_add(WhTop& top, float v, int n) {
     if (top.i == INT_MAX) top = WhTop{v, n, 1.f};
     else if (v > top.m) { top.s = top.s * expf(top.m - v) + 1.f; top.m = v; top.i = n; }
@@ -506,15 +518,32 @@ __device__ __forceinline__ void wh_top_add(WhTop& top, float v, int n) {
 // TS = true (tdx_whisper_decode_ts): id n < tb is allowed when n >= text_lo and n != tb - 1 (<|notimestamps|>), id n >= tb when
 // ts_lo <= n <= ts_hi; class 0 over the allowed ids below tb, class 1 over those from tb up (a slice can hold both).  want_ns: a
 // third pair (max, sum exp) over every id of the slice, no mask, and the logit of id ns_id.
-template <int BT, bool TS>
+// SAMPLE (tdx_whisper_decode_ts_sample, with TS): a row with temp[b] > 0 also keeps, per class, the record (max z, its id, that id's
+// raw logit v) of z = v / temp[b] + g over exactly the ids the class's triple admits; g is the noise of whisper_noise.hpp at the
+// position pos[b] + 1 of the id being chosen.  All 256 threads compute the slice's noise into LDS ahead of the column loop (16
+// Philox calls per sampling row), so none of it sits in the serial epilogue of a group of four columns.  Ties in z: the lowest id.
+template <int BT, bool TS, bool SAMPLE>
 __global__ __launch_bounds__(256) void wh_head_kernel(SkArgs a, const unsigned char* __restrict__ mask, const int* __restrict__ bnd, int tb, int want_ns,
-                                                       int ns_id, WhHeadOut o, int nsl) {
+                                                       int ns_id, WhHeadOut o, int nsl, WhSample sp) {
+    static_assert(TS || !SAMPLE, "sampling runs under the timestamp rules");
     constexpr int NC = TS ? 3 : 1;
     __shared__ float stat[2 * WH_MAXB];
     __shared__ float red[4][4 * BT];
     __shared__ float tm[NC][4 * BT], tsum[NC][4 * BT];
     __shared__ int ti[NC][4 * BT];
+    __shared__ float gn[SAMPLE ? BT : 1][WH_SLICE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (SAMPLE) {
+        for (int e = tid; e < BT * (WH_SLICE / 4); e += 256) {
+            const int b = e / (WH_SLICE / 4), q = e % (WH_SLICE / 4);
+            if (b < a.B && sp.temp[b] > 0.f) {
+                const Philox4 r = wh_noise_words(sp.seed, sp.stream[b], a.pos[b] + 1, blockIdx.x * (WH_SLICE / 4) + q);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) gn[b][4 * q + c] = wh_gumbel(r.w[c]);
+            }
+        }
+        __syncthreads();
+    }
     if (a.lng) { sk_stats(a, stat, wave, lane); __syncthreads(); }
     const int rb = min(tid >> 2, a.B - 1);
     const int text_lo = TS ? bnd[rb] : 0, ts_lo = TS ? bnd[WH_MAXB + rb] : 0, ts_hi = TS ? bnd[2 * WH_MAXB + rb] : 0;
@@ -522,6 +551,9 @@ __global__ __launch_bounds__(256) void wh_head_kernel(SkArgs a, const unsigned c
     WhTop top[NC];
 #pragma unroll
     for (int k = 0; k < NC; ++k) top[k] = WhTop{-INFINITY, INT_MAX, 0.f};
+    WhDraw zt[2] = {WhDraw{-INFINITY, INT_MAX, 0.f}, WhDraw{-INFINITY, INT_MAX, 0.f}};
+    float temp = 0.f;
+    if constexpr (SAMPLE) temp = sp.temp[rb];
     for (int g = 0; g < WH_SLICE / 4; ++g) {
         const int n0 = blockIdx.x * WH_SLICE + 4 * g;
         if (n0 >= a.N) break;                                       // (uniform over the workgroup)
@@ -541,7 +573,12 @@ __global__ __launch_bounds__(256) void wh_head_kernel(SkArgs a, const unsigned c
                         if (n == ns_id && (tid >> 2) < a.B) o.nlogit[tid >> 2] = v;
                     }
                     const bool ok = n < tb ? (n >= text_lo && n != tb - 1) : (n >= ts_lo && n <= ts_hi);
-                    if (ok && !(mask[n] & deny)) wh_top_add(top[n < tb ? 0 : 1], v, n);
+                    if (ok && !(mask[n] & deny)) {
+                        wh_top_add(top[n < tb ? 0 : 1], v, n);
+                        if constexpr (SAMPLE) {
+                            if (temp > 0.f) wh_draw_add(zt[n < tb ? 0 : 1], WhDraw{v / temp + gn[rb][4 * g + (tid & 3)], n, v});
+                        }
+                    }
                 } else {
                     if (!(mask[n] & deny)) wh_top_add(top[0], v, n);
                 }
@@ -563,6 +600,21 @@ __global__ __launch_bounds__(256) void wh_head_kernel(SkArgs a, const unsigned c
             } else {
                 const long q = (long)tid * nsl + blockIdx.x;
                 o.nm[q] = t.m; o.nsum[q] = t.s;
+            }
+        }
+    }
+    if constexpr (SAMPLE) {
+        __syncthreads();                                            // tm / ti / tsum have been read: their first two classes carry the records
+        if (tid < 4 * BT)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) { tm[k][tid] = zt[k].z; ti[k][tid] = zt[k].i; tsum[k][tid] = zt[k].v; }
+        __syncthreads();
+        if (tid < BT && tid < a.B) {
+            for (int k = 0; k < 2; ++k) {
+                WhDraw t{-INFINITY, INT_MAX, 0.f};
+                for (int c = 0; c < 4; ++c) wh_draw_add(t, WhDraw{tm[k][4 * tid + c], ti[k][4 * tid + c], tsum[k][4 * tid + c]});
+                const long q = ((long)k * a.B + tid) * nsl + blockIdx.x;
+                sp.zm[q] = t.z; sp.zi[q] = t.i; sp.zv[q] = t.v;
             }
         }
     }
@@ -622,14 +674,44 @@ __device__ __forceinline__ WhTop wh_join_slices(const float* __restrict__ pm, co
     }
     return t;
 }
+// the slices' records of a row's two classes (rows r0, r1 of zm / zi / zv) -> one each; 32 lanes per clip.  A lane has the loads of
+// WH_JOIN slices of both classes in flight at once: one slice per trip made the join a chain of load latencies (26 trips at 811
+// slices, 26 us per step at the large-v3 vocabulary).
+constexpr int WH_JOIN = 8;
+__device__ __forceinline__ void wh_join_draws(const WhSample& sp, long r0, long r1, int nsl, int l, WhDraw& t0, WhDraw& t1) {
+    for (int j0 = l; j0 < nsl; j0 += 32 * WH_JOIN) {
+        WhDraw a[WH_JOIN], b[WH_JOIN];
+#pragma unroll
+        for (int u = 0; u < WH_JOIN; ++u) {
+            const int j = j0 + 32 * u;
+            a[u] = b[u] = WhDraw{-INFINITY, INT_MAX, 0.f};
+            if (j < nsl) {
+                a[u] = WhDraw{sp.zm[r0 * nsl + j], sp.zi[r0 * nsl + j], sp.zv[r0 * nsl + j]};
+                b[u] = WhDraw{sp.zm[r1 * nsl + j], sp.zi[r1 * nsl + j], sp.zv[r1 * nsl + j]};
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < WH_JOIN; ++u) { wh_draw_add(t0, a[u]); wh_draw_add(t1, b[u]); }
+    }
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) {
+        wh_draw_add(t0, WhDraw{__shfl_xor(t0.z, o, 64), __shfl_xor(t0.i, o, 64), __shfl_xor(t0.v, o, 64)});
+        wh_draw_add(t1, WhDraw{__shfl_xor(t1.z, o, 64), __shfl_xor(t1.i, o, 64), __shfl_xor(t1.v, o, 64)});
+    }
+}
 // The step after the head, block = 32 B threads: joins the slices of class 0 and, under the rules, of class 1, and applies the mass
 // rule (every id below tb is denied when the log-sum-exp of the allowed timestamp logits exceeds the largest allowed text logit;
 // with class 1 empty the merge leaves class 0's triple as it is); writes the step's outputs (argmax, its log-softmax), the
 // no-speech probability at the step that fed sot_pos, the next token (of the row's own prefix while it lasts, then the generated
 // one), pos + 1, the history and the allowed intervals of the next step, the done flag and the count of finished clips.  A row
 // is done after eos or after its own last step (pend).
+// SAMPLE: a row with temp[b] > 0 draws its id.  The mass rule is decided on the raw triples as above (upstream applies the rules to the
+// untempered log-softmax before the draw); if the timestamps win, the id is class 1's perturbed winner, otherwise the larger z of
+// the two classes' winners (equal z: the lower id).  The score is the chosen id's untempered log-probability over the allowed
+// set, v - (t.m + logf(t.s)).  A row with temp[b] = 0 takes the greedy branch, bit for bit.
+template <bool SAMPLE>
 __global__ __launch_bounds__(1024) void wh_next_kernel(WhHeadOut o, int nsl, WhState s, int B, int T, WhTsRules r, int* __restrict__ ids,
-                                                        float* __restrict__ score, int* __restrict__ counts, float* __restrict__ nospeech) {
+                                                        float* __restrict__ score, int* __restrict__ counts, float* __restrict__ nospeech, WhSample sp) {
     __shared__ int fin[WH_MAXB];
     const int b = threadIdx.x >> 5, l = threadIdx.x & 31;
     int* ti = s.ti;
@@ -641,14 +723,29 @@ __global__ __launch_bounds__(1024) void wh_next_kernel(WhHeadOut o, int nsl, WhS
     WhTop ts{-INFINITY, INT_MAX, 0.f}, ns{-INFINITY, INT_MAX, 0.f};
     if (r.on) ts = wh_join_slices(o.pm, o.pi, o.ps, (long)B + b, nsl, l);
     if (nospeech) ns = wh_join_slices(o.nm, nullptr, o.nsum, b, nsl, l);
+    WhDraw ztext{-INFINITY, INT_MAX, 0.f}, zts{-INFINITY, INT_MAX, 0.f};
+    float temp = 0.f;
+    if constexpr (SAMPLE) {
+        temp = sp.temp[b];
+        if (temp > 0.f) wh_join_draws(sp, b, (long)B + b, nsl, l, ztext, zts);
+    }
     if (l == 0) {
         if (!d) {
             WhTop t = text;
-            if (ts.i != INT_MAX && (text.i == INT_MAX || ts.m + logf(ts.s) > text.m)) t = ts;
+            const bool ts_wins = ts.i != INT_MAX && (text.i == INT_MAX || ts.m + logf(ts.s) > text.m);
+            if (ts_wins) t = ts;
             else wh_merge(t, ts);
-            const int am = t.i == INT_MAX ? r.eos : t.i;
+            int am = t.i == INT_MAX ? r.eos : t.i;
+            float sc = -logf(t.s);
+            if constexpr (SAMPLE) {
+                if (temp > 0.f) {
+                    WhDraw pick = zts;
+                    if (!ts_wins) wh_draw_add(pick, ztext);
+                    if (pick.i != INT_MAX) { am = pick.i; sc = pick.v - (t.m + logf(t.s)); }
+                }
+            }
             ids[(long)b * T + p] = am;
-            score[(long)b * T + p] = -logf(t.s);
+            score[(long)b * T + p] = sc;
             if (nospeech && p == sot) nospeech[b] = expf(o.nlogit[b] - ns.m) / ns.s;
             int nxt;
             if (p + 1 < plen) nxt = fed;
@@ -972,21 +1069,23 @@ int launch_skinny(SkArgs a, int njobs, float* xn, float* partial, hipStream_t st
     LAUNCH_CHECK();
     return TDX_OK;
 }
-template <int BT, bool TS>
-int launch_head_t(const SkArgs& a, const unsigned char* mask, const int* bnd, int tb, int want_ns, int ns_id, const WhHeadOut& o, int nsl, hipStream_t st) {
-    hipLaunchKernelGGL((wh_head_kernel<BT, TS>), dim3(nsl), dim3(256), 0, st, a, mask, bnd, tb, want_ns, ns_id, o, nsl);
+template <int BT, bool TS, bool SAMPLE>
+int launch_head_t(const SkArgs& a, const unsigned char* mask, const int* bnd, int tb, int want_ns, int ns_id, const WhHeadOut& o, int nsl,
+                  const WhSample& sp, hipStream_t st) {
+    hipLaunchKernelGGL((wh_head_kernel<BT, TS, SAMPLE>), dim3(nsl), dim3(256), 0, st, a, mask, bnd, tb, want_ns, ns_id, o, nsl, sp);
     LAUNCH_CHECK();
     return TDX_OK;
 }
-// TS: the timestamp rules are on (two classes of triples, the no-speech pair when want_ns)
-template <bool TS>
-int launch_head(const SkArgs& a, const unsigned char* mask, const int* bnd, int tb, int want_ns, int ns_id, const WhHeadOut& o, int nsl, hipStream_t st) {
-    if (a.B <= 1) return launch_head_t<1, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
-    if (a.B <= 2) return launch_head_t<2, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
-    if (a.B <= 4) return launch_head_t<4, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
-    if (a.B <= 8) return launch_head_t<8, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
-    if (a.B <= 16) return launch_head_t<16, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
-    return launch_head_t<32, TS>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, st);
+// TS: the timestamp rules are on (two classes of triples, the no-speech pair when want_ns); SAMPLE: the rows' draws as well
+template <bool TS, bool SAMPLE = false>
+int launch_head(const SkArgs& a, const unsigned char* mask, const int* bnd, int tb, int want_ns, int ns_id, const WhHeadOut& o, int nsl, hipStream_t st,
+                const WhSample& sp = WhSample{}) {
+    if (a.B <= 1) return launch_head_t<1, TS, SAMPLE>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, sp, st);
+    if (a.B <= 2) return launch_head_t<2, TS, SAMPLE>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, sp, st);
+    if (a.B <= 4) return launch_head_t<4, TS, SAMPLE>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, sp, st);
+    if (a.B <= 8) return launch_head_t<8, TS, SAMPLE>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, sp, st);
+    if (a.B <= 16) return launch_head_t<16, TS, SAMPLE>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, sp, st);
+    return launch_head_t<32, TS, SAMPLE>(a, mask, bnd, tb, want_ns, ns_id, o, nsl, sp, st);
 }
 SkJob sk_job(const float* W, const float* bias, const float* res, float* y, long ld, int brow = 0, int gelu = 0) {
     return SkJob{W, bias, res, y, ld, brow, gelu};
@@ -1048,6 +1147,17 @@ DecWs dec_ws(const tdx_whisper* h, int B) {
     w.nm = o; o += al((size_t)B * w.nsl); w.nsum = o; o += al((size_t)B * w.nsl); w.nlogit = o; o += al(WH_MAXB);
     w.prefix = o; o += al((size_t)B * T);
     w.cache = o; o += al((size_t)h->c.dec_layers * 2 * B * T * d);
+    w.total = o;
+    return w;
+}
+// what tdx_whisper_decode_ts_sample keeps behind the common workspace (floats from its end): the rows' temperatures and streams and
+// the head's records zm, zi, zv [2][B][nsl]
+struct SampleWs { size_t temp, stream, zm, zi, zv, total; };
+SampleWs sample_ws(const tdx_whisper* h, int B) {
+    const size_t nsl = (h->c.vocab + WH_SLICE - 1) / WH_SLICE;
+    SampleWs w; size_t o = 0;
+    w.temp = o; o += al(WH_MAXB); w.stream = o; o += al(2 * WH_MAXB);
+    w.zm = o; o += al(2 * B * nsl); w.zi = o; o += al(2 * B * nsl); w.zv = o; o += al(2 * B * nsl);
     w.total = o;
     return w;
 }
@@ -1142,6 +1252,11 @@ int tdx_whisper_destroy(tdx_whisper* h) {
 size_t tdx_whisper_workspace_bytes(const tdx_whisper* h, int B) {
     if (!h || B < 1 || B > WH_MAXB) return 0;
     return std::max(std::max(logmel_ws(h, B).total, enc_ws(h, B).total), dec_ws(h, B).total) * sizeof(float);
+}
+
+size_t tdx_whisper_decode_sample_workspace_bytes(const tdx_whisper* h, int B) {
+    if (!h || B < 1 || B > WH_MAXB) return 0;
+    return tdx_whisper_workspace_bytes(h, B) + sample_ws(h, B).total * sizeof(float);
 }
 
 double tdx_whisper_flops(const tdx_whisper* h, int B, int steps) {
@@ -1344,15 +1459,19 @@ struct WhRows {
 
 // The decode loop of the three entry points, which have checked their own arguments and filled `rows`: the static mask, the
 // workspace check, the uploads, the init launch, then 16 steps at a time (decoder layers, head, next) and one pinned read.
-// rules.on selects the head's instantiation; nospeech_dev (rules on only) asks for the no-speech pair.
+// rules.on selects the head's instantiation; nospeech_dev (rules on only) asks for the no-speech pair.  draws (rules on only):
+// tdx_whisper_decode_ts_sample's temperatures, streams and seed; the head and the step then run their sampling instantiations
+// and the workspace carries sample_ws behind the common one.
+struct WhDraws { std::vector<float> temp; std::vector<unsigned long long> stream; unsigned long long seed; };
 static int wh_decode_run(const std::string& fn, tdx_whisper* h, const float* enc_state_dev, int B, const WhRows& rows, const WhTsRules& rules,
                          const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int no_speech_id, float* nospeech_dev,
                          const WhCapture* cap, const std::vector<char>& listed, int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_,
-                         size_t ws_bytes, void* stream) {
+                         size_t ws_bytes, void* stream, const WhDraws* draws = nullptr) {
     const int V = h->c.vocab, T = h->c.n_text_ctx, d = h->c.d_model;
     std::vector<unsigned char> mask;
     TRY(wh_static_mask(fn, V, suppress_host, n_suppress, begin_suppress_host, n_begin, mask));
-    if (ws_bytes < tdx_whisper_workspace_bytes(h, B)) return tdx::fail(TDX_E_WORKSPACE, fn + ": workspace too small");
+    if (ws_bytes < (draws ? tdx_whisper_decode_sample_workspace_bytes(h, B) : tdx_whisper_workspace_bytes(h, B)))
+        return tdx::fail(TDX_E_WORKSPACE, fn + ": workspace too small");
     tdx::DeviceGuard guard(h->device);
     if (guard.err != hipSuccess) return tdx::fail_hip(guard.err, __FILE__, __LINE__);
     hipStream_t st = (hipStream_t)stream;
@@ -1370,6 +1489,16 @@ static int wh_decode_run(const std::string& fn, tdx_whisper* h, const float* enc
     if (rc == hipSuccess) rc = hipMemcpyAsync(ti, rows.st.data(), sizeof(int) * rows.st.size(), hipMemcpyHostToDevice, st);
     if (rc == hipSuccess) rc = hipMemcpyAsync(mask_dev, mask.data(), mask.size(), hipMemcpyHostToDevice, st);
     if (rc == hipSuccess && cap) rc = hipMemcpyAsync(heads_dev, cap->heads_host, sizeof(int) * 2 * cap->nh, hipMemcpyHostToDevice, st);
+    WhSample sp{};
+    bool sampling = false;                                      // no row with temp > 0: the greedy kernels, nothing uploaded
+    for (int b = 0; draws && b < B; ++b) sampling |= draws->temp[b] > 0.f;
+    if (sampling) {
+        const SampleWs sw = sample_ws(h, B);
+        float* g = (float*)((char*)ws_ + tdx_whisper_workspace_bytes(h, B));
+        sp = WhSample{g + sw.temp, (const unsigned long long*)(g + sw.stream), draws->seed, g + sw.zm, (int*)(g + sw.zi), g + sw.zv};
+        if (rc == hipSuccess) rc = hipMemcpyAsync(g + sw.temp, draws->temp.data(), sizeof(float) * B, hipMemcpyHostToDevice, st);
+        if (rc == hipSuccess) rc = hipMemcpyAsync(g + sw.stream, draws->stream.data(), sizeof(unsigned long long) * B, hipMemcpyHostToDevice, st);
+    }
     if (rc != hipSuccess) return tdx::fail_hip(rc, __FILE__, __LINE__);
     hipLaunchKernelGGL(wh_init_kernel, dim3(1), dim3(64), 0, st, s, B, T, rules, counts_dev);
     LAUNCH_CHECK();
@@ -1380,9 +1509,16 @@ static int wh_decode_run(const std::string& fn, tdx_whisper* h, const float* enc
         TRY(wh_decoder_step(ctx));
         SkArgs a = wh_sk_args(s, B, x, h->dln_g, h->dln_b, V, d);
         a.job[0] = sk_job(h->tok, nullptr, nullptr, nullptr, 0);
-        TRY(rules.on ? launch_head<true>(a, mask_dev, bnd, rules.tb, nospeech_dev != nullptr, no_speech_id, ho, w.nsl, st)
-                     : launch_head<false>(a, mask_dev, bnd, 0, 0, 0, ho, w.nsl, st));
-        hipLaunchKernelGGL(wh_next_kernel, dim3(1), dim3(32 * B), 0, st, ho, w.nsl, s, B, T, rules, step_ids_dev, step_scores_dev, counts_dev, nospeech_dev);
+        if (sampling) {
+            TRY((launch_head<true, true>(a, mask_dev, bnd, rules.tb, nospeech_dev != nullptr, no_speech_id, ho, w.nsl, st, sp)));
+            hipLaunchKernelGGL(wh_next_kernel<true>, dim3(1), dim3(32 * B), 0, st, ho, w.nsl, s, B, T, rules, step_ids_dev, step_scores_dev, counts_dev,
+                               nospeech_dev, sp);
+        } else {
+            TRY(rules.on ? launch_head<true>(a, mask_dev, bnd, rules.tb, nospeech_dev != nullptr, no_speech_id, ho, w.nsl, st)
+                         : launch_head<false>(a, mask_dev, bnd, 0, 0, 0, ho, w.nsl, st));
+            hipLaunchKernelGGL(wh_next_kernel<false>, dim3(1), dim3(32 * B), 0, st, ho, w.nsl, s, B, T, rules, step_ids_dev, step_scores_dev, counts_dev,
+                               nospeech_dev, sp);
+        }
         LAUNCH_CHECK();
         return TDX_OK;
     };
@@ -1440,12 +1576,12 @@ int tdx_whisper_decode_xattn(tdx_whisper* h, const float* enc_state_dev, int B, 
                            begin_suppress_host, n_begin, eos, max_new, step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
 }
 
-int tdx_whisper_decode_ts(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int max_prefix, const int* prefix_len_host,
-                          const int* begin_host, const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int eos,
-                          int no_timestamps_id, int max_initial_timestamp_index, const int* max_new_host, int no_speech_id, const int* sot_pos_host,
-                          float* nospeech_dev, const int* heads_host, int nh, const int* first_row_host, int max_rows, float* xattn_dev,
-                          int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_, size_t ws_bytes, void* stream) {
-    const std::string fn = "tdx_whisper_decode_ts";
+// tdx_whisper_decode_ts and, with draws, tdx_whisper_decode_ts_sample
+static int wh_decode_ts(const std::string& fn, const WhDraws* draws, tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int max_prefix,
+                        const int* prefix_len_host, const int* begin_host, const int* suppress_host, int n_suppress, const int* begin_suppress_host,
+                        int n_begin, int eos, int no_timestamps_id, int max_initial_timestamp_index, const int* max_new_host, int no_speech_id,
+                        const int* sot_pos_host, float* nospeech_dev, const int* heads_host, int nh, const int* first_row_host, int max_rows,
+                        float* xattn_dev, int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_, size_t ws_bytes, void* stream) {
     if (!h || !enc_state_dev || !prefix_host || !prefix_len_host || !max_new_host || !step_ids_dev || !step_scores_dev || !counts_dev || !ws_ || B < 1 ||
         B > WH_MAXB || max_prefix < 1 || n_suppress < 0 || n_begin < 0 || (n_suppress > 0 && !suppress_host) || (n_begin > 0 && !begin_suppress_host))
         return tdx::fail(TDX_E_INVALID, fn + ": bad argument (1 <= B <= 32, max_prefix >= 1)");
@@ -1486,7 +1622,36 @@ int tdx_whisper_decode_ts(tdx_whisper* h, const float* enc_state_dev, int B, con
     // (an index past the last timestamp id allows every timestamp: clamped, so that tb + index cannot overflow)
     const WhTsRules rules{1, tb, eos, V, std::min(max_initial_timestamp_index, V - 1 - tb)};
     return wh_decode_run(fn, h, enc_state_dev, B, rows, rules, suppress_host, n_suppress, begin_suppress_host, n_begin, no_speech_id, nospeech_dev, cap, listed,
-                         step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
+                         step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream, draws);
+}
+
+int tdx_whisper_decode_ts(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int max_prefix, const int* prefix_len_host,
+                          const int* begin_host, const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int eos,
+                          int no_timestamps_id, int max_initial_timestamp_index, const int* max_new_host, int no_speech_id, const int* sot_pos_host,
+                          float* nospeech_dev, const int* heads_host, int nh, const int* first_row_host, int max_rows, float* xattn_dev,
+                          int* step_ids_dev, float* step_scores_dev, int* counts_dev, void* ws_, size_t ws_bytes, void* stream) {
+    return wh_decode_ts("tdx_whisper_decode_ts", nullptr, h, enc_state_dev, B, prefix_host, max_prefix, prefix_len_host, begin_host, suppress_host, n_suppress,
+                        begin_suppress_host, n_begin, eos, no_timestamps_id, max_initial_timestamp_index, max_new_host, no_speech_id, sot_pos_host,
+                        nospeech_dev, heads_host, nh, first_row_host, max_rows, xattn_dev, step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
+}
+
+int tdx_whisper_decode_ts_sample(tdx_whisper* h, const float* enc_state_dev, int B, const int* prefix_host, int max_prefix, const int* prefix_len_host,
+                                 const int* begin_host, const int* suppress_host, int n_suppress, const int* begin_suppress_host, int n_begin, int eos,
+                                 int no_timestamps_id, int max_initial_timestamp_index, const int* max_new_host, int no_speech_id,
+                                 const int* sot_pos_host, float* nospeech_dev, const int* heads_host, int nh, const int* first_row_host, int max_rows,
+                                 float* xattn_dev, int* step_ids_dev, float* step_scores_dev, int* counts_dev, const float* temperature_host,
+                                 const unsigned long long* stream_host, unsigned long long seed, void* ws_, size_t ws_bytes, void* stream) {
+    const std::string fn = "tdx_whisper_decode_ts_sample";
+    if (B < 1 || B > WH_MAXB) return tdx::fail(TDX_E_INVALID, fn + ": bad argument (1 <= B <= 32, max_prefix >= 1)");
+    if (!temperature_host) return tdx::fail(TDX_E_INVALID, fn + ": temperature_host must not be NULL");
+    if (!stream_host) return tdx::fail(TDX_E_INVALID, fn + ": stream_host must not be NULL");
+    WhDraws draws{std::vector<float>(temperature_host, temperature_host + B), std::vector<unsigned long long>(stream_host, stream_host + B), seed};
+    for (int b = 0; b < B; ++b)
+        if (!(draws.temp[b] >= 0.f) || std::isinf(draws.temp[b]))
+            return tdx::fail(TDX_E_INVALID, fn + ": temperature of row " + std::to_string(b) + " must be finite and not negative");
+    return wh_decode_ts(fn, &draws, h, enc_state_dev, B, prefix_host, max_prefix, prefix_len_host, begin_host, suppress_host, n_suppress, begin_suppress_host,
+                        n_begin, eos, no_timestamps_id, max_initial_timestamp_index, max_new_host, no_speech_id, sot_pos_host, nospeech_dev, heads_host, nh,
+                        first_row_host, max_rows, xattn_dev, step_ids_dev, step_scores_dev, counts_dev, ws_, ws_bytes, stream);
 }
 
 constexpr int WH_LONG_FBLK = 4096;

@@ -218,23 +218,27 @@ class HotPath:
             res[si].append(r)
         return res
 
-    def recognise_whisper(self, streams, language: str = "chinese", prompt_ids=None, timestamps: bool = False, long_form: bool = False):
+    def recognise_whisper(self, streams, language: str = "chinese", prompt_ids=None, timestamps: bool = False, long_form: bool = False,
+                          fallback: bool = False):
         """H3 with Whisper: the streams cut into the same <= 30 s segments, 32 segments per launch sequence -> per stream the list of
         its segments' {"text", "token_ids", "scores"}.  timestamps (the whisper_v2 / whisper_v3 engines): every segment also carries
         "token_times" and "words" [(word, [start_s, end_s]), ...], both on the stream's own clock (the segment's start added), and
         "offset", that start in seconds.
         long_form: every stream goes whole through WhisperASR.transcribe (windows that follow the timestamp tokens, so no word is
         cut at a fixed 30 s mark) -> per stream one entry per Whisper segment: transcribe's segment dict plus "token_ids", "language"
-        and "offset" = the segment's start; "words" are on the stream's clock already."""
+        and "offset" = the segment's start; "words" are on the stream's clock already.
+        fallback (with long_form): transcribe runs whisper.transcribe's temperature fallback with upstream's defaults (temperatures
+        0.0 .. 1.0, compression_ratio_threshold 2.4); the segments then also carry "temperature" and "compression_ratio"."""
         if self.whisper is None:
             from ._lib import TdxError
             raise TdxError("recognise_whisper needs the Whisper weights (whisper_state_dict / whisper_model_dir)")
         streams = [self._dev(s) for s in streams]
         if long_form:
+            from .whisper import fallback_options
             auto = language is None or str(language).strip().lower() == "auto"
             res = []
-            for r in (self.whisper.transcribe(streams, language=None if auto else language, prompt_ids=prompt_ids, word_timestamps=timestamps)
-                      if streams else []):
+            for r in (self.whisper.transcribe(streams, language=None if auto else language, prompt_ids=prompt_ids, word_timestamps=timestamps,
+                                              **fallback_options(fallback)) if streams else []):
                 res.append([dict(s, token_ids=s["tokens"], language=r["language"], offset=s["start"]) for s in r["segments"]])
             return res
         segs, owner, starts = [], [], []

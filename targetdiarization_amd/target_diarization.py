@@ -50,6 +50,7 @@ def _whole_clip_vad(audio: np.ndarray):
 
 class TargetDiarization:
     whisper_long_form = False                 # (an instance made without __init__ keeps the 30 s cuts)
+    whisper_fallback = False                  # (... and greedy decoding)
 
     def __init__(self, diarization_pipeline_dir: str = "iic/speech_campplus_speaker-diarization_common",
                  od_model_dir: str = "pyannote/speaker-diarization-3.1", mdx_weights_file: str = "mdx/weights/UVR-MDX-NET-Inst_HQ_3.onnx",
@@ -68,9 +69,10 @@ class TargetDiarization:
                  sensevoice_state_dict=None, sensevoice_token_list=None, sensevoice_cmvn=None, sensevoice_model_dir=None,
                  sensevoice_token_file=None, whisper_state_dict=None, whisper_config=None, whisper_model_dir=None, whisper_token_list=None,
                  whisper_tokenizer=None, whisper_generation_config=None, noise_reduce: bool = False, sd_cluster: str = "host",
-                 whisper_long_form: bool = False, **kwargs):
+                 whisper_long_form: bool = False, whisper_fallback: bool = False, **kwargs):
         self.target_similarity_threshold = target_similarity_threshold
         self.whisper_long_form = bool(whisper_long_form)   # whisper_v2 / whisper_v3: H3 through WhisperASR.transcribe (long-form) instead of 30 s cuts
+        self.whisper_fallback = bool(whisper_fallback)     # ... with whisper.transcribe's temperature fallback (its defaults) on that path
         self.noise_reduce = bool(noise_reduce)    # noisereduce's spectral gate on the device as denoise_vocal's body when the MDX denoiser is off
         self.asr_engine = asr_engine
         self.cuda_device = cuda_device
@@ -348,7 +350,8 @@ class TargetDiarization:
         elif str(self.asr_engine).lower() in ("whisper_v2", "whisper_v3") and getattr(self.hp, "whisper", None) is not None:
             # the engines with word timestamps (ASRProcessor.py:443-488): the language is detected per segment (language="auto")
             # whisper_long_form: each timeline goes whole through WhisperASR.transcribe instead of being cut every 30 s
-            whtres = self.hp.recognise_whisper(lines, language="auto", timestamps=True, long_form=self.whisper_long_form) if lines else []
+            whtres = self.hp.recognise_whisper(lines, language="auto", timestamps=True, long_form=self.whisper_long_form,
+                                               fallback=self.whisper_fallback) if lines else []
         elif self.hp.asr is not None and lines:
             if self.decoder is None and self.hp.dec is not None:       # the device CIF + NAR decoder (N2)
                 encs, dres = self.hp.encode_device(lines, decode=True)

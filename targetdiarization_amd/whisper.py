@@ -7,9 +7,11 @@ tests/test_whisper_host.py pins the restatement, the prefix and the language tab
 The device does everything up to the token ids: log-mel features, the encoder, the cross-attention K / V of every decoder layer and
 the greedy decoding loop over a KV cache (one host read per 16 steps).  The host builds the prefix, and turns ids into text through
 the byte-level BPE alphabet when a piece table is given.  Deviations from the reference: fp32 (it runs .half()), one prefix per call,
-greedy decoding only (no beams or temperature fallback), tokenizer files are read when present, never required.  generate() is the
-one-window path; transcribe() is the long-form one: features of the whole clip, 30 s windows decoded with timestamp
-tokens under per-row prefixes (decode_ts), segments cut at the timestamp pairs, the next window from the last timestamp.
+no beam search, tokenizer files are read when present, never required.  generate() is the one-window path; transcribe() is the
+long-form one: features of the whole clip, 30 s windows decoded with timestamp tokens under per-row prefixes
+(decode_ts), segments cut at the timestamp pairs, the next window from the last timestamp.  Decoding is greedy unless temperatures
+are given: decode_ts(temperature=) draws from softmax(logits / T) inside the vocabulary head, and transcribe(temperature=(...))
+restates whisper.transcribe's temperature fallback (decode_with_fallback) over it.
 
 Word timestamps (the reference's whisper_v2 / whisper_v3 engines, ASRProcessor.py:232-243, 443-488): decode_xattn() also
 captures the cross-attention rows of the alignment heads, token_align() turns them into one encoder frame per token on the device
@@ -21,6 +23,7 @@ from __future__ import annotations
 import ctypes as C
 import json
 import os
+import zlib
 
 import numpy as np
 import torch
@@ -32,6 +35,10 @@ MAX_BATCH = 32
 TIME_PRECISION = 0.02                                  # seconds per encoder position
 MEDIAN_WIDTH = 7                                       # WhisperConfig.median_filter_width, openai/whisper timing.py
 MAX_ALIGN_HEADS = 64
+MAX_TEMPERATURES = 16                                  # attempts per window: a row's noise stream is 16 x the clip's index + the attempt
+FALLBACK_TEMPERATURES = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)  # whisper.transcribe's defaults
+FALLBACK_COMPRESSION_RATIO = 2.4
+PROMPT_RESET_TEMPERATURE = 0.5                         # a window decoded above it does not condition the next one
 XATTN_BUDGET = 1 << 30                                 # bytes of captured attention per decode call on the alignment path
 UNSPACED_LANGUAGES = ("zh", "ja", "th", "lo", "my", "yue")
 PREPEND_PUNCTUATIONS = "\"'“¡¿([{-"
@@ -326,6 +333,36 @@ def longform_prefix(init, history, condition: bool, first_prompt, timestamp_begi
     return list(init)
 
 
+def compression_ratio(text: str) -> float:
+    """openai/whisper utils.compression_ratio: len(bytes) / len(zlib.compress(bytes)) of the text as UTF-8"""
+    b = text.encode("utf-8")
+    return len(b) / len(zlib.compress(b))
+
+
+def needs_fallback(ratio, avg, nosp, thresholds) -> bool:
+    """whisper.transcribe's decode_with_fallback decision for one decoded window.  thresholds: (compression_ratio_threshold,
+    logprob_threshold, no_speech_threshold), each None to skip its check.  Too repetitive (ratio above its threshold) or too
+    unlikely (avg_logprob below its threshold) asks for the next temperature, unless the window counts as silent (no_speech_prob
+    above its threshold and avg_logprob below its threshold): that one is skipped, not decoded again."""
+    cr, lp, ns = thresholds
+    need = (cr is not None and ratio > cr) or (lp is not None and avg < lp)
+    if ns is not None and lp is not None and nosp > ns and avg < lp:
+        need = False
+    return bool(need)
+
+
+def fallback_options(on: bool) -> dict:
+    """transcribe()'s keywords behind the whisper_fallback switches: whisper.transcribe's own defaults when on, nothing when off"""
+    return dict(temperature=FALLBACK_TEMPERATURES, compression_ratio_threshold=FALLBACK_COMPRESSION_RATIO) if on else {}
+
+
+def _temperatures(temperature):
+    temps = (float(temperature),) if isinstance(temperature, (int, float)) else tuple(float(t) for t in temperature)
+    if not 1 <= len(temps) <= MAX_TEMPERATURES:
+        raise ValueError(f"{len(temps)} temperatures: 1..{MAX_TEMPERATURES} (a row's noise stream is {MAX_TEMPERATURES} x the clip's index + the attempt)")
+    return temps
+
+
 def _int_array(v):                                      # (one element for an empty list: never a NULL pointer)
     return (C.c_int * max(1, len(v)))(*[int(t) for t in v])
 
@@ -375,10 +412,10 @@ class WhisperASR:
         ok = 1 <= nh <= MAX_ALIGN_HEADS and max_rows >= 1
         return torch.zeros(B, nh, max_rows, self.cfg["n_audio_ctx"], device=self.device) if ok else None
 
-    def _call(self, fn, B, *args):
+    def _call(self, fn, B, *args, ws_bytes=None):
         """fn(handle, *args, workspace, its bytes, the current stream) under the model's guard"""
         with self._guard.call():
-            ws = self._guard.workspace(self.workspace_bytes(B))
+            ws = self._guard.workspace(self.workspace_bytes(B) if ws_bytes is None else ws_bytes)
             _lib.check(fn(self._h, *args, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream))
 
     def workspace_bytes(self, B):
@@ -563,12 +600,17 @@ class WhisperASR:
         return feat
 
     def decode_ts(self, state: torch.Tensor, prefixes, max_new, suppress=(), begin_suppress=(), eos=None, no_timestamps_id=None,
-                  max_initial_timestamp_index=None, begin=None, sot_pos=None, no_speech_id=None, heads=None, first_row=None, max_rows=None):
+                  max_initial_timestamp_index=None, begin=None, sot_pos=None, no_speech_id=None, heads=None, first_row=None, max_rows=None,
+                  temperature=None, streams=None, seed=0):
         """greedy decoding under Whisper's timestamp rules, one prefix per row (tdx_whisper_decode_ts) -> step_ids, step_scores,
         counts as decode(), nospeech float32 [B] (None without sot_pos) and xattn [B, nh, max_rows, n_audio_ctx] (None without
         heads).  prefixes: a list of id lists; max_new: an int or one per row; begin: per row, where the row's history starts
         (default: its prefix length); sot_pos: per row, the position of <|startoftranscript|>; first_row: per row (default: its
-        prefix length)."""
+        prefix length).
+        temperature (a float or one per row; None: the greedy entry point, as ever): tdx_whisper_decode_ts_sample, every row draws
+        its ids from softmax(logits / T) over the ids the rules allow, a row at 0 decodes greedily; the scores are the drawn ids'
+        untempered log-probabilities.  streams: one 64-bit noise stream per row (default 0), seed: the generator's key; a row's
+        result depends on (seed, its stream, its inputs) alone."""
         self._check_open()
         g = self.gen_cfg
         B = self._check_state("decode_ts", state)
@@ -599,20 +641,39 @@ class WhisperASR:
             flat = _int_array([t for pair in heads for t in pair])
             max_rows = max(1, max(max_new) - 1) if max_rows is None else int(max_rows)
             xattn = self._alloc_xattn(B, nh, max_rows)
-        self._call(self._l.tdx_whisper_decode_ts, B, state.data_ptr(), B, _int_array(flat_prefix), mp, _int_array(plen), opt(begin), _int_array(suppress),
-                   len(suppress), _int_array(begin_suppress), len(begin_suppress), eos, nots, mi, _int_array(max_new), ns_id, opt(sot_pos),
-                   nospeech.data_ptr() if nospeech is not None else None, flat, nh, opt(first_row), int(max_rows or 0),
-                   xattn.data_ptr() if xattn is not None else None, ids.data_ptr(), scores.data_ptr(), counts.data_ptr())
+        args = (state.data_ptr(), B, _int_array(flat_prefix), mp, _int_array(plen), opt(begin), _int_array(suppress),
+                len(suppress), _int_array(begin_suppress), len(begin_suppress), eos, nots, mi, _int_array(max_new), ns_id, opt(sot_pos),
+                nospeech.data_ptr() if nospeech is not None else None, flat, nh, opt(first_row), int(max_rows or 0),
+                xattn.data_ptr() if xattn is not None else None, ids.data_ptr(), scores.data_ptr(), counts.data_ptr())
+        if temperature is None:
+            self._call(self._l.tdx_whisper_decode_ts, B, *args)
+            return ids, scores, counts, nospeech, xattn
+        temps = [float(temperature)] * B if isinstance(temperature, (int, float)) else [float(t) for t in temperature]
+        streams = [0] * B if streams is None else [int(t) for t in streams]
+        for name, v in (("temperature", temps), ("streams", streams)):
+            if len(v) != B:
+                raise _lib.TdxError(f"WhisperASR.decode_ts: {name} has {len(v)} entries for {B} rows")
+        self._call(self._l.tdx_whisper_decode_ts_sample, B, *args, (C.c_float * B)(*temps), (C.c_ulonglong * B)(*[t & (2 ** 64 - 1) for t in streams]),
+                   int(seed) & (2 ** 64 - 1), ws_bytes=int(self._l.tdx_whisper_decode_sample_workspace_bytes(self._h, B)))
         return ids, scores, counts, nospeech, xattn
 
     def transcribe(self, wavs, language=None, task: str = "transcribe", prompt_ids=None, condition_on_prev_tokens: bool = True,
-                   no_speech_threshold=0.6, logprob_threshold=-1.0, word_timestamps: bool = True, keys=None):
-        """whisper.transcribe(model, audio, initial_prompt=, word_timestamps=True, language=) at temperature 0, as transformers'
-        long-form generate runs it: clips of any length, decoded in 30 s windows with timestamp tokens, cut into segments at the
-        timestamp pairs, the next window starting at the last timestamp.  Per clip {"key", "language", "text", "segments": [{"id",
-        "seek", "start", "end", "text", "tokens", "avg_logprob", "no_speech_prob", "words"}]}.  All clips still running share one
-        encode and one decode_ts call per round of the loop, whatever their languages and prefix lengths."""
+                   no_speech_threshold=0.6, logprob_threshold=-1.0, word_timestamps: bool = True, keys=None, temperature=0.0,
+                   compression_ratio_threshold=None, seed=0):
+        """whisper.transcribe(model, audio, initial_prompt=, word_timestamps=True, language=), as transformers' long-form generate
+        runs it: clips of any length, decoded in 30 s windows with timestamp tokens, cut into segments at the timestamp pairs, the
+        next window starting at the last timestamp.  Per clip {"key", "language", "text", "segments": [{"id", "seek", "start",
+        "end", "text", "tokens", "avg_logprob", "no_speech_prob", "words"}]}.  All clips still running share one encode and one
+        decode_ts call per round of the loop, whatever their languages and prefix lengths.
+        temperature: a float (0.0: greedy), or up to 16 of them for upstream's decode_with_fallback: a window whose text compresses
+        better than compression_ratio_threshold or whose avg_logprob is below logprob_threshold (needs_fallback) is decoded again
+        at the next temperature, all such rows of a round in one decode_ts call on their gathered encoder state; the last attempt
+        stands.  A row's noise stream is (16 x the clip's index in the call + the attempt) << 32 | seek, so a clip's text does not
+        depend on the other clips.  A window decoded above temperature 0.5 does not condition the next one.  With anything but the
+        default 0.0 the segments also carry "temperature" and "compression_ratio" (of the attempt that stands)."""
         self._check_open()
+        temps = _temperatures(temperature)
+        thresholds = (compression_ratio_threshold, logprob_threshold, no_speech_threshold)
         if isinstance(wavs, (np.ndarray, torch.Tensor)):
             wavs = [wavs]
         g, c = self.gen_cfg, self.cfg
@@ -661,27 +722,50 @@ class WhisperASR:
                         raise ValueError(f"a prefix of {len(p)} ids leaves no room in a context of {T}")
                 max_new = [new_token_limit(len(p), None, {"max_length": g.get("max_length")}, T) for p in prefixes]
                 heads = self.alignment_heads if word_timestamps else None
-                ids, scores, counts, nosp, xattn = self.decode_ts(state, prefixes, max_new, suppress=sup, begin_suppress=beg, eos=eos, no_timestamps_id=tb - 1,
-                                                                   sot_pos=[len(p) - len(inits[i]) for p, i in zip(prefixes, live)], heads=heads)
-                counts_l, nosp_l = counts.cpu().tolist(), nosp.cpu().tolist()
-                frames = None
-                if word_timestamps:
-                    frames = token_align(xattn, [max(0, m - 1) for m in counts_l], [max(1, f // 2) for f in nfr]).cpu().tolist()
-                    del xattn
-                ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
+                sot = [len(p) - len(inits[i]) for p, i in zip(prefixes, live)]
+                # decode_with_fallback: attempt a decodes the rows that attempts 0 .. a - 1 left in need, at temps[a]; the last stands
+                rows, done = list(range(len(live))), {}
+                for attempt, temp in enumerate(temps):
+                    whole = len(rows) == len(live)
+                    kw = {}
+                    if attempt > 0 or temp != 0.0:
+                        kw = dict(temperature=[temp] * len(rows), seed=seed,
+                                  streams=[((MAX_TEMPERATURES * (c0 + live[k]) + attempt) << 32) | seek[live[k]] for k in rows])
+                    ids, scores, counts, nosp, xattn = self.decode_ts(
+                        state if whole else state[:, :, rows].contiguous(), prefixes if whole else [prefixes[k] for k in rows],
+                        max_new if whole else [max_new[k] for k in rows], suppress=sup, begin_suppress=beg, eos=eos, no_timestamps_id=tb - 1,
+                        sot_pos=sot if whole else [sot[k] for k in rows], heads=heads, **kw)
+                    counts_l, nosp_l = counts.cpu().tolist(), nosp.cpu().tolist()
+                    ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
+                    again = []
+                    for j, k in enumerate(rows):
+                        p0, m = len(prefixes[k]) - 1, counts_l[j]
+                        tok = [int(t) for t in ids[j, p0:p0 + m]]
+                        avg = float(np.sum(scores[j, p0:p0 + m], dtype=np.float64)) / m if m else 0.0
+                        ratio = compression_ratio(self.text_of(tok).strip())
+                        done[k] = {"tok": tok, "m": m, "avg": avg, "ratio": ratio, "nosp": nosp_l[j], "temp": temp}
+                        if attempt + 1 < len(temps) and needs_fallback(ratio, avg, nosp_l[j], thresholds):
+                            again.append(k)
+                    if word_timestamps:                     # the alignment of the rows whose attempt stands (0 rows: nothing is written)
+                        fr = token_align(xattn, [0 if k in again else max(0, counts_l[j] - 1) for j, k in enumerate(rows)],
+                                         [max(1, nfr[k] // 2) for k in rows]).cpu().tolist()
+                        for j, k in enumerate(rows):
+                            done[k]["frames"] = fr[j]
+                        del xattn
+                    if not again:
+                        break
+                    rows = again
                 for k, i in enumerate(live):
-                    p0, m = len(prefixes[k]) - 1, counts_l[k]
-                    tok = [int(t) for t in ids[k, p0:p0 + m]]
-                    avg = float(np.sum(scores[k, p0:p0 + m], dtype=np.float64)) / m if m else 0.0
+                    tok, m, avg, nosp_k = done[k]["tok"], done[k]["m"], done[k]["avg"], done[k]["nosp"]
                     if (no_speech_threshold is not None and logprob_threshold is not None and avg < logprob_threshold
-                            and nosp_l[k] > no_speech_threshold):
+                            and nosp_k > no_speech_threshold):
                         seek[i] += nfr[k]                   # a silent window: skipped whole
                         continue
                     body = tok[:-1] if tok and tok[-1] == eos else tok
                     t0 = seek[i] * TIME_PRECISION / 2
                     times = None
                     if word_timestamps:
-                        t = [f * TIME_PRECISION for f in frames[k][:max(0, m - 1)]]
+                        t = [f * TIME_PRECISION for f in done[k]["frames"][:max(0, m - 1)]]
                         times = (t + [t[-1]]) if t else [0.0] * m
                     cut, step = cut_segments(body, tb, seek[i], nfr[k])
                     at = 0
@@ -692,8 +776,12 @@ class WhisperASR:
                             words = [(w, [a + t0, b + t0]) for w, (a, b) in _word_timestamps(s["tokens"], tt, self.token_list, langs[i], eos)]
                         at += len(s["tokens"])
                         segs[i].append({"id": len(segs[i]), "seek": seek[i], "start": s["start"], "end": s["end"], "text": self.text_of(s["tokens"]),
-                                        "tokens": s["tokens"], "avg_logprob": avg, "no_speech_prob": float(nosp_l[k]), "words": words})
+                                        "tokens": s["tokens"], "avg_logprob": avg, "no_speech_prob": float(nosp_k), "words": words})
+                        if temps != (0.0,):
+                            segs[i][-1].update(temperature=done[k]["temp"], compression_ratio=done[k]["ratio"])
                         history[i].append(s["tokens"])
+                    if done[k]["temp"] > PROMPT_RESET_TEMPERATURE:
+                        history[i] = []                     # upstream's prompt_reset_since: the next window carries no previous text
                     seek[i] += step
             for i in range(n):
                 out.append({"key": keys[c0 + i] if keys is not None else f"clip_{c0 + i}", "language": langs[i],
