@@ -110,6 +110,14 @@ typedef struct tdx_h3_seg {
 int tdx_h3_gemm_ex(int b_kmajor, int paired, int twoseg, int a_conv, const tdx_h3_seg* seg0, const tdx_h3_seg* seg1_or_null, int M, int N,
                    int pair_off, int batches, int Hin, int Win, int Hout, int Wout, int stride, int ntaps, int cin, int taps_total,
                    const void* zero_row, float* out_dev, long ldo, long strideO, int nreal, int* plan_or_null, void* stream);
+/* the fp32-A operand form of the x3 core (csrc/gemm_h3f.hpp): A = fp32 NHWC pixel rows a_dev [B*Hin*Win][lda floats] split WHILE STAGED with
+ * the static scale a_mul, a power of two (xs = x * a_mul, hi = f16(xs), lo = f16(xs - hi); |x| * a_mul < 65504 is the caller's), *inv_dev = 1 / a_mul, B =
+ * row-major weight planes [N][K] + row scales.  Output row m = (b, h, w) of [B, Hout, Wout] reads pixel (b, h*stride, w*stride):
+ *   out[m*ldo + n] = inv * sb[n] * sum over k of A'[pix(m)][k] * B'[n][k]      for n < nreal,
+ * bit-identical to tdx_h3_split_rows_static + tdx_h3_gemm_ex(a_conv = 1, ntaps = 1, sa_mul = 0) on the same data.  Refused: a null pointer,
+ * K % 16, lda < K, lda % 4, M % (Hout*Wout), an output pixel that reads outside the image. */
+int tdx_h3_gemm_f32a(const float* a_dev, long lda, float a_mul, const float* inv_dev, const void* pb, const float* sb, int M, int N, int K,
+                     int Hin, int Win, int Hout, int Wout, int stride, float* out_dev, long ldo, int nreal, void* stream);
 /* the plan of launch_gemm_h3x (plan_gemm_h3) and its block -> tile map (h3_tile_of_block) on the HOST, no device touched:
  * tests/test_h3_tile_map.py.  tdx_h3_plan: plan[6] as above and grid[2] = (gridDim.x, gridDim.y) for one launch of M x N (PAIRED: N pair
  * columns) over ktot = the sum of the segments' K.  tdx_h3_tile_of_block: 1 and (*z, *bm, *bn) if block (bx, by) of that launch

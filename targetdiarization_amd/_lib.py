@@ -247,6 +247,7 @@ class H3Seg(C.Structure):
 DIAG_SIGNATURES = {
     "tdx_diag_last_error": (C.c_char_p, []),
     "tdx_h3_gemm_ex": (_i, [_i] * 4 + [C.POINTER(H3Seg)] * 2 + [_i] * 12 + [_vp, _vp, _l, _l, _i, C.POINTER(_i), _vp]),
+    "tdx_h3_gemm_f32a": (_i, [_vp, _l, C.c_float, _vp, _vp, _vp] + [_i] * 8 + [_vp, _l, _i, _vp]),
     "tdx_h3_plan": (_i, [_i] * 5 + [C.POINTER(_i)] * 2),
     "tdx_h3_tile_of_block": (_i, [C.POINTER(_i), _i, _i, _i] + [C.POINTER(_i)] * 3),
     "tdx_h3_split_rows_static": (_i, [_vp, _l, _vp, _l, _i, C.c_float, _vp]),

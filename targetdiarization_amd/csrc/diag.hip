@@ -16,6 +16,7 @@
 #include "../../include/tdx_test.h"
 #include "dft_basis.hpp"
 #include "epilogues.hpp"
+#include "gemm_h3f.hpp"
 #include "mf2_attention.hpp"
 #include "weight_pack.hpp"
 #include "whisper_noise.hpp"
@@ -399,6 +400,29 @@ int tdx_h3_gemm_ex(int b_kmajor, int paired, int twoseg, int a_conv, const tdx_h
     if (twoseg) return run_gemm_h3<false, false, true, false>(g, batches, e, plan_or_null, st);
     if (b_kmajor) return run_gemm_h3<true, false, false, false>(g, batches, e, plan_or_null, st);
     return run_gemm_h3<false, false, false, false>(g, batches, e, plan_or_null, st);
+}
+
+// the x3 core with an fp32 A operand split while it is staged (gemm_h3f.hpp), with a plain store: tests/test_gpu_h3_f32a.py.  The same product
+// as tdx_h3_split_rows_static(a, s = a_mul) + tdx_h3_gemm_ex(A_CONV, one tap, sa = inv_dev, sa_mul = 0) on the same data, bit for bit.
+int tdx_h3_gemm_f32a(const float* a, long lda, float a_mul, const float* inv_dev, const void* pb, const float* sb, int M, int N, int K,
+                     int Hin, int Win, int Hout, int Wout, int stride, float* out, long ldo, int nreal, void* stream) {
+    const auto bad = [](const char* m) { return tdx::fail(TDX_E_INVALID, std::string("tdx_h3_gemm_f32a: ") + m); };
+    if (!a || !inv_dev || !pb || !sb || !out) return bad("null argument");
+    if (M < 1 || N < 1 || K < 16 || K % 16) return bad("need M >= 1, N >= 1, K >= 16, K % 16 == 0");
+    if (lda < K || lda % 4) return bad("need lda >= K floats, lda % 4 == 0 (16-byte loads)");
+    if (!(a_mul > 0.f) || !(a_mul < 3e38f)) return bad("need 0 < a_mul < inf");
+    if (nreal < 1 || nreal > N || ldo < 1) return bad("need 1 <= nreal <= N, ldo >= 1");
+    if (Hin < 1 || Win < 1 || Hout < 1 || Wout < 1 || stride < 1) return bad("need positive extents, stride >= 1");
+    if ((long)Hout * Wout > 0x7fffffffL || M % (Hout * Wout)) return bad("need M == B * Hout * Wout");
+    if ((long)(Hout - 1) * stride >= Hin || (long)(Wout - 1) * stride >= Win) return bad("an output pixel reads outside the image");
+    if ((long)(M / (Hout * Wout)) * Hin * Win > 0x7fffffffL) return bad("rows beyond int");
+    H3Args g{};
+    g.seg[0] = h3_seg(a, inv_dev, 4L * lda, pb, sb, 4L * K, K);
+    g.seg[0].sa_mul = 0;
+    g.nseg = 1; g.M = M; g.N = N;
+    g.cv_Hin = Hin; g.cv_Win = Win; g.cv_Hout = Hout; g.cv_Wout = Wout; g.cv_stride = stride; g.cv_ntaps = 1; g.cv_cin = K;
+    const hipError_t r = launch_gemm_h3f(g, a_mul, EpiPlainN{out, ldo, 0, nreal}, (hipStream_t)stream);
+    return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
 }
 
 // the plan and the block -> tile map of the x3 core on the host (gemm_h3.hpp plan_gemm_h3 / h3_tile_of_block): tests/test_h3_tile_map.py.

@@ -5,8 +5,10 @@
 //
 // Layout: NHWC fp32, rows = (b, freq, time), channels contiguous and padded to a multiple of
 // 32.  The convolutions are implicit GEMMs (CONV mode: one K segment per tap, the A-loader computes the
-// shifted/strided input row and zero-fills the halo) — stage 1's 1x1 convolutions on the fp32-MFMA core (gemm.hpp),
-// stages 2-4 on the split-f16 x3 core (gemm_h3.hpp) over planes with a static scale (ReLU20-bounded activations) —
+// shifted/strided input row and zero-fills the halo) — stages 3-4 on the split-f16 x3 core (gemm_h3.hpp) over planes with
+// a static scale (ReLU20-bounded activations), the 1x1 convolutions of stages 1-2 on the fp32-A form of that core
+// (gemm_h3f.hpp: the fp32 rows are split while they are staged; TDX_ERES_F32A = 0 / 1 / 2 selects none / stage 2 / both;
+// conv1 and the shortcut of the first block read the stem's unbounded ReLU output and stay on the fp32-MFMA core, gemm.hpp) —
 // except the 3x3 chain convolutions of stages 1-2, which run on an LDS-tiled direct x3 convolution (chain_conv_x3_kernel).
 // Eval-mode BatchNorm is folded into the weights on the host; ReLU20 / residual / Res2Net chain add / AFF gate are
 // fused into the epilogues.
@@ -19,6 +21,7 @@
 
 #include "../../include/tdx.h"
 #include "epilogues.hpp"
+#include "gemm_h3f.hpp"
 #include "weight_pack.hpp"
 #include "weight_planes.hpp"
 
@@ -525,6 +528,23 @@ int conv_gemm_h3(const unsigned char* Ap, const float* inv_scale, const unsigned
     return TDX_OK;
 }
 
+// a 1x1 convolution on the x3 core's fp32-A form (gemm_h3f.hpp): A = the fp32 NHWC input itself (pixel pitch lda floats, |x| * a_mul <
+// 65504), split with the static scale a_mul while it is staged — no split pass, no planes in HBM, the bits of conv_gemm_h3 over
+// h3_split_rows_static / split_rows_static_s2 planes
+template <class Epi>
+int conv_gemm_h3f(const float* A, long lda, float a_mul, const float* inv_scale, const ConvW& cw, int B, int Hin, int Win, int Hout, int Wout,
+                  int stride, Epi e, hipStream_t st) {
+    const long M = (long)B * Hout * Wout;
+    H3Args g{};
+    g.seg[0] = h3_seg(A, inv_scale, 4L * lda, cw.hp, cw.hs, 4L * cw.cinp, cw.cinp);
+    g.seg[0].sa_mul = 0;
+    g.nseg = 1; g.M = (int)M; g.N = cw.Npad;
+    g.cv_Hin = Hin; g.cv_Win = Win; g.cv_Hout = Hout; g.cv_Wout = Wout; g.cv_stride = stride; g.cv_ntaps = 1; g.cv_cin = cw.cinp;
+    if (cw.taps != 1 || !cw.hp || lda < cw.cinp) return tdx::fail(TDX_E_INVALID, "conv_gemm_h3f: a 1x1 convolution with weight planes and lda >= cinp");
+    const hipError_t r = launch_gemm_h3f(g, a_mul, e, st);
+    return r == hipSuccess ? TDX_OK : tdx::fail_hip(r, __FILE__, __LINE__);
+}
+
 // ... with the 9 taps split over 3 batches of 3 taps (few output rows: e.g. 72 tiles of 576 k-steps for two 8.7 s clips) into
 // slab[3][M][N], then summed
 constexpr long DS_SPLIT_ROWS = 4096;
@@ -683,6 +703,7 @@ int tdx_eres2net_create(const void* blob, size_t blob_bytes, int device, tdx_ere
         for (int s = 0; s < NSTAGE; ++s)
             for (int i = 0; i < kBlocks[s]; ++i, ++bi) {
                 BlockW& b = h->blocks[bi];
+                if (s < 1) { if (i > 0) jobs.push_back(&b.conv1); jobs.push_back(&b.conv3); }     // stage 1's 1x1s on the fp32-A form (not the first block's conv1 / shortcut)
                 if (s < 1) { for (int j = 0; j < SCALE; ++j) jobs.push_back(&b.convs[j]); continue; }     // stage 1: the chain convolutions only
                 jobs.push_back(&b.conv1); if (b.has_sc) jobs.push_back(&b.sc);
                 for (int j = 0; j < SCALE; ++j) jobs.push_back(&b.convs[j]);
@@ -775,6 +796,10 @@ int tdx_eres2net_forward(tdx_eres2net* h, const float* feat, int B, int F, float
     const float* inv20 = h->dev + h->consts;            // 2^-10
     const float* inv40 = h->dev + h->consts + 1;        // 2^-9
     const unsigned char* zero_row = (const unsigned char*)(h->dev + h->consts + 64);
+    // the 1x1 convolutions with ReLU20-bounded inputs on the fp32-A form of the x3 core (gemm_h3f.hpp): 0 = none (separate split passes
+    // for stage 2, the fp32-MFMA core for stage 1), 1 = stage 2, 2 = stages 1 and 2 (read per forward, like TDX_ERES_AFF34_ROWS)
+    const char* f32a_env = getenv("TDX_ERES_F32A");
+    const int f32a_level = f32a_env ? atoi(f32a_env) : 2;
 
     hipLaunchKernelGGL(stem_kernel, dim3((unsigned)((rows1 * 16 + 255) / 256)), dim3(256), 0, st, feat, h->dev + h->stem_w, h->dev + h->stem_b, P[0], F, (long)rows1);
     LAUNCH_CHECK();
@@ -789,9 +814,19 @@ int tdx_eres2net_forward(tdx_eres2net* h, const float* feat, int B, int F, float
         const int iy = cur < 0 ? 0 : (cur + 1) % 3, ir = cur < 0 ? 1 : (cur + 2) % 3;
         float* y = last_of_stage3 ? keep3 : P[iy];
         float* res = P[ir];
-        const bool x3 = b.conv1.hp != nullptr;          // stages 3-4: the convolutions run on the split-f16 x3 core
+        const bool x3 = s >= 1;                         // stages 2-4: the convolutions run on the split-f16 x3 core
+        const bool f32a = (s == 0 && f32a_level >= 2) || (s == 1 && f32a_level >= 1);      // ... reading fp32 rows, split while staged
+        // the static scale 2^10 needs |x| < 64: every block input is a ReLU20 output except the stem's (a plain ReLU, unbounded),
+        // so conv1 and the shortcut of the very first block stay on the fp32-MFMA core
+        const bool f32a_in = f32a && !(s == 0 && cnt == 0);
         const float* resid = x;
-        if (x3) {
+        if (f32a_in) {
+            TRY(conv_gemm_h3f(x, b.cin, 1024.0f, inv20, b.conv1, B, Hin, Win, Ho, Wo, b.stride, EpiBiasActN<ActRelu20>{h->dev + b.conv1.b, o1, b.w4, b.w4}, st));
+            if (b.has_sc) {
+                TRY(conv_gemm_h3f(x, b.cin, 1024.0f, inv20, b.sc, B, Hin, Win, Ho, Wo, b.stride, EpiBiasActN<>{h->dev + b.sc.b, res, b.cout, b.cout}, st));
+                resid = res;
+            }
+        } else if (x3) {
             // block input (ReLU20 output, <= 20) as planes with the static scale 2^10, shared by conv1 and the shortcut
             int Hc = Hin, Wc = Win, sc_ = b.stride;            // geometry of the 1x1 convolutions over the planes
             if (b.stride == 2 && b.cin % 16 == 0) {            // only the pixels the stride-2 convolutions read, compacted
@@ -838,7 +873,9 @@ int tdx_eres2net_forward(tdx_eres2net* h, const float* feat, int B, int F, float
             if (b.is_aff && j + 1 < SCALE)      // in_{j+1} = AFF(sp_j, spx[j+1])
                 TRY(run_aff(h, b.aff[j], cat + j * b.width, b.w4, o1 + (j + 1) * b.width, b.w4, tbuf, spin[(j + 1) & 1], b.wpad, M, st));
         }
-        if (x3) {   // conv3 + bn3 + residual + relu20 -> y   (cat = ReLU20 outputs)
+        if (f32a) {   // conv3 + bn3 + residual + relu20 -> y   (cat = ReLU20 outputs: static scale 2^10)
+            TRY(conv_gemm_h3f(cat, b.w4, 1024.0f, inv20, b.conv3, B, Ho, Wo, Ho, Wo, 1, EpiBiasRes<ActRelu20>{h->dev + b.conv3.b, resid, y, b.cout}, st));
+        } else if (x3) {
             if (tdx::launch_h3_split_rows_static(cat, b.w4, hcat, M, b.w4, 1024.0f, st) != hipSuccess)
                 return tdx::fail_hip(hipGetLastError(), __FILE__, __LINE__);
             TRY(conv_gemm_h3(hcat, inv20, zero_row, b.conv3, B, Ho, Wo, Ho, Wo, 1, EpiBiasRes<ActRelu20>{h->dev + b.conv3.b, resid, y, b.cout}, st));
