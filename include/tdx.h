@@ -832,6 +832,47 @@ int tdx_spectral_laplacian(const float* emb_dev, int n, int d, int drop, double*
                            size_t workspace_bytes, void* stream);
 int tdx_symeig_lowest(double* M_dev, int n, int m, double* w_dev, double* V_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * FFT of any length n — prime, odd or a power of two — and the band mix of AudioProcessor.mix_audio_by_freq
+ * (AudioProcessor.py:845-882) on top of it — DESIGN 8.27.  Stateless: no handle, no allocation, no synchronisation, nothing but
+ * kernel launches on the caller's stream (capturable).  No floating-point atomics: a result depends on (n, data) alone, row b of
+ * a batch equals a call with that row alone bit for bit, and so does a repeated call.
+ *      Layout: complex64, re / im interleaved, [batch][n]; a half spectrum is [batch][n / 2 + 1].  numpy's conventions: the
+ *      forward transform is unnormalised, the inverse is scaled by 1 / n.
+ *      Powers of two: Stockham autosort, up to TDX_FFT_TILE points in one workgroup's LDS, longer ones in several passes that
+ *      each read and write the data once.  Any other n: Bluestein's chirp-z over the power of two M >= 2n - 1, the chirp
+ *      evaluated in fp64 from k^2 mod 2n and rounded once, rebuilt in the workspace on every call (up to 64 points: the DFT sum
+ *      itself in fp64; the band mix of a clip of up to 64 samples runs in fp64 throughout and is rounded once).
+ *
+ *      tdx_fft_c2c: x_dev [batch][n] complex -> y_dev [batch][n] complex, inverse != 0 for the inverse.
+ *      tdx_fft_r2c: x_dev [batch][n] real -> X_dev [batch][n / 2 + 1] complex (np.fft.rfft).  Even n: one complex transform of
+ *      n / 2 points and a split; odd n: the complex path.
+ *      tdx_fft_c2r: X_dev [batch][n / 2 + 1] complex -> y_dev [batch][n] real (np.fft.irfft(X, n)); the imaginary parts of bin 0
+ *      and, for even n, of bin n / 2 are ignored.
+ *      tdx_fft_band_mix: two real clips of n samples -> y_dev [2 (n / 2)].  Z = DFT_n(main + i aux) is one complex transform;
+ *      F_main[k] = (Z[k] + conj Z[n - k]) / 2, F_aux[k] = (Z[k] - conj Z[n - k]) / 2i for the bins k <= n / 2.  ranges = the bin
+ *      ranges [lo, hi) of main, aux and their overlap (fft.band_mix_plan): mix[k] = F_main[k] in main's range, then F_aux[k] in
+ *      aux's, then F_main[k] w + F_aux[k] (1 - w) in the overlap, w = np.linspace(1, 0, count)[k - lo] formed in fp64 (j step +
+ *      1, the last one exactly 0, [1.0] for one bin), blended in fp64 and rounded once; a bin in no range is exactly 0.
+ *      y = np.fft.irfft(mix): the n / 2 + 1 bins read as the spectrum of m = 2 (n / 2) samples (an odd n comes back one sample
+ *      shorter), the imaginary parts of bin 0 and of the last bin dropped, through one inverse complex transform of m / 2
+ *      points.  Taps (each NULL or complex64 [n / 2 + 1]): F_main, F_aux and mix (with all its imaginary parts).
+ *
+ *      Limits, each TDX_E_INVALID with its own message before the device is touched: 1 <= n <= 2^26 (band mix: 2 <= n),
+ *      1 <= batch <= 65535, bin ranges 0 <= lo <= hi <= n / 2 + 1, no null pointer (taps excepted), every pointer 8-byte
+ *      aligned (the kernels move pairs of floats; a real row of even length is read as n / 2 complex), the workspace at least tdx_fft_workspace_bytes(n, batch) (one size for the three transforms) or
+ *      tdx_fft_band_mix_workspace_bytes(n); both are 0 for arguments outside the limits.  In-place operation (the output is the
+ *      input) is rejected; input and output must not overlap.
+ * ---------------------------------------------------------------------------------- */
+#define TDX_FFT_TILE 4096
+size_t tdx_fft_workspace_bytes(long n, int batch);
+int tdx_fft_c2c(const float* x_dev, long n, int batch, int inverse, float* y_dev, void* ws, size_t ws_bytes, void* stream);
+int tdx_fft_r2c(const float* x_dev, long n, int batch, float* X_dev, void* ws, size_t ws_bytes, void* stream);
+int tdx_fft_c2r(const float* X_dev, long n, int batch, float* y_dev, void* ws, size_t ws_bytes, void* stream);
+size_t tdx_fft_band_mix_workspace_bytes(long n);
+int tdx_fft_band_mix(const float* main_dev, const float* aux_dev, long n, const long ranges[6], float* y_dev, float* tap_main, float* tap_aux,
+                     float* tap_mix, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,13 @@ int tdx_diag_loader_bind(const void* blob, size_t blob_bytes, int n, int npad, i
 int tdx_test_whisper_noise(unsigned long long seed, unsigned long long row_stream, int p, int n0, int count, float* g_dev, unsigned* word_dev,
                            void* stream);
 
+/* tdx_fft_c2c (csrc/fft.hpp) with a tile of 2^tile_log2 points, 4 <= tile_log2 <= 12, in place of TDX_FFT_TILE: the same kernels and
+ * the same planner, so that the multi-pass plans occur at small sizes (tests/test_gpu_fft.py).  tdx_test_fft_passes: the passes of a
+ * power-of-two transform of 2^m points under that tile (host only), 0 for arguments outside 0 <= m <= 27. */
+size_t tdx_test_fft_workspace_bytes(long n, int batch, int tile_log2);
+int tdx_test_fft_passes(int m, int tile_log2);
+int tdx_test_fft_c2c(const float* x_dev, long n, int batch, int inverse, float* y_dev, void* ws, size_t ws_bytes, void* stream, int tile_log2);
+
 /* per-CU operand fill rates (tools/fill_bench*.py) */
 int tdx_fill_bench(int mode, const void* src_dev, long bytes_per_block, int blocks, int iters, float* sink_dev, void* stream);
 int tdx_fill_bench2(int mode, const void* src_dev, int stride, int blocks, int iters, float* sink_dev, void* stream);

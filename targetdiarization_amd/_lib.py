@@ -197,6 +197,12 @@ SIGNATURES = {
     "tdx_spectral_workspace_bytes": (_sz, [_i, _i, _i]),
     "tdx_spectral_laplacian": (_i, [_fp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "tdx_symeig_lowest": (_i, [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "tdx_fft_workspace_bytes": (_sz, [C.c_long, _i]),
+    "tdx_fft_c2c": (_i, [_fp, C.c_long, _i, _i, _fp, _vp, _sz, _vp]),
+    "tdx_fft_r2c": (_i, [_fp, C.c_long, _i, _fp, _vp, _sz, _vp]),
+    "tdx_fft_c2r": (_i, [_fp, C.c_long, _i, _fp, _vp, _sz, _vp]),
+    "tdx_fft_band_mix_workspace_bytes": (_sz, [C.c_long]),
+    "tdx_fft_band_mix": (_i, [_fp, _fp, C.c_long, C.POINTER(C.c_long), _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
 }
 
 
@@ -268,6 +274,9 @@ DIAG_SIGNATURES = {
     "tdx_diag_dft_synthesis": (_i, [_i, _i, _l, _l, _i, _vp]),
     "tdx_diag_loader_bind": (_i, [_vp, _sz] + [_i] * 9 + [_vp, _sz, C.POINTER(_i)]),
     "tdx_test_whisper_noise": (_i, [C.c_ulonglong, C.c_ulonglong, _i, _i, _i, _vp, _vp, _vp]),
+    "tdx_test_fft_workspace_bytes": (_sz, [_l, _i, _i]),
+    "tdx_test_fft_passes": (_i, [_i, _i]),
+    "tdx_test_fft_c2c": (_i, [_vp, _l, _i, _i, _vp, _vp, _sz, _vp, _i]),
     "tdx_fill_bench": (_i, [_i, _vp, _l, _i, _i, _vp, _vp]),
     "tdx_fill_bench2": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
     "tdx_fill_bench3": (_i, [_vp, _l, _i, _l, _i, _i, _i, _vp, _vp]),

@@ -113,6 +113,7 @@ class AudioProcessor:
                 print(f"Failed to init noise gate: {e}")
                 self.noise_reduce = False
         self.effects = None                              # effects.PhaseVocoder, created by the first audio_stretch / audio_pitch / eq_match
+        self.fft = None                                  # fft.DeviceFFT, created by the first mix_audio_by_freq
         self.restorer = None
         self.is_restore_audio = is_restore_audio
         if self.is_restore_audio and (restorer_state_dict is not None or os.path.isdir(self.restorer_weights_folder)):
@@ -415,6 +416,131 @@ class AudioProcessor:
         except Exception as e:
             print(f"Failed in eq_match: {e}")
             return source_audio
+
+    # ---- AudioProcessor.py:386-414, 786-842: one elementwise pass over data that lives on the host (and numpy's global random
+    # stream, which np.random.seed must keep reproducing) — host-only on purpose, plain numpy with the reference's arithmetic
+    def audio_gain(self, audio_data: np.ndarray, gain_db: float, clip_limit: bool = False):
+        if self.verbose_log:
+            print("\nRunning module: audio_gain")
+            print(f"Gain dB: {gain_db}")
+            print(f"Apply clip limit: {clip_limit}")
+        if gain_db == 0.0:
+            if self.verbose_log:
+                print("gain_db is zero. Skip.")
+            return audio_data
+        output_audio = audio_data * 10 ** (gain_db / 20.0)
+        if clip_limit:
+            output_audio = np.clip(output_audio, -1, 1)
+        return output_audio
+
+    def audio_normalize(self, audio_data: np.ndarray, target_peak_db: float = -0.1):
+        if self.verbose_log:
+            print("\nRunning module: audio_normalize")
+            print(f"Target peak dB: {target_peak_db}")
+        current_peak = np.max(np.abs(audio_data))
+        if current_peak == 0.0:
+            return audio_data
+        gain_db = target_peak_db - 20 * np.log10(current_peak)
+        return np.clip(audio_data * 10 ** (gain_db / 20), -1.0, 1.0)
+
+    def generate_noise(self, sampling_rate: int = 16000, duration_sec: float = 1.0, gain_db: float = 0.0, noise_type: str = "brown"):
+        """white / pink / brown noise or silence, float32 [int(duration_sec * sampling_rate)]; the pink filter runs in float64"""
+        n = int(duration_sec * sampling_rate)
+        white = np.random.normal(0, 1, n)             # drawn for every type, silence included: the global stream advances alike
+        if noise_type == "silence":
+            shaped = np.zeros(n)
+        elif noise_type == "pink":                    # 1 / sqrt(f) on the spectrum (bin 0 kept), peak-normalised
+            f = np.fft.rfftfreq(n, d=1.0 / sampling_rate)
+            shaped = np.fft.irfft(np.fft.rfft(white) * np.concatenate(([1], 1 / np.sqrt(f[1:]))), n=n)
+            shaped = shaped / np.max(np.abs(shaped))
+        elif noise_type == "brown":                   # a random walk, peak-normalised
+            shaped = np.cumsum(white)
+            shaped = shaped / np.max(np.abs(shaped))
+        else:                                         # any other name: the white noise as drawn
+            shaped = white
+        out = shaped.astype(np.float32)
+        return out if gain_db == 0.0 else self.audio_gain(out, gain_db)
+
+    @staticmethod
+    def _to_mono_host(audio_data: np.ndarray):
+        """int16_to_float32 + audio_to_mono of the reference (:350-368, :1043-1048) for one [n, C] host array"""
+        if np.issubdtype(audio_data.dtype, np.floating):
+            audio_data = audio_data.astype(np.float32)
+        else:
+            audio_data = np.clip(audio_data / 32768.0, -1.0, 1.0).astype(np.float32)
+        channels = audio_data.shape[1]
+        weights = {6: np.array([1, 1, 1, 0.5, 0.7, 0.7]), 8: np.array([1, 1, 1, 0.5, 0.7, 0.7, 0.5, 0.5])}.get(channels, np.ones(channels))
+        return np.average(audio_data.reshape((-1, channels)), axis=1, weights=weights).astype(np.float32)
+
+    def mix_audio(self, audio_data_list: list, combine_channels: bool = True, normalize: bool = True):
+        """Sum (or stack as channels) a list of clips, the shorter ones padded with silence; like the reference, multi-channel
+        entries of the caller's list are replaced by their mono mix."""
+        if self.verbose_log:
+            print("\nRunning module: mix_audio")
+        if isinstance(audio_data_list, np.ndarray):
+            print("Input should be a np.ndarray audio list.")
+            return audio_data_list
+        if len(audio_data_list) == 1:
+            print("Length of audio_data_list should be greater than 2.")
+            return audio_data_list[0]
+        for i, clip in enumerate(audio_data_list):
+            if clip.ndim > 1:
+                audio_data_list[i] = self._to_mono_host(clip)
+        length = max((c.shape[0] for c in audio_data_list), default=0)
+        rows = [c if c.shape[0] == length else np.concatenate((c, np.zeros(length - c.shape[0], dtype=np.float32))) for c in audio_data_list]
+        if combine_channels:
+            mixed = np.zeros(length, dtype=np.float32)
+            for r in rows:                           # in list order, one at a time: the sum's rounding is the reference's
+                mixed = mixed + r
+        else:
+            mixed = np.stack(rows, axis=1)
+        mixed = mixed.astype(np.float32)
+        return self.audio_normalize(mixed) if normalize else mixed
+
+    def _fft(self):
+        if self.fft is None:
+            if str(self.device) == "cpu":
+                raise _lib.TdxError("no device (cuda_device=-1); there is no CPU path")
+            from .fft import DeviceFFT
+            self.fft = DeviceFFT(self._dev())
+        return self.fft
+
+    # AudioProcessor.py:845-882
+    def mix_audio_by_freq(self, audio_main: np.ndarray, audio_aux: np.ndarray, sampling_rate: int = 16000, main_freq_range=[0, 4000],
+                          aux_freq_range=[0, 8000], force_align: bool = False):
+        """The spectrum of `audio_main` in main_freq_range, that of `audio_aux` in aux_freq_range and a linear cross-fade where the two
+        overlap, transformed back: float32 [2 * (n // 2)] (the reference calls irfft without a length, so an odd clip comes back one
+        sample shorter; it returns float64).  One whole-clip FFT on the device (fft.DeviceFFT.band_mix, csrc/fft.hpp).  With force_align
+        a shorter aux is padded with silence (the reference pads main instead and then fails).  Clips of different lengths without
+        force_align, input that is not 1-D, fewer than 2 samples or a failure print their reason and return audio_main."""
+        if self.verbose_log:
+            print("\nRunning module: mix_audio_by_freq")
+        try:
+            main, aux = np.asarray(audio_main), np.asarray(audio_aux)
+            if main.ndim != 1 or aux.ndim != 1:
+                print(f"mix_audio_by_freq: the clips must be 1-D, got shapes {main.shape} and {aux.shape}; audio_main returned unchanged")
+                return audio_main
+            if main.shape[0] != aux.shape[0]:
+                if not force_align:
+                    print("audio_main and audio_aux should have same lengths with same sampling rates.")
+                    return audio_main
+                if main.shape[0] < aux.shape[0]:
+                    aux = aux[:main.shape[0]]
+                else:
+                    aux = np.concatenate((aux, np.zeros(main.shape[0] - aux.shape[0], dtype=aux.dtype)))
+            if main.shape[0] < 2:
+                print("mix_audio_by_freq: the clips need at least 2 samples; audio_main returned unchanged")
+                return audio_main
+            from .fft import band_mix_plan
+            plan = band_mix_plan(main.shape[0], sampling_rate, list(main_freq_range) if main_freq_range else None,
+                                 list(aux_freq_range) if aux_freq_range else None)
+            if self.verbose_log:
+                print(f"Frequency selected from audio_main: {plan['main_freq_range']}")
+                print(f"Frequency selected from audio_aux: {plan['aux_freq_range']}")
+            return self._fft().band_mix(main, aux, plan)
+        except Exception as e:
+            print(f"Failed in mix_audio_by_freq: {e}")
+            return audio_main
 
     def init_mdx_model(self):
         """:224-241: the block STFT geometry (hop by `quality`, dim_t = 2**8 frames)"""

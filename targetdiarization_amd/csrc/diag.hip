@@ -16,6 +16,7 @@
 #include "../../include/tdx_test.h"
 #include "dft_basis.hpp"
 #include "epilogues.hpp"
+#include "fft.hpp"
 #include "gemm_h3f.hpp"
 #include "mf2_attention.hpp"
 #include "weight_pack.hpp"
@@ -639,6 +640,21 @@ extern "C" int tdx_fill_bench(int mode, const void* src, long bytes_per_block, i
     if (mode == 0) hipLaunchKernelGGL(fill_bench_kernel<0>, dim3(blocks), dim3(512), 131072, (hipStream_t)stream, (const unsigned char*)src, bytes_per_block, iters, sink);
     else hipLaunchKernelGGL(fill_bench_kernel<1>, dim3(blocks), dim3(512), 131072, (hipStream_t)stream, (const unsigned char*)src, bytes_per_block, iters, sink);
     return hipGetLastError() == hipSuccess ? TDX_OK : TDX_E_HIP;
+}
+
+// the FFT of fft.hpp under a small tile (include/tdx_test.h): tests/test_gpu_fft.py
+static bool fft_tile_ok(int tile_log2) { return tile_log2 >= tdx::fft::MIN_TILE_LOG2 && tile_log2 <= tdx::fft::MAX_TILE_LOG2; }
+extern "C" size_t tdx_test_fft_workspace_bytes(long n, int batch, int tile_log2) {
+    if (tdx::fft::size_error(n, batch) || !fft_tile_ok(tile_log2)) return 0;
+    return std::max<size_t>(tdx::fft::c2c_ws_floats(n, batch, tile_log2), 64) * sizeof(float);
+}
+extern "C" int tdx_test_fft_passes(int m, int tile_log2) { return m < 0 || m > 27 || !fft_tile_ok(tile_log2) ? 0 : tdx::fft::passes_of(m, tile_log2); }
+extern "C" int tdx_test_fft_c2c(const float* x_dev, long n, int batch, int inverse, float* y_dev, void* ws, size_t ws_bytes, void* stream, int tile_log2) {
+    if (!x_dev || !y_dev || !ws || x_dev == y_dev) return tdx::fail(TDX_E_INVALID, "tdx_test_fft_c2c: need x_dev, y_dev, ws, x_dev != y_dev");
+    if (const char* e = tdx::fft::size_error(n, batch)) return tdx::fail(TDX_E_INVALID, std::string("tdx_test_fft_c2c: ") + e);
+    if (!fft_tile_ok(tile_log2)) return tdx::fail(TDX_E_INVALID, "tdx_test_fft_c2c: need 4 <= tile_log2 <= 12");
+    if (ws_bytes < tdx_test_fft_workspace_bytes(n, batch, tile_log2)) return tdx::fail(TDX_E_INVALID, "tdx_test_fft_c2c: workspace too small");
+    return tdx::fft::c2c(x_dev, n, batch, inverse != 0, y_dev, (float*)ws, tile_log2, (hipStream_t)stream);
 }
 
 // the noise of Whisper's sampled decoding as the vocabulary head computes it (whisper_noise.hpp): tests/test_gpu_whisper_fallback.py
